@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: HiFiGAN-V1 generator inference, 22.05 kHz audio samples / second.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last step's waveform if --dump-outputs is given
+(DIR/wav.npy, float32, rank 0's replica) and prints one JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step and
+the workload's description.  Everything else -- the roofline block, the other precision, the length sensitivity, the training and
+FastSpeech2 legs and the CPU baselines -- is measured only with --full (the --no-* switches then leave legs out).
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE in the environment), or started bare -- then this process, WITHOUT touching the GPU, starts that launcher as a
@@ -15,7 +20,7 @@ init with weight norm folded; one step = one generator forward = 32 x 768 x 256 
 Inference does not shard anything between GPUs ("replicas only"): N ranks run N
 independent replicas, `value` is the sum over ranks, scaling is weak.
 
-The JSON line carries, besides the driver's contract fields:
+With --full the JSON line carries, besides the driver's contract fields:
   roofline      the dominant kernel family of the forward, timed live with HIP events on the launch
                 stream (evmi_generator_forward_profiled); achieved = algorithmic FLOP per launch /
                 mean launch duration, against the dense bf16 MFMA peak (2.5 PFLOP/s)
@@ -45,6 +50,7 @@ HOP = 256
 MFMA_PEAK_TFLOPS_BF16 = 2500.0  # dense; /opt/skills/guides/MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
 METRIC = "hifigan_v1_infer_audio_samples_per_sec"
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: all files together
 
 
 def parse_args(argv=None):
@@ -52,6 +58,11 @@ def parse_args(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: roofline block, other precision, length sensitivity, training and "
+                        "FastSpeech2 legs, CPU baselines (a plain run measures the headline alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the waveform the last timed step computed to DIR/wav.npy (float32; rank 0)")
     p.add_argument("--batch", type=int, default=B_PER_GPU)
     p.add_argument("--frames", type=int, default=T_FRAMES)
     p.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
@@ -72,7 +83,10 @@ def parse_args(argv=None):
     p.add_argument("--selftest-cpu", action="store_true",
                    help="launcher self-test: ranks rendezvous over gloo on the CPU, time a dummy step and report the rank count "
                         "(tests/test_bench_dist.py; measures nothing)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port() -> int:
@@ -186,6 +200,22 @@ def synthetic_mel(batch: int, frames: int, seed: int):
 
     g = torch.Generator().manual_seed(seed)
     return (torch.randn(batch, 80, frames, generator=g) * 2.0 - 5.0).clamp(-11.5129, 2.0)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every tensor as DIR/<name>.npy in float32, DUMP_BYTES_MAX in all.  A tensor larger than its share is written
+    as every k-th element of its flattened values (the smallest k that fits; a fixed sample, the same from run to run)."""
+    import numpy as np
+    import torch
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", dtype=torch.float32).numpy()
+        if a.nbytes > share:
+            a = np.ascontiguousarray(a.reshape(-1)[:: -(-a.nbytes // share)])
+        np.save(d / f"{name}.npy", a)
 
 
 def _median(xs):
@@ -808,11 +838,12 @@ def main(argv=None) -> int:
 
     elapsed = timed_region(step, args.steps, args.warmup, lambda: torch.cuda.synchronize(dev), barrier, max_reduce)
     value = world * samples_per_step * args.steps / elapsed
-    # the roofline block's per-kernel events: directly behind the timed region, before any other leg touches clocks or the allocator
-    roof = measured_roofline(gen, mel, elapsed / args.steps * 1e3, args.profile_passes)
+    roof, other_precision, lengths, train, fs2, fs2_train = None, None, {}, None, None, None
+    if args.full:
+        # the roofline block's per-kernel events: directly behind the timed region, before any other leg touches clocks or the allocator
+        roof = measured_roofline(gen, mel, elapsed / args.steps * 1e3, args.profile_passes)
     # the other arithmetic beside it (the reference computes in fp32; bf16 operands with fp32 accumulation are SURVEY 8(d) C2's contract)
     other = "f32" if args.precision == "bf16" else "bf16"
-    other_precision, lengths = None, {}
 
     leg_seconds = {"headline": round(time.perf_counter() - t_start, 1)}
 
@@ -829,24 +860,17 @@ def main(argv=None) -> int:
         finally:
             leg_seconds[name] = round(time.perf_counter() - t0, 1)
 
-    if not args.no_side_legs:
-        side = guarded("side_legs", _side_legs, args, other, gen, mel, samples_per_step, dev, rank, world, barrier, max_reduce)
-        other_precision, lengths = (side, {}) if isinstance(side, dict) else side
-    train = None
-    if not args.no_train:
-        train = guarded("train_leg", train_leg, args, dev, rank, world, use_dist, barrier, max_reduce)
-    fs2 = None if args.no_fs2 else guarded("fs2_leg", fs2_leg, args, dev, rank, world, barrier, max_reduce)
-    fs2_train = None if args.no_fs2 else guarded("fs2_train_leg", fs2_train_leg, args, dev, rank, world, use_dist, barrier, max_reduce)
+    if args.full:
+        if not args.no_side_legs:
+            side = guarded("side_legs", _side_legs, args, other, gen, mel, samples_per_step, dev, rank, world, barrier, max_reduce)
+            other_precision, lengths = (side, {}) if isinstance(side, dict) else side
+        if not args.no_train:
+            train = guarded("train_leg", train_leg, args, dev, rank, world, use_dist, barrier, max_reduce)
+        fs2 = None if args.no_fs2 else guarded("fs2_leg", fs2_leg, args, dev, rank, world, barrier, max_reduce)
+        fs2_train = None if args.no_fs2 else guarded("fs2_train_leg", fs2_train_leg, args, dev, rank, world, use_dist, barrier, max_reduce)
 
     result = None
     if rank == 0:
-        pmc = recorded_pmc_traffic(roof["kernel"])
-        if pmc:
-            roof["traffic"] = pmc[0]
-            roof["traffic_source"] = f"profiles/{pmc[1]} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, bytes per launch)"
-            roof["traffic_commit"] = profile_commit(ROOT / "profiles" / pmc[1])
-            roof["traffic_code"] = profile_commit(ROOT / "profiles" / pmc[1], "code")
-            roof["algorithmic_bytes_per_launch"] = round(roof["algorithmic_hbm_gbs"] * 1e9 * roof["avg_launch_ms"] * 1e-3)
         flops_per_sample = 2.0 * gen.macs_per_sample()
         result = {
             "metric": METRIC,
@@ -872,12 +896,17 @@ def main(argv=None) -> int:
             },
             "whole_job_tflops": round(value * flops_per_sample / 1e12, 2),
             "realtime_factor": round(value / 22050.0, 1),
-            "other_precision": other_precision,
-            "length_sensitivity": lengths,
-            "roofline": roof,
-            "commit": git_head(),
-            "code": code_fingerprint(),
         }
+        if args.full:
+            pmc = recorded_pmc_traffic(roof["kernel"])
+            if pmc:
+                roof["traffic"] = pmc[0]
+                roof["traffic_source"] = f"profiles/{pmc[1]} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, bytes per launch)"
+                roof["traffic_commit"] = profile_commit(ROOT / "profiles" / pmc[1])
+                roof["traffic_code"] = profile_commit(ROOT / "profiles" / pmc[1], "code")
+                roof["algorithmic_bytes_per_launch"] = round(roof["algorithmic_hbm_gbs"] * 1e9 * roof["avg_launch_ms"] * 1e-3)
+            result.update(other_precision=other_precision, length_sensitivity=lengths, roofline=roof)
+        result.update(commit=git_head(), code=code_fingerprint())
         if use_dist:
             result["rccl_ranks"] = rccl_ranks
         if train is not None:
@@ -885,7 +914,7 @@ def main(argv=None) -> int:
         if fs2 is not None:
             result["fs2"] = fs2
             result["fs2_train"] = fs2_train
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = guarded("cpu_baseline", cpu_baseline, args.cpu_frames, args.cpu_batch)
             cores = result["cpu_baseline"].get("cores", 16)
             if "value" in result["cpu_baseline"]:
@@ -896,6 +925,8 @@ def main(argv=None) -> int:
                 fs2["cpu_baseline"] = guarded("cpu_baseline_fs2", cpu_baseline_fs2, cores)
             if fs2_train is not None and "error" not in fs2_train:
                 fs2_train["cpu_baseline"] = guarded("cpu_baseline_fs2_train", cpu_baseline_fs2_train, cores)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"wav": out["wav"]})
     if use_dist:
         import torch.distributed as dist
 

@@ -272,6 +272,34 @@ def test_rank_count_mismatch_is_a_hard_error(monkeypatch, capfd):
     assert "WORLD_SIZE=4" in capfd.readouterr().err
 
 
+def test_plain_run_and_full_run_options():
+    """A plain run measures the headline alone; --full adds the other legs; --steps is the exact count of timed steps (at least 1)."""
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_float32_within_the_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs: DIR/<name>.npy in float32; a tensor past its share of the cap is written as a fixed strided sample."""
+    import numpy as np
+
+    small = torch.randn(2, 1, 300, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "d"), {"wav": small})
+    got = np.load(tmp_path / "d" / "wav.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 1, 300) and np.array_equal(got, small.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2 * 1000)
+    big = torch.arange(3000, dtype=torch.float32).reshape(3, 1000)
+    bench.dump_outputs(str(tmp_path / "e"), {"a": big, "b": big[:1, :10]})
+    a, b = np.load(tmp_path / "e" / "a.npy"), np.load(tmp_path / "e" / "b.npy")
+    assert a.nbytes + b.nbytes <= 2 * 1000 and a.dtype == np.float32
+    assert np.array_equal(a, big.reshape(-1)[::12].numpy())  # 12000 bytes into a 1000-byte share: every 12th element
+    assert np.array_equal(b, big[:1, :10].numpy())
+
+
 def test_train_base_command_devices_2_over_gloo(tmp_path, monkeypatch):
     """``train_base_command(..., devices=2)`` outside a launcher starts one rank per device running the same command
     (base_cli/interfaces.py:84-97 -> Lightning's DDP launcher).  With CPU stand-ins for the three classes (tests/ddp_stub.py) over

@@ -48,10 +48,9 @@ def test_positional_embedding_matches_reference_checkpoint_buffer():
     assert inv.shape == (128,)
     want = torch.tensor([1.0 / 10000 ** (2 * i / 256) for i in range(128)])
     torch.testing.assert_close(inv, want, rtol=1e-6, atol=0)
-    ref = Path("/root/reference/everyvoice/tests/data/test.ckpt")
-    if ref.exists():  # only in the build container
-        ck = torch.load(ref, map_location="cpu", weights_only=False)
-        torch.testing.assert_close(inv, ck["state_dict"]["position_embedding.inv_freq"], rtol=1e-6, atol=0)
+    # the checkpoint's buffer, stored as data (tests/golden/make_reference_pins.py)
+    ck_inv = torch.from_numpy(np.load(GOLD.parent / "position_inv_freq.npy"))
+    torch.testing.assert_close(inv, ck_inv, rtol=1e-6, atol=0)
 
 
 def test_default_sizes_follow_the_reference_schema():

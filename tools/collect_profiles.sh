@@ -9,7 +9,7 @@ mkdir -p $OUT
 for what in "$@"; do
   case $what in
     bench)
-      python3 $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err ;;
+      python3 $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err ;;
     stats)
       OPERANDS=bf16 GRAPH=1 bash $R/tools/prof_train.sh ${TAG}_train 10
       python3 $R/tools/trace_phases.py $OUT/${TAG}_train/${TAG}_train_kernel_trace.csv > $OUT/${TAG}_train_phases.txt
