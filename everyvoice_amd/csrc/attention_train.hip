@@ -17,6 +17,8 @@
 //   * dkv kernel: one wave owns 32 keys (K^T and V^T in registers), walks the query tiles (Q, dO, lse, D staged in LDS).
 // Each (query, key) tile is therefore recomputed twice in the backward; in exchange every output element has ONE writer and a
 // fixed summation order: the gradients are bitwise reproducible (the checkpoint / resume test relies on that).
+#include <type_traits>
+
 #include "common.h"
 
 namespace evmi {
@@ -756,6 +758,17 @@ __global__ __launch_bounds__(256, 2) void attention_train_dkv_bf16_kernel(const 
     }
 }
 
+// body(std::integral_constant<int, DH>{}) for the head dimensions built (32 / 64 / 128)
+template <class F>
+static int with_head_dim(int dh, const char* what, F&& body) {
+  switch (dh) {
+    case 128: return body(std::integral_constant<int, 128>{});
+    case 64: return body(std::integral_constant<int, 64>{});
+    case 32: return body(std::integral_constant<int, 32>{});
+  }
+  return fail(EVMI_ERR_UNSUPPORTED, std::string(what) + ": head dimension must be 32, 64 or 128");
+}
+
 // The bf16 forward without dropout; lse may be NULL (the inference forward of fs2_ops.hip: evmi_attention_cbt_bf16 runs on this
 // kernel too -- 149 -> 82 us per decoder layer against the register-staged inference kernel it replaced).
 int launch_mha_fwd_bf16_plain(const float* qkv, const int* lens, float* out, float* lse_or_null, int B, int T, int D, int heads,
@@ -786,24 +799,12 @@ int evmi_mha_fwd_f32(const float* qkv_dev, const int* lens_dev, float* out_dev, 
   const float scale = 1.f / sqrtf((float)dh);
   const dim3 grid((T + 127) / 128, heads, B);
   hipStream_t s = (hipStream_t)stream;
-#define EVMI_MHA_FWD(DH, SLOT)                                                                                                    \
-  {                                                                                                                               \
-    constexpr size_t lds = (size_t)4 * DH * 32 * sizeof(float);                                                                   \
-    static thread_local bool configured_dev[kMaxDevices][3] = {};                                                \
-    bool* configured = configured_dev[device_slot()];          \
-    if (!configured[SLOT]) {                                                                                                      \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)attention_train_fwd_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                         (int)lds));                                                                              \
-      configured[SLOT] = true;                                                                                                    \
-    }                                                                                                                             \
-    hipLaunchKernelGGL(attention_train_fwd_kernel<DH>, grid, dim3(256), lds, s, qkv_dev, lens_dev, out_dev, lse_dev, B, T, D,     \
-                       scale, p_drop, seed);                                                                                      \
-  }
-  if (dh == 128) EVMI_MHA_FWD(128, 0)
-  else if (dh == 64) EVMI_MHA_FWD(64, 1)
-  else if (dh == 32) EVMI_MHA_FWD(32, 2)
-  else return fail(EVMI_ERR_UNSUPPORTED, "mha_fwd: head dimension must be 32, 64 or 128");
-#undef EVMI_MHA_FWD
+  if (int rc = with_head_dim(dh, "mha_fwd", [&](auto c) {
+        constexpr int DH = decltype(c)::value;
+        return launch_with_lds(attention_train_fwd_kernel<DH>, grid, dim3(256), (size_t)4 * DH * 32 * sizeof(float), s, qkv_dev, lens_dev,
+                               out_dev, lse_dev, B, T, D, scale, p_drop, seed);
+      }))
+    return rc;
   EVMI_LAUNCH_CHECK("mha_fwd");
   return EVMI_OK;
 }
@@ -818,23 +819,15 @@ int evmi_mha_fwd_bf16(const float* qkv_dev, const int* lens_dev, float* out_dev,
   const float scale = 1.f / sqrtf((float)dh);
   const dim3 grid((T + 127) / 128, heads, B);
   hipStream_t s = (hipStream_t)stream;
-#define EVMI_MHA_FWD(DH)                                                                                                          \
-  {                                                                                                                               \
-    if (p_drop > 0.f && attn_drop_pairs(B, T))                                                                                    \
-      hipLaunchKernelGGL((attention_train_fwd_bf16_kernel<DH, 2>), grid, dim3(256), 0, s, qkv_dev, lens_dev, out_dev, lse_dev, B, T, D, \
-                         scale, p_drop, seed);                                                                                    \
-    else if (p_drop > 0.f)                                                                                                        \
-      hipLaunchKernelGGL((attention_train_fwd_bf16_kernel<DH, 1>), grid, dim3(256), 0, s, qkv_dev, lens_dev, out_dev, lse_dev, B, T, D, \
-                         scale, p_drop, seed);                                                                                    \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((attention_train_fwd_bf16_kernel<DH, 0>), grid, dim3(256), 0, s, qkv_dev, lens_dev, out_dev, lse_dev, B, T, D, \
-                         scale, p_drop, seed);                                                                                    \
-  }
-  if (dh == 128) EVMI_MHA_FWD(128)
-  else if (dh == 64) EVMI_MHA_FWD(64)
-  else if (dh == 32) EVMI_MHA_FWD(32)
-  else return fail(EVMI_ERR_UNSUPPORTED, "mha_fwd_bf16: head dimension must be 32, 64 or 128");
-#undef EVMI_MHA_FWD
+  const int drop = p_drop > 0.f ? (attn_drop_pairs(B, T) ? 2 : 1) : 0;
+  if (int rc = with_head_dim(dh, "mha_fwd_bf16", [&](auto c) {
+        constexpr int DH = decltype(c)::value;
+        const auto fwd = drop == 2 ? attention_train_fwd_bf16_kernel<DH, 2>
+                         : drop == 1 ? attention_train_fwd_bf16_kernel<DH, 1> : attention_train_fwd_bf16_kernel<DH, 0>;
+        hipLaunchKernelGGL(fwd, grid, dim3(256), 0, s, qkv_dev, lens_dev, out_dev, lse_dev, B, T, D, scale, p_drop, seed);
+        return EVMI_OK;
+      }))
+    return rc;
   EVMI_LAUNCH_CHECK("mha_fwd_bf16");
   return EVMI_OK;
 }
@@ -852,33 +845,18 @@ int evmi_mha_bwd_bf16(const float* qkv_dev, const int* lens_dev, const float* ou
   const long long n = (long long)B * heads * T;
   hipLaunchKernelGGL(attention_rowdot_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out_dev, dout_dev, dsum_dev, B, T, heads, dh);
   const dim3 grid((T + 127) / 128, heads, B);
-#define EVMI_MHA_BWD_DROP(DH, DROP, SLOT)                                                                                        \
-  {                                                                                                                               \
-    constexpr size_t lds = attention_dkv_bf16_lds<DH>();                                                                          \
-    static thread_local bool configured_dev[kMaxDevices][12] = {};                                               \
-    bool* configured = configured_dev[device_slot()];          \
-    if (!configured[SLOT]) {                                                                                                      \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)attention_train_dkv_bf16_kernel<DH, DROP>,                                  \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                  \
-      configured[SLOT] = true;                                                                                                    \
-    }                                                                                                                             \
-    hipLaunchKernelGGL((attention_train_dq_bf16_kernel<DH, DROP>), grid, dim3(256), 0, s, qkv_dev, lens_dev, dout_dev, lse_dev,   \
-                       dsum_dev, dqkv_dev, B, T, D, scale, p_drop, seed);                                                         \
-    hipLaunchKernelGGL((attention_train_dkv_bf16_kernel<DH, DROP>), grid, dim3(256), lds, s, qkv_dev, lens_dev, dout_dev, lse_dev,\
-                       dsum_dev, dqkv_dev, B, T, D, scale, p_drop, seed);                                                         \
-  }
-#define EVMI_MHA_BWD(DH, SLOT)                                                                                                    \
-  {                                                                                                                               \
-    if (p_drop > 0.f && attn_drop_pairs(B, T)) EVMI_MHA_BWD_DROP(DH, 2, SLOT)                                                     \
-    else if (p_drop > 0.f) EVMI_MHA_BWD_DROP(DH, 1, SLOT + 1)                                                                     \
-    else EVMI_MHA_BWD_DROP(DH, 0, SLOT + 2)                                                                                       \
-  }
-  if (dh == 128) EVMI_MHA_BWD(128, 0)
-  else if (dh == 64) EVMI_MHA_BWD(64, 3)
-  else if (dh == 32) EVMI_MHA_BWD(32, 6)
-  else return fail(EVMI_ERR_UNSUPPORTED, "mha_bwd_bf16: head dimension must be 32, 64 or 128");
-#undef EVMI_MHA_BWD
-#undef EVMI_MHA_BWD_DROP
+  const int drop = p_drop > 0.f ? (attn_drop_pairs(B, T) ? 2 : 1) : 0;
+  if (int rc = with_head_dim(dh, "mha_bwd_bf16", [&](auto c) {
+        constexpr int DH = decltype(c)::value;
+        const auto dq = drop == 2 ? attention_train_dq_bf16_kernel<DH, 2>
+                        : drop == 1 ? attention_train_dq_bf16_kernel<DH, 1> : attention_train_dq_bf16_kernel<DH, 0>;
+        const auto dkv = drop == 2 ? attention_train_dkv_bf16_kernel<DH, 2>
+                         : drop == 1 ? attention_train_dkv_bf16_kernel<DH, 1> : attention_train_dkv_bf16_kernel<DH, 0>;
+        hipLaunchKernelGGL(dq, grid, dim3(256), 0, s, qkv_dev, lens_dev, dout_dev, lse_dev, dsum_dev, dqkv_dev, B, T, D, scale, p_drop, seed);
+        return launch_with_lds(dkv, grid, dim3(256), attention_dkv_bf16_lds<DH>(), s, qkv_dev, lens_dev, dout_dev, lse_dev, dsum_dev, dqkv_dev,
+                               B, T, D, scale, p_drop, seed);
+      }))
+    return rc;
   EVMI_LAUNCH_CHECK("mha_bwd_bf16");
   return EVMI_OK;
 }
@@ -896,28 +874,16 @@ int evmi_mha_bwd_f32(const float* qkv_dev, const int* lens_dev, const float* out
   const long long n = (long long)B * heads * T;
   hipLaunchKernelGGL(attention_rowdot_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out_dev, dout_dev, dsum_dev, B, T, heads, dh);
   const dim3 grid((T + 127) / 128, heads, B);
-#define EVMI_MHA_BWD(DH, SLOT)                                                                                                    \
-  {                                                                                                                               \
-    constexpr size_t lds_q = (size_t)4 * DH * 32 * sizeof(float), lds_kv = lds_q + 128 * sizeof(float);                           \
-    static thread_local bool configured_dev[kMaxDevices][3] = {};                                                \
-    bool* configured = configured_dev[device_slot()];          \
-    if (!configured[SLOT]) {                                                                                                      \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)attention_train_dq_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                         (int)lds_q));                                                                            \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)attention_train_dkv_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                         (int)lds_kv));                                                                           \
-      configured[SLOT] = true;                                                                                                    \
-    }                                                                                                                             \
-    hipLaunchKernelGGL(attention_train_dq_kernel<DH>, grid, dim3(256), lds_q, s, qkv_dev, lens_dev, dout_dev, lse_dev, dsum_dev,  \
-                       dqkv_dev, B, T, D, scale, p_drop, seed);                                                                   \
-    hipLaunchKernelGGL(attention_train_dkv_kernel<DH>, grid, dim3(256), lds_kv, s, qkv_dev, lens_dev, dout_dev, lse_dev, dsum_dev,\
-                       dqkv_dev, B, T, D, scale, p_drop, seed);                                                                   \
-  }
-  if (dh == 128) EVMI_MHA_BWD(128, 0)
-  else if (dh == 64) EVMI_MHA_BWD(64, 1)
-  else if (dh == 32) EVMI_MHA_BWD(32, 2)
-  else return fail(EVMI_ERR_UNSUPPORTED, "mha_bwd: head dimension must be 32, 64 or 128");
-#undef EVMI_MHA_BWD
+  if (int rc = with_head_dim(dh, "mha_bwd", [&](auto c) {
+        constexpr int DH = decltype(c)::value;
+        constexpr size_t lds_q = (size_t)4 * DH * 32 * sizeof(float), lds_kv = lds_q + 128 * sizeof(float);
+        if (int rc = launch_with_lds(attention_train_dq_kernel<DH>, grid, dim3(256), lds_q, s, qkv_dev, lens_dev, dout_dev, lse_dev, dsum_dev,
+                                     dqkv_dev, B, T, D, scale, p_drop, seed))
+          return rc;
+        return launch_with_lds(attention_train_dkv_kernel<DH>, grid, dim3(256), lds_kv, s, qkv_dev, lens_dev, dout_dev, lse_dev, dsum_dev,
+                               dqkv_dev, B, T, D, scale, p_drop, seed);
+      }))
+    return rc;
   EVMI_LAUNCH_CHECK("mha_bwd");
   return EVMI_OK;
 }

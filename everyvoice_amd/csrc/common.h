@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 #include "evmi.h"
@@ -41,6 +42,47 @@ int fail(int code, const std::string& msg);
       return ::evmi::fail(EVMI_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(_e)); \
     }                                                                                          \
   } while (0)
+
+// ---- launch plumbing ------------------------------------------------------------------------
+// hipFuncAttributeMaxDynamicSharedMemorySize for `kernel` on the current device, set the first time `bytes` goes above what was
+// set there before (the record is keyed by the kernel, per device and per host thread; a linear scan of a fixed table, no lock
+// and no allocation).  A device index at or above kMaxDevices, or a full table, keeps no record: the attribute is set every time.
+constexpr int kMaxLdsKernels = 256;
+inline int ensure_dynamic_lds(const void* kernel, size_t bytes) {
+  struct Record { const void* kernel; size_t bytes; };
+  static thread_local Record records[kMaxDevices][kMaxLdsKernels];
+  static thread_local int n_records[kMaxDevices] = {};
+  int d = -1;
+  if (hipGetDevice(&d) != hipSuccess || d >= kMaxDevices) d = -1;
+  Record* r = nullptr;
+  if (d >= 0) {
+    for (int i = 0; i < n_records[d] && !r; ++i)
+      if (records[d][i].kernel == kernel) r = &records[d][i];
+    if (r && bytes <= r->bytes) return EVMI_OK;
+  }
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess)
+    return fail(EVMI_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, " + std::to_string(bytes) + "): " + hipGetErrorString(e));
+  if (r) r->bytes = bytes;
+  else if (d >= 0 && n_records[d] < kMaxLdsKernels) records[d][n_records[d]++] = Record{kernel, bytes};
+  return EVMI_OK;
+}
+
+// hipLaunchKernelGGL with `lds` bytes of dynamic LDS, the attribute set first where the launch needs it (the caller checks the launch)
+template <typename... Params, typename... Args>
+inline int launch_with_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args&&... args) {
+  if (int rc = ensure_dynamic_lds((const void*)kernel, lds)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<Args&&>(args)...);
+  return EVMI_OK;
+}
+
+// Environment switches (A/B forms and test references): the value of `name` as an integer (atoi), `dflt` where it is not set.  When
+// a switch is read is the caller's choice: a function-local static reads it once per process.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }  // set at all, whatever its value
 
 // ---- bf16 vectors ---------------------------------------------------------------------------
 typedef __bf16 bf16_t;

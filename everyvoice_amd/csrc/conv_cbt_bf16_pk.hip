@@ -20,7 +20,6 @@
 //  * The input gradient of a strided layer runs its polyphase components in one launch (grid.z), as in the fp32 kernel.
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -48,7 +47,7 @@ struct ConvPkArgs {
   int phases;
   long long wf_phase_stride;  // units
   int ph_shift[8], ph_nout[8], ph_off[8];
-  int xcd_remap, xcd_hb;  // xcd_hb: m-tiles per band of the XCD-ordered tile list (see the kernel)
+  int xcd_hb;          // m-tiles per band of the XCD-ordered tile list (see the kernel)
   // split-K: grid.x = column tiles * ksplit; split sp takes the ring steps [sp * steps_per_split, ...) and stores its raw
   // accumulators to part[sp][phase][c_out][part_ld] (part_ld = B * longest phase); conv_pk_reduce_kernel adds them in split
   // order + epilogue
@@ -263,22 +262,20 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_pk_kernel(ConvPkArgs a) 
   const int wm = wave / WN, wn = wave % WN;
   const int kh = lane >> 5, ln = lane & 31;
 
+  // Workgroups go to the eight XCDs (private L2s) round robin; every XCD takes a contiguous run of the tile list.  The list is
+  // ordered in BANDS of xcd_hb m-tiles, column by column inside a band, so a run is a compact block of tiles -- xcd_hb m-tiles
+  // by (columns / runs per band) n-tiles -- whose weight rows and window columns are each fetched into that L2 once and shared.
+  // (xcd_hb = 1 is the plain m-tile-major list: a run is one m-tile across many columns, i.e. every XCD pulls ALL the input
+  // windows through its L2 -- eight copies of the activations over the fabric, the traffic the 1024-channel layers were bound by.)
   unsigned bx = blockIdx.x, by = blockIdx.y;
-  if (a.xcd_remap) {
-    // Workgroups go to the eight XCDs (private L2s) round robin; every XCD takes a contiguous run of the tile list.  The list is
-    // ordered in BANDS of xcd_hb m-tiles, column by column inside a band, so a run is a compact block of tiles -- xcd_hb m-tiles
-    // by (columns / runs per band) n-tiles -- whose weight rows and window columns are each fetched into that L2 once and shared.
-    // (xcd_hb = 1 is the plain m-tile-major list: a run is one m-tile across many columns, i.e. every XCD pulls ALL the input
-    // windows through its L2 -- eight copies of the activations over the fabric, the traffic the 1024-channel layers were bound by.)
+  if (gridDim.x * gridDim.y >= 16) {
     const unsigned nwg = gridDim.x * gridDim.y, orig = blockIdx.x + gridDim.x * blockIdx.y;
-    if (nwg >= 16) {
-      const unsigned q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-      const unsigned L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-      const unsigned hb = (unsigned)a.xcd_hb, band = L / (hb * gridDim.x), rem = L - band * hb * gridDim.x;
-      const unsigned hcur = min(hb, gridDim.y - band * hb);
-      bx = rem / hcur;
-      by = band * hb + (rem - bx * hcur);
-    }
+    const unsigned q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
+    const unsigned L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    const unsigned hb = (unsigned)a.xcd_hb, band = L / (hb * gridDim.x), rem = L - band * hb * gridDim.x;
+    const unsigned hcur = min(hb, gridDim.y - band * hb);
+    bx = rem / hcur;
+    by = band * hb + (rem - bx * hcur);
   }
   const int g = by / a.mtiles_per_group, mt_idx = by % a.mtiles_per_group;
   const int co0 = g * a.cout_g + mt_idx * BM;
@@ -897,11 +894,6 @@ struct PkTile { int bm, bn; };
 static const PkTile kPkTiles[] = {{128, 128}, {64, 128}, {64, 64}, {32, 128}, {64, 256}, {32, 256}, {128, 256}, {128, 256}, {128, 128}, {128, 128}, {32, 512}};
 constexpr int kNumPkTiles = sizeof(kPkTiles) / sizeof(kPkTiles[0]);
 
-static int pk_env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 struct PkPlan {
   int ti;
   size_t lds;
@@ -942,10 +934,9 @@ static const char* plan_pk(ConvPkArgs& a, int cin_g, int t_in, int groups, const
   // units per item, so only items of 96 units or more are padded (with every item padded the 128 x 128 kernel's conflicts fell
   // from 31.8 % to 5.2 % of its LDS cycles, but the GAN step got 0.3 ms slower: the period discriminators' 11-34-unit items grew
   // by up to half).
-  {
-    static const int align_tp = 1;
+  if (ext >= 96) {  // (short items: the padding would cost more than the conflicts)
     const long long want_mod = ((long long)n_max * a.stride) & 15;
-    if (align_tp && ext >= 96) ext += ((want_mod - (ext & 15)) + 16) & 15;  // (short items: the padding would cost more than the conflicts)
+    ext += ((want_mod - (ext & 15)) + 16) & 15;
   }
   // pointwise stride-1 layers are packed tight (ext == t_in here): the layout the weight gradient reads too (conv_pk_common.h); a
   // single item's row is rounded up to the weight gradient's K step (nothing follows it: the pitch is free)
@@ -961,7 +952,7 @@ static const char* plan_pk(ConvPkArgs& a, int cin_g, int t_in, int groups, const
   int ti;
   // wide layers on few columns (the 1024-channel discriminator layers: 1.6-2.8 k columns): 128 x 128 tiles -- one LDS read per
   // MFMA instead of the 64 x 64 tile's two -- fill the CUs only with the contraction split over workgroups
-  static const int allow_split = pk_env_int("EVMI_PK_SPLITK", 1);
+  static const int allow_split = env_int("EVMI_PK_SPLITK", 1);
   a.ksplit = 1;
   // (flat one-item calls -- B == 1 with thousands of columns -- also split between 256 and 384 tiles: 4.2-4.7 k columns of a
   // 1024-channel layer otherwise fall to 64 x 128 tiles, 136 vs 92 us, tools/pkflat_bench.py)
@@ -980,7 +971,7 @@ static const char* plan_pk(ConvPkArgs& a, int cin_g, int t_in, int groups, const
         if (cost < best) { best = cost; ks = c; }
       }
     } else {
-      static const int split_want = pk_env_int("EVMI_PK_SPLIT_WANT", 384);
+      static const int split_want = env_int("EVMI_PK_SPLIT_WANT", 384);
       ks = (int)std::min<long long>(8, (split_want + blocks(0) - 1) / blocks(0));
       while (ks > 1 && a.kblocks / ks < split_min_kb) --ks;
     }
@@ -990,9 +981,9 @@ static const char* plan_pk(ConvPkArgs& a, int cin_g, int t_in, int groups, const
   int cand[12], nc = 0;
   // 256-column tiles for narrow layers on many columns (the generator's last stages: 65-131 k columns, 32-64 channels; half the
   // prologues / epilogues per column): measured 26.6 vs 25.3 ms per GAN step (EVMI_PK_WIDE=1 vs 0) -- kept as a switch, off
-  static const int wide = pk_env_int("EVMI_PK_WIDE", 0);
+  static const int wide = env_int("EVMI_PK_WIDE", 0);
   // weights in registers for the wide tile wherever it would be picked (EVMI_PK_ADIR=0: the LDS form, A/B)
-  static const int use_adir = pk_env_int("EVMI_PK_ADIR", 1);
+  static const int use_adir = env_int("EVMI_PK_ADIR", 1);
   if (a.ksplit > 1) { if (use_adir) cand[nc++] = 9; cand[nc++] = 0; cand[nc++] = 1; cand[nc++] = 2; cand[nc++] = 3; }
   else if (a.cout_g > 64) {
     // Measured at the FastSpeech2 decoder's shapes (32 x 814 columns; tools/debug/pk_tile_bench.py, pack + convolution):
@@ -1023,7 +1014,7 @@ static const char* plan_pk(ConvPkArgs& a, int cin_g, int t_in, int groups, const
     if ((wide || (a.B == 1 && a.stride <= 2)) && blocks(5) >= want) cand[nc++] = 5;
     cand[nc++] = 3;
   }
-  const int forced = pk_env_int("EVMI_PK_TILE", -1);
+  const int forced = env_int("EVMI_PK_TILE", -1);
   if (forced >= 0 && forced < kNumPkTiles) { cand[0] = forced; nc = 1; }
   ti = cand[0];
   const size_t two_wg = 78 * 1024, one_wg = 160 * 1024;
@@ -1051,7 +1042,6 @@ static const char* plan_pk(ConvPkArgs& a, int cin_g, int t_in, int groups, const
     while (kbs < kbs_cap && lds_of(kbs + 1, 2) <= budget) ++kbs;
     // (three slots at 2/3 of the depth measured slower on every layer: the per-step cost -- barrier, scalar bookkeeping, the
     // un-overlapped first fragment reads -- outweighs the extra step of load latency hidden)
-    if (0 && lds_of(std::max(1, kbs * 2 / 3), 3) <= budget && kbs >= 3) { nst = 3; kbs = std::max(1, kbs * 2 / 3); }
     if (adir) {  // fixed step depth (the fragment registers are indexed at compile time), two slots
       if (a.kblocks < PK_ADIR_KBS || lds_of(PK_ADIR_KBS, 2) > two_wg) { if (last) return "LDS budget"; continue; }
       kbs = PK_ADIR_KBS;
@@ -1079,7 +1069,7 @@ static const char* plan_pk(ConvPkArgs& a, int cin_g, int t_in, int groups, const
       const long long Y = a.mtiles_per_group, X = (long long)a.ntiles_n * a.ksplit, N = a.ntiles_n;
       double best = 1e300;
       a.xcd_hb = 1;
-      static const int fixed_hb = pk_env_int("EVMI_PK_XCD_HB", 0);
+      static const int fixed_hb = env_int("EVMI_PK_XCD_HB", 0);
       for (int xm = 8; xm >= 1; xm >>= 1) {
         const long long hb = (Y + xm - 1) / xm;
         if (groups > 1 && hb > 1 && (Y % hb)) continue;  // (a band must not straddle two groups)
@@ -1120,42 +1110,29 @@ struct PkInputFusion {  // what the pack applies to the input on its way in (see
   SeedArg seed = SeedArg{0ull, nullptr};
 };
 
-static int launch_pk_tile(ConvPkArgs& a, const PkPlan& pl, hipStream_t stream) {
-  static const int xcd_remap = 1;
-  a.xcd_remap = xcd_remap;
-  const size_t lds = pl.lds;
-  static thread_local size_t configured_dev[kMaxDevices][2 * kNumPkTiles] = {};
-  size_t* configured = configured_dev[device_slot()];
-#define EVMI_PK_LAUNCH_AS(BM, BN, WM, WN, ADIR, TAILS, IDX)                                                              \
-  {                                                                                                                      \
-    if (lds > configured[IDX]) {                                                                                         \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)conv_pk_kernel<BM, BN, WM, WN, ADIR, TAILS>,                       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-      configured[IDX] = lds;                                                                                             \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((conv_pk_kernel<BM, BN, WM, WN, ADIR, TAILS>), pl.grid, dim3(WM * WN * 64), lds, stream, a);      \
-  }
-#define EVMI_PK_LAUNCH(BM, BN, WM, WN, ADIR, IDX)                                                                        \
-  {                                                                                                                      \
-    if (tails) EVMI_PK_LAUNCH_AS(BM, BN, WM, WN, ADIR, true, kNumPkTiles + IDX)                                          \
-    else EVMI_PK_LAUNCH_AS(BM, BN, WM, WN, ADIR, false, IDX)                                                             \
-  }
+template <int BM, int BN, int WM, int WN, bool ADIR = false>
+static int launch_pk_as(const ConvPkArgs& a, const PkPlan& pl, bool tails, hipStream_t stream) {
+  return launch_with_lds(tails ? conv_pk_kernel<BM, BN, WM, WN, ADIR, true> : conv_pk_kernel<BM, BN, WM, WN, ADIR, false>, pl.grid,
+                         dim3(WM * WN * 64), pl.lds, stream, a);
+}
+
+static int launch_pk_tile(const ConvPkArgs& a, const PkPlan& pl, hipStream_t stream) {
   const bool tails = a.po.y && a.po.tail;
-  switch (pl.ti) {
-    case 0: EVMI_PK_LAUNCH(128, 128, 2, 2, false, 0) break;
-    case 1: EVMI_PK_LAUNCH(64, 128, 1, 4, false, 1) break;
-    case 2: EVMI_PK_LAUNCH(64, 64, 2, 2, false, 2) break;
-    case 4: EVMI_PK_LAUNCH(64, 256, 1, 4, false, 4) break;
-    case 5: EVMI_PK_LAUNCH(32, 256, 1, 4, false, 5) break;
-    case 6: EVMI_PK_LAUNCH(128, 256, 2, 2, false, 6) break;
-    case 7: EVMI_PK_LAUNCH(128, 256, 2, 4, false, 7) break;
-    case 8: EVMI_PK_LAUNCH(128, 128, 2, 4, false, 8) break;
-    case 10: EVMI_PK_LAUNCH(32, 512, 1, 4, false, 10) break;
-    case 9: EVMI_PK_LAUNCH(128, 128, 2, 2, true, 9) break;
-    default: EVMI_PK_LAUNCH(32, 128, 1, 4, false, 3) break;
+  int rc;
+  switch (pl.ti) {  // (kPkTiles order)
+    case 0: rc = launch_pk_as<128, 128, 2, 2>(a, pl, tails, stream); break;
+    case 1: rc = launch_pk_as<64, 128, 1, 4>(a, pl, tails, stream); break;
+    case 2: rc = launch_pk_as<64, 64, 2, 2>(a, pl, tails, stream); break;
+    case 4: rc = launch_pk_as<64, 256, 1, 4>(a, pl, tails, stream); break;
+    case 5: rc = launch_pk_as<32, 256, 1, 4>(a, pl, tails, stream); break;
+    case 6: rc = launch_pk_as<128, 256, 2, 2>(a, pl, tails, stream); break;
+    case 7: rc = launch_pk_as<128, 256, 2, 4>(a, pl, tails, stream); break;
+    case 8: rc = launch_pk_as<128, 128, 2, 4>(a, pl, tails, stream); break;
+    case 10: rc = launch_pk_as<32, 512, 1, 4>(a, pl, tails, stream); break;
+    case 9: rc = launch_pk_as<128, 128, 2, 2, true>(a, pl, tails, stream); break;
+    default: rc = launch_pk_as<32, 128, 1, 4>(a, pl, tails, stream); break;
   }
-#undef EVMI_PK_LAUNCH_AS
-#undef EVMI_PK_LAUNCH
+  if (rc) return rc;
   EVMI_LAUNCH_CHECK("conv_cbt_bf16_pk");
   return EVMI_OK;
 }

@@ -9,7 +9,6 @@
 // Same contract as the matrix-core kernel (evmi_conv1d_cbt_f32): columns are the flattened (b, to) index,
 // outputs may be placed on a strided grid (out_stride / out_offset) and accumulated.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "conv_cbt_direct.h"
@@ -230,7 +229,7 @@ __global__ void wgrad_cin1_final_kernel(const float* __restrict__ partial, float
 }
 
 long long wgrad_cin1_plan(int B, int c_in, int n_out, int c_out, int k, int groups) {
-  static const bool disabled = getenv("EVMI_NO_DIRECT_CONV") != nullptr;
+  static const bool disabled = env_set("EVMI_NO_DIRECT_CONV");
   if (disabled || c_in != 1 || groups != 1 || k > CIN1_KMAX || c_out > 4096) return 0;
   const long long n_total = (long long)B * n_out;
   const long long nblk = (n_total + 256 * WCIN1_COLS - 1) / (256 * WCIN1_COLS);
@@ -246,12 +245,7 @@ int launch_wgrad_cin1(const float* x, const float* dy, float* dw, float* ws, lon
   const int nblk = (int)((n_total + 256 * WCIN1_COLS - 1) / (256 * WCIN1_COLS));
   WgradCin1Args a{x, dy, ws, B, t_in, n_out, c_out, k, stride, dil, pad};
   const size_t lds = (size_t)WCIN1_CO * CIN1_KMAX * 257 * sizeof(float);
-  static thread_local bool configured[kMaxDevices] = {};
-  if (!configured[device_slot()]) {
-    EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_cin1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    configured[device_slot()] = true;
-  }
-  hipLaunchKernelGGL(wgrad_cin1_kernel, dim3(nblk, (c_out + WCIN1_CO - 1) / WCIN1_CO), dim3(256), lds, stream, a);
+  if (int rc = launch_with_lds(wgrad_cin1_kernel, dim3(nblk, (c_out + WCIN1_CO - 1) / WCIN1_CO), dim3(256), lds, stream, a)) return rc;
   EVMI_LAUNCH_CHECK("wgrad_cin1");
   const int n = c_out * k;
   hipLaunchKernelGGL(wgrad_cin1_final_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, ws, dw, n, nblk, accumulate);
@@ -261,7 +255,7 @@ int launch_wgrad_cin1(const float* x, const float* dy, float* dw, float* ws, lon
 
 long long conv_direct_plan(const ConvDirectArgs& in, int groups, int& cc, int& nchunks) {
   cc = nchunks = 0;
-  static const bool disabled = getenv("EVMI_NO_DIRECT_CONV") != nullptr;  // A/B against the matrix-core kernel
+  static const bool disabled = env_set("EVMI_NO_DIRECT_CONV");  // A/B against the matrix-core kernel
   if (groups != 1 || disabled) return 0;
   if (in.c_in == 1 && in.k <= CIN1_KMAX) return 1;
   if (in.c_out > SMALLCO_MAX) return 0;

@@ -24,8 +24,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <type_traits>
-#include <cstdio>
-#include <cstdlib>
 
 #include "common.h"
 #include "conv_cbt_direct.h"
@@ -62,9 +60,6 @@ struct ConvF32Args {
   int bf;       // 1 = bf16 operands
   int cblocks;  // ceil(cin_g / 16): 16-channel blocks of the weight fragments
   int tj, nch;  // taps per step and steps per channel step (long kernels are split over the ring steps)
-  int xcd_remap;  // 1 = XCD-aware tile order (EVMI_F32_XCD=0 switches it off for A/B runs)
-  int ablate;   // timing experiments only (EVMI_F32_ABLATE): 1 no input loads, 2 no weight loads, 4 no MFMA
-  long long* tl;  // timing experiments only (EVMI_F32_TL): s_memtime stamps of workgroup (0, 0), [step][wave][4]
 };
 
 // activation epilogue shared by the convolution kernels (the code is wave-uniform: one branch)
@@ -258,14 +253,12 @@ __global__ __launch_bounds__(256, 2) void conv_cbt_f32_mfma_kernel(ConvF32Args a
   // XCD-aware tile order: the dispatcher deals workgroups round-robin over the 8 XCDs (private L2s); give every XCD a
   // contiguous range of the (m-tile major) tile list instead, so the workgroups that share weight fragments share an L2
   unsigned bx = blockIdx.x, by = blockIdx.y;
-  if (a.xcd_remap) {
+  if (gridDim.x * gridDim.y >= 16) {
     const unsigned nwg = gridDim.x * gridDim.y, orig = blockIdx.x + gridDim.x * blockIdx.y;
-    if (nwg >= 16) {
-      const unsigned q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-      const unsigned L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-      by = L / gridDim.x;
-      bx = L - by * gridDim.x;
-    }
+    const unsigned q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
+    const unsigned L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    by = L / gridDim.x;
+    bx = L - by * gridDim.x;
   }
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ks = wave / (WM * WN), wmn = wave % (WM * WN), wm = wmn / WN, wn = wmn % WN;
@@ -347,10 +340,6 @@ __global__ __launch_bounds__(256, 2) void conv_cbt_f32_mfma_kernel(ConvF32Args a
   }
 
   const int nsteps = ((a.pairs + ps - 1) / ps) * (BF ? a.nch : 1);
-  if (a.ablate) {  // experiments read uninitialised LDS otherwise
-    for (int v = tid; v < a.nst * a.stage; v += NTHREADS) smem[v] = 0.f;
-    lds_barrier();
-  }
 
   // ---- loader: every wave brings its share of the operands of step t -> ring slot t%3 (LDS-direct, no registers).
   // Weights: the 1 KB quads of the step round-robin over the waves (SGPR base + lane offset addressing);
@@ -373,34 +362,30 @@ __global__ __launch_bounds__(256, 2) void conv_cbt_f32_mfma_kernel(ConvF32Args a
     float* sa = smem + slot * a.stage;
     float* sx = sa + a_floats;
     int issued = 0;
-    if (!(a.ablate & 2)) {
-      int u = wave;  // unit = (m-block, quad), round-robin over the four waves
+    int u = wave;  // unit = (m-block, quad), round-robin over the four waves
 #pragma unroll
-      for (int mbi = 0; mbi < MBT; ++mbi) {
-        const char* src = reinterpret_cast<const char*>(wf_tile + min(mbi, mb_last) * mb_stride + a_step);
-        float* dst = sa + mbi * nqa_pad * 64;
-        for (; u < nquads; u += 4) {
-          lds_direct_b128(reinterpret_cast<const float*>(src + (size_t)u * 1024 + lane16), dst + u * 256);
-          ++issued;
-        }
-        u -= nquads;
+    for (int mbi = 0; mbi < MBT; ++mbi) {
+      const char* src = reinterpret_cast<const char*>(wf_tile + min(mbi, mb_last) * mb_stride + a_step);
+      float* dst = sa + mbi * nqa_pad * 64;
+      for (; u < nquads; u += 4) {
+        lds_direct_b128(reinterpret_cast<const float*>(src + (size_t)u * 1024 + lane16), dst + u * 256);
+        ++issued;
       }
+      u -= nquads;
     }
-    if (!(a.ablate & 1)) {
-      const float* xr = xgrp + (long long)(c0 + wave) * ch_stride;
-      float* dstrow = sx + wave * xrow;
-      for (int r = wave; r < nrows; r += 4) {
-        const bool zero_row = r >= cbcur;
+    const float* xr = xgrp + (long long)(c0 + wave) * ch_stride;
+    float* dstrow = sx + wave * xrow;
+    for (int r = wave; r < nrows; r += 4) {
+      const bool zero_row = r >= cbcur;
 #pragma unroll
-        for (int pi = 0; pi < F32_PMAX; ++pi) {
-          if (pi >= pieces) break;
-          const float* srcp = (zero_row || so[pi] < 0) ? g_zero_line + lane : xr + so[pi];
-          if (pi * 64 + lane < xrow) lds_direct_b32(srcp, dstrow + pi * 64);
-          ++issued;
-        }
-        xr += 4 * ch_stride;
-        dstrow += 4 * xrow;
+      for (int pi = 0; pi < F32_PMAX; ++pi) {
+        if (pi >= pieces) break;
+        const float* srcp = (zero_row || so[pi] < 0) ? g_zero_line + lane : xr + so[pi];
+        if (pi * 64 + lane < xrow) lds_direct_b32(srcp, dstrow + pi * 64);
+        ++issued;
       }
+      xr += 4 * ch_stride;
+      dstrow += 4 * xrow;
     }
     return issued;
   };
@@ -413,23 +398,17 @@ __global__ __launch_bounds__(256, 2) void conv_cbt_f32_mfma_kernel(ConvF32Args a
   for (int t = 0; t < nsteps; ++t) {
     slot = slot + 1 == nst ? 0 : slot + 1;       // t % nst
     const int slot_ahead = slot == 0 ? nst - 1 : slot - 1;  // (t + nst - 1) % nst: the slot step t-1 just released
-    const bool stamp = a.tl && bx == 0 && by == 0 && t < 24;
-    long long* tl = a.tl + (t * 4 + wave) * 4;
-    if (stamp && lane == 0) tl[0] = __builtin_readcyclecounter();
     wait_vmcnt_le(n_next);  // step t has landed (this wave's part); step t+1 may still be in flight
     lds_barrier();          // ... everyone's part; slot (t+2)%3 was last read in step t-1
-    if (stamp && lane == 0) tl[1] = __builtin_readcyclecounter();
     {
       const int issued = t + nst - 1 < nsteps ? issue(t + nst - 1, slot_ahead) : 0;
       n_next = nst == 3 ? issued : 0;  // two slots: the step just issued is the next one consumed: wait for all of it
     }
-    if (stamp && lane == 0) tl[2] = __builtin_readcyclecounter();
     if (BF) {
       const int tc = t / a.nch, j0 = (t - tc * a.nch) * a.tj, tjc = min(a.tj, k - j0);
       const int nkb = ((min(2 * ps, a.cin_g - tc * 2 * ps) + 15) >> 4) * tjc;
       const int q_lo = KS == 1 ? 0 : (ks * nkb) / KS, q_hi = KS == 1 ? nkb : ((ks + 1) * nkb) / KS;
-      if (!(a.ablate & 4)) bf_consume<MT, NT>(smem, abase, xbase, slot * a.stage, q_lo, q_hi, tjc, j0, d, xrow, acc);
-      if (stamp && lane == 0) tl[3] = __builtin_readcyclecounter();
+      bf_consume<MT, NT>(smem, abase, xbase, slot * a.stage, q_lo, q_hi, tjc, j0, d, xrow, acc);
       continue;
     }
     const int cbcur = min(2 * ps, a.cin_g - t * 2 * ps);
@@ -456,7 +435,6 @@ __global__ __launch_bounds__(256, 2) void conv_cbt_f32_mfma_kernel(ConvF32Args a
     };
     load_group(fa, fb);
     const int nfull = nq / U, rem = nq - nfull * U;
-    if (!(a.ablate & 4))
     for (int gi = 0; gi < nfull; ++gi) {
       load_group(ga, gb);  // the group after this one (past the end: in-bounds LDS, never used)
 #pragma unroll
@@ -490,7 +468,6 @@ __global__ __launch_bounds__(256, 2) void conv_cbt_f32_mfma_kernel(ConvF32Args a
           for (int nt = 0; nt < NT; ++nt)
             acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[u][mt], fb[u][nt], acc[mt][nt], 0, 0, 0);
       }
-    if (stamp && lane == 0) tl[3] = __builtin_readcyclecounter();
   }
 
   // ---- K-split partial tiles: waves ks > 0 hand their accumulators to wave ks == 0 through LDS ----
@@ -585,14 +562,12 @@ __global__ __launch_bounds__(256, 2) void conv_cbt_f32_mfma_wp_kernel(ConvF32Arg
   // XCD-aware tile order: the dispatcher deals workgroups round-robin over the 8 XCDs (private L2s); give every XCD a
   // contiguous range of the (m-tile major) tile list instead, so the workgroups that share weight fragments share an L2
   unsigned bx = blockIdx.x, by = blockIdx.y;
-  if (a.xcd_remap) {
+  if (gridDim.x * gridDim.y >= 16) {
     const unsigned nwg = gridDim.x * gridDim.y, orig = blockIdx.x + gridDim.x * blockIdx.y;
-    if (nwg >= 16) {
-      const unsigned q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-      const unsigned L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-      by = L / gridDim.x;
-      bx = L - by * gridDim.x;
-    }
+    const unsigned q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
+    const unsigned L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    by = L / gridDim.x;
+    bx = L - by * gridDim.x;
   }
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ks = wave / NWN, wn = wave % NWN;
@@ -860,14 +835,7 @@ struct F32Tile { int bm, bn, ks; };
 static const F32Tile kTiles[] = {{128, 128, 1}, {64, 128, 2}, {64, 64, 4}, {32, 256, 2}, {32, 128, 4}};
 constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
 
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 static int pick_tile(const ConvF32Args& a, int groups) {
-  const int forced = -1;
-  if (forced >= 0 && forced < kNumTiles) return forced;
   const long long n_total = (long long)a.B * a.n_out;
   auto blocks = [&](int i) {
     return ((n_total + kTiles[i].bn - 1) / kTiles[i].bn) * ((a.cout_g + kTiles[i].bm - 1) / kTiles[i].bm) * groups;
@@ -905,17 +873,12 @@ static const char* plan_conv_f32(ConvF32Args& a, int groups, F32Plan& pl) {
     const int items_max = (int)std::min<long long>(a.B, (bn + nmin - 2) / nmin + 1);
     return ((bn - 1) * a.stride + (items_max - 1) * std::max(halo - a.stride, 0) + halo) | 1;
   };
-  static const bool use_wp = 1 != 0;  // wave-private rings for the K-split tiles (A/B switch)
   int ti = pick_tile(a, groups);
-  if (a.bf) {
-    const int ft = -1;
-    if (ft >= 0 && ft < kNumTiles) ti = ft;
-  }
   // wave-private rings (K-split tiles): every wave stages only its own column slice, but a workgroup holds 8 slots:
   // taken where one step of one wave fits 1/8 of the LDS budget; long kernels (the 41-tap scale-discriminator layers)
   // keep the shared ring
   auto wp_fits = [&](int t) {
-    if (!use_wp || kTiles[t].ks <= 1) return false;
+    if (kTiles[t].ks <= 1) return false;
     const int xr = xrow_of(kTiles[t].bn / (4 / kTiles[t].ks));
     if (a.bf) {  // one 16-channel block with all its taps per wave step
       const size_t stb = (size_t)((kTiles[t].bm / 32) * a.k * 256 + 16 * xr + 4) * sizeof(float);
@@ -945,19 +908,8 @@ static const char* plan_conv_f32(ConvF32Args& a, int groups, F32Plan& pl) {
       while (ps * 2 <= ps_cap && lds_bf(ps * 2, a.k, 2) <= two_wg && (wp ? (a.pairs + 2 * ps - 1) / (2 * ps) >= ks : (ps < 16 || (ps / 8) * a.k < 2 * ks)))
         ps *= 2;
       if (!wp && lds_bf(ps, a.k, 3) <= two_wg) nst = 3;
-    } else if (!wp && 0) {  // tap-chunked steps re-stage the input window per chunk: measured slower than fp32
-      const size_t budget = lds_bf(8, 1, 2) <= two_wg ? two_wg : one_wg;
-      while (tj > 1 && lds_bf(8, tj, 2) > budget) --tj;
-      if (lds_bf(8, tj, 2) > budget) return "LDS budget";
-      const int nch = (a.k + tj - 1) / tj;
-      tj = (a.k + nch - 1) / nch;  // balanced chunks
-    } else {
+    } else {  // (tap-chunked steps, which re-stage the input window per chunk, were measured slower than fp32)
       return "LDS budget";
-    }
-    {  // tuning overrides (experiments)
-      const int fps = 0, fnst = 0;
-      if (fps >= 8 && fps % 8 == 0 && tj == a.k) ps = std::min(fps, ((a.pairs + 7) / 8) * 8);
-      if (!wp && (fnst == 2 || fnst == 3)) nst = fnst;
     }
     a.ps = ps; a.tj = tj; a.nch = (a.k + tj - 1) / tj; a.nst = nst;
     a.stage = stage_bf(ps, tj);
@@ -988,10 +940,6 @@ static const char* plan_conv_f32(ConvF32Args& a, int groups, F32Plan& pl) {
   // overhead) when three would leave less than ~24 K pairs of work per wave and step
   int nst = 3, ps = deepest(3);
   if (wp || lds_bytes(ps, 3) > 78 * 1024 || (ps * a.k < 24 * ks && deepest(2) > ps)) { nst = 2; ps = deepest(2); }
-  const int forced_nst = 0;
-  if (!wp && (forced_nst == 2 || forced_nst == 3)) { nst = forced_nst; ps = deepest(nst); }
-  const int forced_ps = 0;
-  if (forced_ps > 0 && lds_bytes(forced_ps, nst) <= 160 * 1024) ps = forced_ps;
   a.nst = nst;
   a.ps = ps;
   a.stage = stage_floats(ps);
@@ -1008,89 +956,33 @@ static const char* plan_conv_f32(ConvF32Args& a, int groups, F32Plan& pl) {
   return nullptr;
 }
 
-static int dispatch_conv_f32(ConvF32Args a, const F32Plan& pl, hipStream_t stream) {
-  const int ti = pl.ti;
-  const size_t lds = pl.lds;
+// the instantiation of tile ti (kTiles order) for the shared or the wave-private ring
+typedef void (*F32Kernel)(ConvF32Args);
+template <bool BF>
+static F32Kernel f32_kernel(int ti, bool wp) {
+  if (wp) {
+    switch (ti) {
+      case 1: return conv_cbt_f32_mfma_wp_kernel<64, 64, 2, 2, BF>;
+      case 2: return conv_cbt_f32_mfma_wp_kernel<64, 64, 1, 4, BF>;
+      case 3: return conv_cbt_f32_mfma_wp_kernel<32, 128, 2, 2, BF>;
+      default: return conv_cbt_f32_mfma_wp_kernel<32, 128, 1, 4, BF>;
+    }
+  }
+  switch (ti) {
+    case 0: return conv_cbt_f32_mfma_kernel<128, 128, 2, 2, 1, BF>;
+    case 1: return conv_cbt_f32_mfma_kernel<64, 128, 1, 2, 2, BF>;
+    case 2: return conv_cbt_f32_mfma_kernel<64, 64, 1, 1, 4, BF>;
+    case 3: return conv_cbt_f32_mfma_kernel<32, 256, 1, 2, 2, BF>;
+    default: return conv_cbt_f32_mfma_kernel<32, 128, 1, 1, 4, BF>;
+  }
+}
+
+static int dispatch_conv_f32(const ConvF32Args& a, const F32Plan& pl, hipStream_t stream) {
   dim3 grid = pl.grid;
   grid.z = a.phases;
-  const int bm = kTiles[ti].bm, bn = kTiles[ti].bn, ks = kTiles[ti].ks;
-  a.ablate = 0;
-  static const int xcd_remap = 1;
-  a.xcd_remap = xcd_remap;
-  a.tl = nullptr;
-  const bool want_tl = 0 != 0;
-  if (want_tl) {
-    EVMI_HIP_CHECK(hipMalloc(&a.tl, 24 * 4 * 4 * sizeof(long long)));
-    EVMI_HIP_CHECK(hipMemsetAsync(a.tl, 0, 24 * 4 * 4 * sizeof(long long), stream));
-  }
-
-  static thread_local size_t configured_dev[kMaxDevices][4 * kNumTiles] = {};
-  size_t* configured = configured_dev[device_slot()];
-#define EVMI_F32_LAUNCH1(BM, BN, WM, WN, KS, BFM, IDX)                                                             \
-  {                                                                                                                \
-    if (lds > configured[IDX]) {                                                                                   \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)conv_cbt_f32_mfma_kernel<BM, BN, WM, WN, KS, BFM>,           \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-      configured[IDX] = lds;                                                                                       \
-    }                                                                                                              \
-    hipLaunchKernelGGL((conv_cbt_f32_mfma_kernel<BM, BN, WM, WN, KS, BFM>), grid, dim3(256), lds, stream, a);      \
-  }
-#define EVMI_F32_LAUNCH(BM, BN, WM, WN, KS, IDX)                                                                   \
-  {                                                                                                                \
-    if (a.bf) EVMI_F32_LAUNCH1(BM, BN, WM, WN, KS, true, IDX + 2 * kNumTiles)                                      \
-    else EVMI_F32_LAUNCH1(BM, BN, WM, WN, KS, false, IDX)                                                          \
-  }
-#define EVMI_F32_LAUNCH_WP1(BM, BNW, NWN, KS, BFM, IDX)                                                            \
-  {                                                                                                                \
-    if (lds > configured[IDX]) {                                                                                   \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)conv_cbt_f32_mfma_wp_kernel<BM, BNW, NWN, KS, BFM>,          \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-      configured[IDX] = lds;                                                                                       \
-    }                                                                                                              \
-    hipLaunchKernelGGL((conv_cbt_f32_mfma_wp_kernel<BM, BNW, NWN, KS, BFM>), grid, dim3(256), lds, stream, a);     \
-  }
-#define EVMI_F32_LAUNCH_WP(BM, BNW, NWN, KS, IDX)                                                                  \
-  {                                                                                                                \
-    if (a.bf) EVMI_F32_LAUNCH_WP1(BM, BNW, NWN, KS, true, IDX + 2 * kNumTiles)                                     \
-    else EVMI_F32_LAUNCH_WP1(BM, BNW, NWN, KS, false, IDX)                                                         \
-  }
-  if (pl.wp) {
-    switch (ti) {
-      case 1: EVMI_F32_LAUNCH_WP(64, 64, 2, 2, 5) break;
-      case 2: EVMI_F32_LAUNCH_WP(64, 64, 1, 4, 6) break;
-      case 3: EVMI_F32_LAUNCH_WP(32, 128, 2, 2, 7) break;
-      default: EVMI_F32_LAUNCH_WP(32, 128, 1, 4, 8) break;
-    }
-  } else {
-    switch (ti) {
-      case 0: EVMI_F32_LAUNCH(128, 128, 2, 2, 1, 0) break;
-      case 1: EVMI_F32_LAUNCH(64, 128, 1, 2, 2, 1) break;
-      case 2: EVMI_F32_LAUNCH(64, 64, 1, 1, 4, 2) break;
-      case 3: EVMI_F32_LAUNCH(32, 256, 1, 2, 2, 3) break;
-      default: EVMI_F32_LAUNCH(32, 128, 1, 1, 4, 4) break;
-    }
-  }
-#undef EVMI_F32_LAUNCH_WP
-#undef EVMI_F32_LAUNCH_WP1
-#undef EVMI_F32_LAUNCH
-#undef EVMI_F32_LAUNCH1
+  const F32Kernel kernel = a.bf ? f32_kernel<true>(pl.ti, pl.wp) : f32_kernel<false>(pl.ti, pl.wp);
+  if (int rc = launch_with_lds(kernel, grid, dim3(256), pl.lds, stream, a)) return rc;
   EVMI_LAUNCH_CHECK("conv_cbt_f32_mfma");
-  if (want_tl) {  // stamps of workgroup (0,0): per step and wave: arrive, past barrier, loads issued, MFMAs done (100 MHz ticks)
-    long long h[24 * 4 * 4];
-    EVMI_HIP_CHECK(hipStreamSynchronize(stream));
-    EVMI_HIP_CHECK(hipMemcpy(h, a.tl, sizeof(h), hipMemcpyDeviceToHost));
-    EVMI_HIP_CHECK(hipFree(a.tl));
-    fprintf(stderr, "[f32 timeline] tile %dx%d ks %d ps %d k %d xrow %d grid %u x %u\n", bm, bn, ks, a.ps, a.k, a.xrow, grid.x, grid.y);
-    const long long t0 = h[0];
-    for (int t = 0; t < 24 && h[(t * 4) * 4]; ++t) {
-      fprintf(stderr, "  step %2d:", t);
-      for (int w = 0; w < 4; ++w) {
-        const long long* e = h + (t * 4 + w) * 4;
-        fprintf(stderr, "  w%d %6lld +%4lld +%4lld +%5lld", w, e[0] - t0, e[1] - e[0], e[2] - e[1], e[3] - e[2]);
-      }
-      fprintf(stderr, "\n");
-    }
-  }
   return EVMI_OK;
 }
 

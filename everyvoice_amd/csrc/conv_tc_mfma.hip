@@ -12,8 +12,6 @@
 //   D: lane l holds output row l&31, channels 8*(reg>>2) + 4*(l>>5) + (reg&3): four consecutive
 //      channels per register quad -> packed to 4 x bf16 and staged through LDS so the global
 //      stores (and the residual / accumulate loads) are full 16-B, row-contiguous accesses.
-#include <cstdlib>
-
 #include "conv_tc_dma_kernel.h"
 #include "conv_tc_kernel.h"
 
@@ -101,10 +99,7 @@ static const ConvTcEntry* conv_dma_table(int* n) {
 }
 
 const ConvTcLaunch* find_conv_tc(int c_in, int c_out, int ks, int dil) {
-  static const bool use_dma = [] {
-    const char* e = getenv("EVMI_CONV_DMA");
-    return !(e && e[0] == '0');
-  }();
+  static const bool use_dma = env_int("EVMI_CONV_DMA", 1) != 0;
   if (use_dma) {
     int nd = 0;
     const ConvTcEntry* d = conv_dma_table(&nd);
@@ -125,27 +120,13 @@ int launch_conv_tc(const ConvTcLaunch* L, const ConvTcArgs& a, int B, hipStream_
   // (1 x 400 frames: 1.13 -> 1.00 ms per forward), the GAN step's generator (16 items of 256 / 2048 rows per stage: 32 / 128
   // workgroups; the step itself does not move, those launches are not on its critical chain).  EVMI_CONV_NARROW=0: never.
   // The bits do not depend on the tile (same K order per output element).
-  static const int narrow_on = [] {
-    const char* e = getenv("EVMI_CONV_NARROW");
-    return e ? atoi(e) : 1;
-  }();
+  static const int narrow_on = env_int("EVMI_CONV_NARROW", 1);
   if (narrow_on && !L->persistent && L->narrow && (long long)((a.n_rows + L->bn - 1) / L->bn) * B * (a.c_out / L->bm) < 256) L = L->narrow;
-  static thread_local const void* configured_dev[kMaxDevices][64];
-  static thread_local int n_configured_dev[kMaxDevices] = {};
-  const int dev_slot = device_slot();
-  const void** configured = configured_dev[dev_slot];
-  int& n_configured = n_configured_dev[dev_slot];
-  bool seen = false;
-  for (int i = 0; i < n_configured; ++i) seen |= (configured[i] == (const void*)L->kernel);
-  if (!seen) {
-    EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)L->kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)L->lds_bytes));
-    if (n_configured < 64) configured[n_configured++] = (const void*)L->kernel;
-  }
   dim3 grid((a.n_rows + L->bn - 1) / L->bn, B, a.c_out / L->bm);
   ConvTcArgs args = a;
   args.n_items = B;
   if (L->persistent) {
+    const int dev_slot = device_slot();
     static thread_local int n_cu_dev[kMaxDevices] = {};
     if (!n_cu_dev[dev_slot]) {
       int dev = 0;
@@ -158,7 +139,7 @@ int launch_conv_tc(const ConvTcLaunch* L, const ConvTcArgs& a, int B, hipStream_
     const long long total = (n_rb + 7) / 8 * 8 * grid.z;
     grid = dim3((unsigned)(total < n_cu_dev[dev_slot] ? total : n_cu_dev[dev_slot]), 1, 1);
   }
-  hipLaunchKernelGGL(L->kernel, grid, dim3(L->threads), L->lds_bytes, stream, args);
+  if (int rc = launch_with_lds(L->kernel, grid, dim3(L->threads), L->lds_bytes, stream, args)) return rc;
   EVMI_LAUNCH_CHECK(L->name);
   return EVMI_OK;
 }

@@ -18,7 +18,6 @@
 //  * Split-K over grid.z with partial tiles added in a fixed order by wgrad_pk_reduce_kernel (deterministic).
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 
 #include "common.h"
 #include "conv_pk_common.h"
@@ -312,45 +311,85 @@ struct WgradPkPlan {
   size_t lds;
   dim3 grid;
   int tgmax;
-  int wide;  // 1: the 128 x 128 tile on eight waves (wgrad_pk_kernel<5, TM, true>)
+  int wide = 0;  // 1: the 128 x 128 tile on eight waves (wgrad_pk_kernel<5, false, true>; no time-major plan takes it)
 };
 
-static int wg_env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
+// Splits of the K range: up to `want` workgroups over `tiles`, at least 8 K steps each (what pays for a workgroup's prologue and tile store)
+static int wgrad_want_splits(long long tiles, long long want, int ksteps) {
+  return (int)std::min<long long>(std::max<long long>(1, (want + tiles - 1) / tiles), std::max(1, ksteps / 8));
+}
+
+// Stages and splits of a tile plan, where the A/B overrides act on every tile: EVMI_WG_NST=2 / 3 forces the stage count where that many
+// stages fit the LDS budget, EVMI_WG_SPLITS=n > 0 the number of splits (at most one per K step).
+static void wgrad_stages_splits(WgradPkArgs& a, WgradPkPlan& pl, size_t stage_bytes, int nst, int splits) {
+  const int fn = env_int("EVMI_WG_NST", 0), fs = env_int("EVMI_WG_SPLITS", 0);
+  if ((fn == 2 || fn == 3) && fn * stage_bytes <= 160 * 1024) nst = fn;
+  if (fs > 0) splits = std::min(fs, a.ksteps);
+  a.nst = nst;
+  pl.lds = nst * stage_bytes;
+  a.steps_per_split = (a.ksteps + splits - 1) / splits;
+  pl.splits = (a.ksteps + a.steps_per_split - 1) / a.steps_per_split;  // no empty splits
 }
 
 // The 128 x 128 tile (wgrad_pk_kernel<.., true>) where both channel extents reach it, no wave splits taps or diagonal blocks, and the
 // shape still gives the chip a workgroup per CU: fills the tile geometry of `a` / `pl` (taps per workgroup <= 5) and returns true.
 // EVMI_WG_WIDE=0: never (A/B).
-static bool plan_wgrad_wide(WgradPkArgs& a, WgradPkPlan& pl, int k, int stride, int dil, int xrow_pad, long long n_groups) {
-  static const int on = wg_env_int("EVMI_WG_WIDE", 1);
-  pl.wide = 0;
+static bool plan_wgrad_wide(WgradPkArgs& a, WgradPkPlan& pl, int stride, int dil, long long n_groups) {
+  static const int on = env_int("EVMI_WG_WIDE", 1);
   if (!on || a.tap_split || a.bd_cin || a.cin_g < 128 || a.cout_g < 128) return false;
   const int tgcap = 5;
-  const int ntg = (k + tgcap - 1) / tgcap, tg = (k + ntg - 1) / ntg;
+  const int ntg = (a.k + tgcap - 1) / tgcap, tg = (a.k + ntg - 1) / ntg;
   const long long xwin = (long long)(WG_KS - 1) * stride + (long long)(tg - 1) * dil + 1;
   if (xwin > 64 * 12) return false;
-  const int xpieces = (int)((xwin + 63) / 64), xrow = xpieces * 64 + xrow_pad;
+  const int xpieces = (int)((xwin + 63) / 64), xrow = xpieces * 64 + wg_xrow_pad(stride);
   const size_t stage_bytes = (size_t)(16 * WG_YROW + 16 * xrow) * 16;
   if (2 * stage_bytes > 160 * 1024) return false;
   const int tiles_ci = (a.cin_g + 127) / 128, tiles_co = (a.cout_g + 127) / 128;
   const long long tiles = (long long)tiles_ci * ntg * tiles_co * n_groups;
-  static const long long want = wg_env_int("EVMI_WG_WIDE_WANT", 256);  // one eight-wave workgroup per CU
-  int splits = (int)std::min<long long>(std::max<long long>(1, (want + tiles - 1) / tiles), std::max(1, a.ksteps / 8));
+  static const long long want = env_int("EVMI_WG_WIDE_WANT", 256);  // one eight-wave workgroup per CU
+  int splits = wgrad_want_splits(tiles, want, a.ksteps);
   const int steps = (a.ksteps + splits - 1) / splits;
   splits = (a.ksteps + steps - 1) / steps;
   if (tiles * splits < 192) return false;  // too few workgroups for the chip: the 64 x 64 tile (four times the tiles) fills it
   a.ntg = ntg; a.tg = tg;
   a.tiles_ci = tiles_ci; a.tiles_co = tiles_co;
   a.xpieces = xpieces; a.xrow = xrow;
-  a.nst = 3 * stage_bytes <= 160 * 1024 ? 3 : 2;
-  a.steps_per_split = steps;
-  pl.lds = a.nst * stage_bytes;
+  wgrad_stages_splits(a, pl, stage_bytes, 3 * stage_bytes <= 160 * 1024 ? 3 : 2, splits);
   pl.tgmax = 5;
-  pl.splits = splits;
   pl.wide = 1;
   return true;
+}
+
+// The 64 x 64 tile on four waves for the geometry set in `a` (k, cin_g / cout_g, ksteps, tap_split): up to 8 taps per workgroup, 16
+// where the two waves of a row split them.
+static const char* plan_wgrad_tile64(WgradPkArgs& a, WgradPkPlan& pl, int stride, int dil, long long n_groups) {
+  const int tgcap = a.tap_split ? 16 : 8;
+  a.ntg = (a.k + tgcap - 1) / tgcap;
+  a.tg = (a.k + a.ntg - 1) / a.ntg;
+  const int tg_wave = a.tap_split ? (a.tg + 1) / 2 : a.tg;
+  pl.tgmax = tg_wave <= 4 ? 4 : 8;
+  a.tiles_ci = (a.cin_g + 63) / 64;
+  a.tiles_co = (a.cout_g + 63) / 64;
+  const long long xwin = (long long)(WG_KS - 1) * stride + (long long)(a.tg - 1) * dil + 1;
+  if (xwin > 64 * 12) return "input window too long";
+  a.xpieces = (int)((xwin + 63) / 64);
+  a.xrow = a.xpieces * 64 + wg_xrow_pad(stride);
+  const size_t stage_bytes = (size_t)(8 * WG_YROW + 8 * a.xrow) * 16;
+  const long long tiles = (long long)a.tiles_ci * a.ntg * a.tiles_co * n_groups;
+  static const long long want = env_int("EVMI_WG_WANT", 512);  // (A/B: workgroups a weight gradient is split up to)
+  wgrad_stages_splits(a, pl, stage_bytes, 3 * stage_bytes <= 78 * 1024 ? 3 : 2, wgrad_want_splits(tiles, want, a.ksteps));
+  if (pl.lds > 160 * 1024) return "LDS budget";
+  return nullptr;
+}
+
+// Grid (x: input-channel tiles x tap groups, y: groups x output-channel tiles, z: splits) and split-K buffer of a tile plan; rows_ci:
+// the (output, input) channel pairs of the weight gradient
+static const char* plan_wgrad_grid(WgradPkArgs& a, WgradPkPlan& pl, long long n_groups, long long rows_ci) {
+  if ((long long)a.tiles_ci * a.ntg > 0x7fffffffLL || n_groups * a.tiles_co > 65535 || pl.splits > 65535) return "grid limits";
+  pl.grid = dim3(a.tiles_ci * a.ntg, (unsigned)(n_groups * a.tiles_co), pl.splits);
+  a.split_stride = rows_ci * a.k;
+  pl.part_elems = pl.splits > 1 ? a.split_stride * pl.splits : 0;
+  return nullptr;
 }
 
 static const char* plan_wgrad_pk(WgradPkArgs& a, WgradPkPlan& pl, int B, int c_in, int t_in, int c_out, int n_out, int k, int stride, int pad,
@@ -382,84 +421,40 @@ static const char* plan_wgrad_pk(WgradPkArgs& a, WgradPkPlan& pl, int B, int c_i
   a.plane_x = (long long)B * Tq * stride;
   a.ksteps = (int)((a.plane_y + WG_KS - 1) / WG_KS);
   a.tap_split = 0; a.bd_cin = a.bd_cout = 0;
-  int splits;
-  if (plan_wgrad_wide(a, pl, k, stride, dil, wg_xrow_pad(stride), groups)) {
-    splits = pl.splits;
-  } else {
-    // taps per workgroup
-    const int tgcap = 8;
-    a.ntg = (k + tgcap - 1) / tgcap;
-    a.tg = (k + a.ntg - 1) / a.ntg;
-    pl.tgmax = a.tg <= 4 ? 4 : 8;
-    a.tiles_ci = (cin_g + 63) / 64;
-    a.tiles_co = (cout_g + 63) / 64;
-    const long long xwin = (long long)(WG_KS - 1) * stride + (long long)(a.tg - 1) * dil + 1;
-    if (xwin > 64 * 12) return "input window too long";
-    a.xpieces = (int)((xwin + 63) / 64);
-    a.xrow = a.xpieces * 64 + wg_xrow_pad(stride);
-    const size_t stage_bytes = (size_t)(8 * WG_YROW + 8 * a.xrow) * 16;
-    a.nst = 3 * stage_bytes <= 78 * 1024 ? 3 : 2;
-    const int fn = wg_env_int("EVMI_WG_NST", 0);
-    if (fn == 2 || fn == 3) a.nst = fn;
-    pl.lds = a.nst * stage_bytes;
-    if (pl.lds > 160 * 1024) return "LDS budget";
-    const long long tiles = (long long)a.tiles_ci * a.ntg * a.tiles_co * groups;
-    static const long long want = wg_env_int("EVMI_WG_WANT", 512);  // (A/B: workgroups a weight gradient is split up to)
-    static const int min_steps = 8;  // K steps per workgroup that pay for its prologue and tile store
-    splits = (int)std::min<long long>(std::max<long long>(1, (want + tiles - 1) / tiles), std::max(1, a.ksteps / min_steps));
-    const int fs = wg_env_int("EVMI_WG_SPLITS", 0);
-    if (fs > 0) splits = std::min(fs, a.ksteps);
-    a.steps_per_split = (a.ksteps + splits - 1) / splits;
-    splits = (a.ksteps + a.steps_per_split - 1) / a.steps_per_split;  // no empty splits
-    pl.splits = splits;
-  }
-  if ((long long)a.tiles_ci * a.ntg > 0x7fffffffLL || (long long)groups * a.tiles_co > 65535 || splits > 65535) return "grid limits";
-  pl.grid = dim3(a.tiles_ci * a.ntg, groups * a.tiles_co, splits);
+  if (!plan_wgrad_wide(a, pl, stride, dil, groups))
+    if (const char* why = plan_wgrad_tile64(a, pl, stride, dil, groups)) return why;
+  if (const char* why = plan_wgrad_grid(a, pl, groups, (long long)c_out * cin_g)) return why;
   // slack: the last K step reads up to its full window past the end of the last row (the wide tile's 16 octet rows: rows past the
   // group are not staged, see the kernel)
   pl.dy_units = (long long)groups * a.octs_y * a.plane_y + WG_KS + 64;
   pl.x_units = (long long)groups * a.octs_x * a.plane_x + (long long)WG_KS * stride + a.xrow + 64;
-  a.split_stride = (long long)c_out * cin_g * k;
-  pl.part_elems = splits > 1 ? a.split_stride * splits : 0;
 
   if (pl.dy_units >= (1LL << 31) || pl.x_units >= (1LL << 31)) return "packed operands too large";
   return nullptr;
 }
 
-// the packed-operand instantiations (one attribute cache for every caller: the attribute belongs to the kernel, not to the call site)
-static int wg_xcd_order() {
-  static const int on = wg_env_int("EVMI_WG_XCD", 1);
-  return on;
-}
-
-static int launch_wgrad_packed(const WgradPkArgs& a_in, const WgradPkPlan& pl, hipStream_t s) {
-  WgradPkArgs a = a_in;
-  a.xcd = wg_xcd_order();
-  static thread_local size_t configured_dev[kMaxDevices][2] = {};
-  size_t* configured = configured_dev[device_slot()];
-  const size_t lds = pl.lds;
-  if (pl.wide) {
-    static thread_local size_t wide_lds[kMaxDevices] = {};
-    size_t& cfg = wide_lds[device_slot()];
-    if (lds > cfg) {
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_pk_kernel<5, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      cfg = lds;
-    }
-    hipLaunchKernelGGL((wgrad_pk_kernel<5, false, true>), pl.grid, dim3(512), lds, s, a);
-  } else if (pl.tgmax == 4) {
-    if (lds > configured[0]) {
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_pk_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured[0] = lds;
-    }
-    hipLaunchKernelGGL((wgrad_pk_kernel<4>), pl.grid, dim3(256), lds, s, a);
-  } else {
-    if (lds > configured[1]) {
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_pk_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured[1] = lds;
-    }
-    hipLaunchKernelGGL((wgrad_pk_kernel<8>), pl.grid, dim3(256), lds, s, a);
-  }
+// The weight-gradient kernel of a plan (tm: time-major operands) into dw -- through the split-K buffer `part` and the ordered reduce
+// where the plan splits K
+static int launch_wgrad(WgradPkArgs a, const WgradPkPlan& pl, bool tm, float* dw, float* part, int accumulate, hipStream_t s) {
+  static const int xcd = env_int("EVMI_WG_XCD", 1);
+  a.xcd = xcd;
+  a.out = pl.splits > 1 ? part : dw;
+  a.accumulate = pl.splits > 1 ? 0 : accumulate;
+  a.partial = pl.splits > 1;
+  const auto kernel = pl.wide ? wgrad_pk_kernel<5, false, true>
+                      : pl.tgmax == 4 ? (tm ? wgrad_pk_kernel<4, true> : wgrad_pk_kernel<4>)
+                                      : (tm ? wgrad_pk_kernel<8, true> : wgrad_pk_kernel<8>);
+  if (int rc = launch_with_lds(kernel, pl.grid, dim3(pl.wide ? 512 : 256), pl.lds, s, a)) return rc;
   EVMI_LAUNCH_CHECK("wgrad_pk_kernel");
+  if (pl.splits == 1) return EVMI_OK;
+  const long long rows_ci = a.split_stride / a.k;  // (co, ci) pairs of dw
+  if (rows_ci >= 131072)  // enough of them to fill the chip with one workgroup per 256: coalesced both ways
+    hipLaunchKernelGGL(wgrad_pk_reduce_kernel, dim3((unsigned)((rows_ci + 255) / 256)), dim3(256), (size_t)a.k * 256 * sizeof(float), s, part,
+                       dw, rows_ci, a.k, pl.splits, a.split_stride, accumulate);
+  else
+    hipLaunchKernelGGL(wgrad_pk_reduce_planes_kernel, dim3((unsigned)((rows_ci + 255) / 256), a.k), dim3(256), 0, s, part, dw, rows_ci, a.k,
+                       pl.splits, a.split_stride, accumulate);
+  EVMI_LAUNCH_CHECK("wgrad_pk_reduce_kernel");
   return EVMI_OK;
 }
 
@@ -531,37 +526,9 @@ static const char* plan_wgrad_tm(WgradPkArgs& a, WgradPkPlan& pl, long long rows
   pl.octs_y = a.octs_y = c_out / 8;
   pl.octs_x = a.octs_x = c_in / 8;
   a.ksteps = (int)((rows + WG_KS - 1) / WG_KS);
-  int splits;
   // (the 128 x 128 tile loses on the generator's time-major layers: c128 / k11 54 -> 58 us, c256 unchanged -- tools/bench_wgrad_bf16.py)
-  pl.wide = 0;
-  if (false) {
-  } else {
-    const int tgcap = 8;
-    a.ntg = (k + tgcap - 1) / tgcap;
-    a.tg = (k + a.ntg - 1) / a.ntg;
-    pl.tgmax = a.tg <= 4 ? 4 : 8;
-    a.tiles_ci = (c_in + 63) / 64;
-    a.tiles_co = (c_out + 63) / 64;
-    const long long xwin = (long long)(WG_KS - 1) + (long long)(a.tg - 1) * dil + 1;
-    if (xwin > 64 * 12) return "input window too long";
-    a.xpieces = (int)((xwin + 63) / 64);
-    a.xrow = a.xpieces * 64 + 4;
-    const size_t stage_bytes = (size_t)(8 * WG_YROW + 8 * a.xrow) * 16;
-    a.nst = 3 * stage_bytes <= 78 * 1024 ? 3 : 2;
-    pl.lds = a.nst * stage_bytes;
-    if (pl.lds > 160 * 1024) return "LDS budget";
-    const long long tiles = (long long)a.tiles_ci * a.ntg * a.tiles_co;
-    const long long want = 512;
-    splits = (int)std::min<long long>(std::max<long long>(1, (want + tiles - 1) / tiles), std::max(1, a.ksteps / 8));
-    a.steps_per_split = (a.ksteps + splits - 1) / splits;
-    splits = (a.ksteps + a.steps_per_split - 1) / a.steps_per_split;
-    pl.splits = splits;
-  }
-  if (splits > 65535) return "grid limits";
-  pl.grid = dim3(a.tiles_ci * a.ntg, a.tiles_co, splits);
-  a.split_stride = (long long)c_out * c_in * k;
-  pl.part_elems = splits > 1 ? a.split_stride * splits : 0;
-  return nullptr;
+  if (const char* why = plan_wgrad_tile64(a, pl, 1, dil, 1)) return why;
+  return plan_wgrad_grid(a, pl, 1, (long long)c_out * c_in);
 }
 
 long long evmi_conv1d_wgrad_tm_bf16_ws_elems(long long rows, int c_in, int c_out, int k, int dil) {
@@ -583,47 +550,8 @@ int evmi_conv1d_wgrad_tm_bf16(const void* x_tm, const void* dy_tm, float* dw_dev
   a.dy_tm = reinterpret_cast<const __bf16*>(dy_tm);
   a.x_tm = reinterpret_cast<const __bf16*>(x_tm);
   a.cy_row = c_out; a.cx_row = c_in; a.x_row_off = -(long long)pad;
-  a.out = pl.splits > 1 ? ws_dev : dw_dev;
-  a.accumulate = pl.splits > 1 ? 0 : accumulate;
-  a.partial = pl.splits > 1;
   a.c_out = c_out;
-  a.xcd = wg_xcd_order();
-  static thread_local size_t configured_dev[kMaxDevices][2] = {};
-  size_t* configured = configured_dev[device_slot()];
-  const size_t lds = pl.lds;
-  if (pl.wide) {
-    static thread_local size_t wide_lds[kMaxDevices] = {};
-    size_t& cfg = wide_lds[device_slot()];
-    if (lds > cfg) {
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_pk_kernel<5, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      cfg = lds;
-    }
-    hipLaunchKernelGGL((wgrad_pk_kernel<5, true, true>), pl.grid, dim3(512), lds, s, a);
-  } else if (pl.tgmax == 4) {
-    if (lds > configured[0]) {
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_pk_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured[0] = lds;
-    }
-    hipLaunchKernelGGL((wgrad_pk_kernel<4, true>), pl.grid, dim3(256), lds, s, a);
-  } else {
-    if (lds > configured[1]) {
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)wgrad_pk_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured[1] = lds;
-    }
-    hipLaunchKernelGGL((wgrad_pk_kernel<8, true>), pl.grid, dim3(256), lds, s, a);
-  }
-  EVMI_LAUNCH_CHECK("wgrad_tm_kernel");
-  if (pl.splits > 1) {
-    const long long rows_ci = (long long)c_out * c_in;
-    if (rows_ci >= 131072)
-      hipLaunchKernelGGL(wgrad_pk_reduce_kernel, dim3((unsigned)((rows_ci + 255) / 256)), dim3(256), (size_t)k * 256 * sizeof(float), s, ws_dev,
-                         dw_dev, rows_ci, k, pl.splits, a.split_stride, accumulate);
-    else
-      hipLaunchKernelGGL(wgrad_pk_reduce_planes_kernel, dim3((unsigned)((rows_ci + 255) / 256), k), dim3(256), 0, s, ws_dev, dw_dev, rows_ci, k,
-                         pl.splits, a.split_stride, accumulate);
-    EVMI_LAUNCH_CHECK("wgrad_tm_reduce");
-  }
-  return EVMI_OK;
+  return launch_wgrad(a, pl, true, dw_dev, ws_dev, accumulate, s);
 }
 
 // ---- flat packed operands (the discriminator chains): dy one long row of n_items * T_dy units per channel octet, x one of
@@ -651,39 +579,11 @@ static const char* plan_wgrad_flat(WgradPkArgs& a, WgradPkPlan& pl, int& sgroups
   a.ksteps = (int)((n_pos + WG_KS - 1) / WG_KS);
   // one 32-column tile of input channels (or two 32 x 32 groups on the diagonal): the waves of a row split the taps -- up to 16 per
   // workgroup, 8 per wave, half the workgroups staging the same windows (EVMI_WG_TAPSPLIT=0: off)
-  static const int tap_split_on = wg_env_int("EVMI_WG_TAPSPLIT", 1);
+  static const int tap_split_on = env_int("EVMI_WG_TAPSPLIT", 1);
   a.tap_split = !tap_split_on ? 0 : (cin_g <= 32 ? 1 : (a.bd_cin == 32 && a.bd_cout == 32 && cin_g == 64 && cout_g == 64 ? 2 : 0));
-  int splits;
-  if (plan_wgrad_wide(a, pl, k, stride, dil, wg_xrow_pad(stride), sgroups)) {
-    splits = pl.splits;
-  } else {
-    const int tgcap = a.tap_split ? 16 : 8;
-    a.ntg = (k + tgcap - 1) / tgcap;
-    a.tg = (k + a.ntg - 1) / a.ntg;
-    const int tg_wave = a.tap_split ? (a.tg + 1) / 2 : a.tg;
-    pl.tgmax = tg_wave <= 4 ? 4 : 8;
-    a.tiles_ci = (cin_g + 63) / 64;
-    a.tiles_co = (cout_g + 63) / 64;
-    const long long xwin = (long long)(WG_KS - 1) * stride + (long long)(a.tg - 1) * dil + 1;
-    if (xwin > 64 * 12) return "input window too long";
-    a.xpieces = (int)((xwin + 63) / 64);
-    a.xrow = a.xpieces * 64 + wg_xrow_pad(stride);
-    const size_t stage_bytes = (size_t)(8 * WG_YROW + 8 * a.xrow) * 16;
-    a.nst = 3 * stage_bytes <= 78 * 1024 ? 3 : 2;
-    pl.lds = a.nst * stage_bytes;
-    if (pl.lds > 160 * 1024) return "LDS budget";
-    const long long tiles = (long long)a.tiles_ci * a.ntg * a.tiles_co * sgroups;
-    const long long want = 512;
-    splits = (int)std::min<long long>(std::max<long long>(1, (want + tiles - 1) / tiles), std::max(1, a.ksteps / 8));
-    a.steps_per_split = (a.ksteps + splits - 1) / splits;
-    splits = (a.ksteps + a.steps_per_split - 1) / a.steps_per_split;
-    pl.splits = splits;
-  }
-  if ((long long)a.tiles_ci * a.ntg > 0x7fffffffLL || (long long)sgroups * a.tiles_co > 65535 || splits > 65535) return "grid limits";
-  pl.grid = dim3(a.tiles_ci * a.ntg, sgroups * a.tiles_co, splits);
-  a.split_stride = (long long)c_out * (c_in / groups) * k;
-  pl.part_elems = splits > 1 ? a.split_stride * splits : 0;
-  return nullptr;
+  if (!plan_wgrad_wide(a, pl, stride, dil, sgroups))
+    if (const char* why = plan_wgrad_tile64(a, pl, stride, dil, sgroups)) return why;
+  return plan_wgrad_grid(a, pl, sgroups, (long long)c_out * (c_in / groups));
 }
 
 long long evmi_conv_pkflat_wgrad_ws_elems(int n_items, int T_dy, int c_in, int c_out, int k, int stride, int dil, int groups) {
@@ -709,22 +609,8 @@ int evmi_conv_pkflat_wgrad(const void* x_pk, long long x_plane, const void* dy_p
   a.xp = reinterpret_cast<const uint4*>(x_pk);
   a.plane_y = dy_plane; a.plane_x = x_plane;
   a.x_unit_off = -(long long)pad;
-  a.out = pl.splits > 1 ? ws_dev : dw_dev;
-  a.accumulate = pl.splits > 1 ? 0 : accumulate;
-  a.partial = pl.splits > 1;
   a.c_out = c_out;
-  if (int rc = launch_wgrad_packed(a, pl, s)) return rc;
-  if (pl.splits > 1) {
-    const long long rows_ci = (long long)c_out * (c_in / groups);
-    if (rows_ci >= 131072)
-      hipLaunchKernelGGL(wgrad_pk_reduce_kernel, dim3((unsigned)((rows_ci + 255) / 256)), dim3(256), (size_t)k * 256 * sizeof(float), s, ws_dev,
-                         dw_dev, rows_ci, k, pl.splits, a.split_stride, accumulate);
-    else
-      hipLaunchKernelGGL(wgrad_pk_reduce_planes_kernel, dim3((unsigned)((rows_ci + 255) / 256), k), dim3(256), 0, s, ws_dev, dw_dev, rows_ci, k,
-                         pl.splits, a.split_stride, accumulate);
-    EVMI_LAUNCH_CHECK("wgrad_pk_reduce (flat)");
-  }
-  return EVMI_OK;
+  return launch_wgrad(a, pl, false, dw_dev, ws_dev, accumulate, s);
 }
 
 static int wgrad_pk_impl(const float* x_dev, const float* dy_dev, float* dw_dev, float* ws_dev, long long ws_elems, int B, int c_in, int t_in,
@@ -766,22 +652,8 @@ static int wgrad_pk_impl(const float* x_dev, const float* dy_dev, float* dw_dev,
   if (n_pack > 0) hipLaunchKernelGGL(pack2_kernel, dim3((unsigned)n_pack), dim3(256), 0, s, py, px);
   a.dyp = dy_packed_dev ? reinterpret_cast<const uint4*>(dy_packed_dev) : dyp;
   a.xp = x_packed_dev ? reinterpret_cast<const uint4*>(x_packed_dev) : xp;
-  a.out = pl.splits > 1 ? part : dw_dev;
-  a.accumulate = pl.splits > 1 ? 0 : accumulate;
-  a.partial = pl.splits > 1;
   a.c_out = c_out;
-  if (int rc = launch_wgrad_packed(a, pl, s)) return rc;
-  if (pl.splits > 1) {
-    const long long rows_ci = (long long)c_out * cin_g;
-    if (rows_ci >= 131072)  // enough (co, ci) pairs to fill the chip with one workgroup per 256 of them: coalesced both ways
-      hipLaunchKernelGGL(wgrad_pk_reduce_kernel, dim3((unsigned)((rows_ci + 255) / 256)), dim3(256), (size_t)k * 256 * sizeof(float), s, part,
-                         dw_dev, rows_ci, k, pl.splits, a.split_stride, accumulate);
-    else
-      hipLaunchKernelGGL(wgrad_pk_reduce_planes_kernel, dim3((unsigned)((rows_ci + 255) / 256), k), dim3(256), 0, s, part, dw_dev, rows_ci, k,
-                         pl.splits, a.split_stride, accumulate);
-    EVMI_LAUNCH_CHECK("wgrad_pk_reduce_kernel");
-  }
-  return EVMI_OK;
+  return launch_wgrad(a, pl, false, dw_dev, part, accumulate, s);
 }
 
 }  // extern "C"

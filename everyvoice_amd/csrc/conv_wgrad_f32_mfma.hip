@@ -362,24 +362,11 @@ int evmi_conv1d_wgrad_cbt_f32(const float* x_dev, const float* dy_dev, float* dw
   a.out = p.splits > 1 ? part : dw_dev;
   a.out_split_stride = p.splits > 1 ? w_elems : 0;
   const dim3 grid(p.ctiles, groups * p.mtiles, p.splits);
-  static thread_local size_t configured_dev[kMaxDevices][6] = {};
-  size_t* configured = configured_dev[device_slot()];
-#define EVMI_WG_LAUNCH(BM, WM, WN, NST, IDX)                                                                        \
-  {                                                                                                                 \
-    if (p.lds > configured[IDX]) {                                                                                  \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)conv_wgrad_f32_mfma_kernel<BM, WM, WN, NST>,                  \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));                 \
-      configured[IDX] = p.lds;                                                                                      \
-    }                                                                                                               \
-    hipLaunchKernelGGL((conv_wgrad_f32_mfma_kernel<BM, WM, WN, NST>), grid, dim3(256), p.lds, s, a);                \
-  }
-  if (p.bm == 128 && p.nst == 3) EVMI_WG_LAUNCH(128, 2, 2, 3, 0)
-  else if (p.bm == 128) EVMI_WG_LAUNCH(128, 2, 2, 2, 1)
-  else if (p.bm == 64 && p.nst == 3) EVMI_WG_LAUNCH(64, 2, 2, 3, 2)
-  else if (p.bm == 64) EVMI_WG_LAUNCH(64, 2, 2, 2, 3)
-  else if (p.nst == 3) EVMI_WG_LAUNCH(32, 1, 4, 3, 4)
-  else EVMI_WG_LAUNCH(32, 1, 4, 2, 5)
-#undef EVMI_WG_LAUNCH
+  const bool nst3 = p.nst == 3;
+  const auto kernel = p.bm == 128 ? (nst3 ? conv_wgrad_f32_mfma_kernel<128, 2, 2, 3> : conv_wgrad_f32_mfma_kernel<128, 2, 2, 2>)
+                      : p.bm == 64 ? (nst3 ? conv_wgrad_f32_mfma_kernel<64, 2, 2, 3> : conv_wgrad_f32_mfma_kernel<64, 2, 2, 2>)
+                                   : (nst3 ? conv_wgrad_f32_mfma_kernel<32, 1, 4, 3> : conv_wgrad_f32_mfma_kernel<32, 1, 4, 2>);
+  if (int rc = launch_with_lds(kernel, grid, dim3(256), p.lds, s, a)) return rc;
   EVMI_LAUNCH_CHECK("conv_wgrad_f32_mfma");
   if (p.splits > 1) {
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((w_elems + 255) / 256)), dim3(256), 0, s, part, dw_dev, w_elems, p.splits,

@@ -700,8 +700,7 @@ int evmi_generator_finalize(evmi_generator* g) {
     hipDeviceProp_t prop;
     EVMI_HIP_CHECK(hipGetDeviceProperties(&prop, g->device));
     g->n_cu = prop.multiProcessorCount;
-    const char* e = getenv("EVMI_NO_FUSED_PAIRS");  // tuning switch: fall back to two launches per pair
-    g->use_pairs = !(e && e[0] == '1');
+    g->use_pairs = env_int("EVMI_NO_FUSED_PAIRS", 0) != 1;  // tuning switch: 1 falls back to two launches per pair
   }
   EVMI_TRY(prepare_tc(g));
   g->finalized = true;

@@ -192,25 +192,12 @@ int launch_istft_head(const bf16_t* x, const bf16_t* w, const float* bias, float
   const int n_out = IS_HOP * L;
   dim3 grid((n_out + IS_SAMPLES - 1) / IS_SAMPLES, B);
   auto lds_of = [](int c) { return (size_t)((IS_FRAMES + IS_KS - 1) * (c + 8) + IS_KS * 32 * (c + 8)) * 2; };
-  static thread_local bool configured_dev[kMaxDevices][3] = {};
-  bool* configured = configured_dev[device_slot()];
-#define EVMI_ISTFT_CASE(CC, IDX)                                                                                  \
-  if (c_in == CC) {                                                                                               \
-    const size_t lds = lds_of(CC) > (size_t)IS_FRAMES * 40 * 4 ? lds_of(CC) : (size_t)IS_FRAMES * 40 * 4;        \
-    if (!configured[IDX]) {                                                                                       \
-      EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)istft_head_kernel<CC>,                                      \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-      configured[IDX] = true;                                                                                     \
-    }                                                                                                             \
-    hipLaunchKernelGGL((istft_head_kernel<CC>), grid, dim3(512), lds, s, x, w, bias, wav, L);                     \
-    EVMI_LAUNCH_CHECK("istft_head");                                                                              \
-    return EVMI_OK;                                                                                               \
-  }
-  EVMI_ISTFT_CASE(32, 0)
-  EVMI_ISTFT_CASE(64, 1)
-  EVMI_ISTFT_CASE(128, 2)
-#undef EVMI_ISTFT_CASE
-  return fail(EVMI_ERR_UNSUPPORTED, "istft_head: unsupported channel count");
+  if (c_in != 32 && c_in != 64 && c_in != 128) return fail(EVMI_ERR_UNSUPPORTED, "istft_head: unsupported channel count");
+  const size_t lds = lds_of(c_in) > (size_t)IS_FRAMES * 40 * 4 ? lds_of(c_in) : (size_t)IS_FRAMES * 40 * 4;
+  const auto kernel = c_in == 32 ? istft_head_kernel<32> : c_in == 64 ? istft_head_kernel<64> : istft_head_kernel<128>;
+  if (int rc = launch_with_lds(kernel, grid, dim3(512), lds, s, x, w, bias, wav, L)) return rc;
+  EVMI_LAUNCH_CHECK("istft_head");
+  return EVMI_OK;
 }
 
 int launch_reflect_pad_left1_f32(const float* x, float* xp, long long n_rows, int L, float slope, hipStream_t s) {

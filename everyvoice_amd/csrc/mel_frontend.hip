@@ -162,16 +162,10 @@ int launch_mel_frontend(const float* audio, const float* basis_ri, const float* 
   const int n_chunks = (n_col_tiles + max_tiles - 1) / max_tiles;
   const int chunk_tiles = (n_col_tiles + n_chunks - 1) / n_chunks;
   const size_t lds = (as_words + ls_words + (size_t)MEL_FRAMES * (16 * chunk_tiles + 1)) * sizeof(float);
-  int dev = 0;
-  EVMI_HIP_CHECK(hipGetDevice(&dev));
-  static thread_local size_t configured[16] = {0};  // per device: the attribute belongs to the device's code object
-  if (dev < 0 || dev >= 16 || lds > configured[dev]) {
-    EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)mel_frontend_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (dev >= 0 && dev < 16) configured[dev] = lds;
-  }
   dim3 grid((n_frames + MEL_FRAMES - 1) / MEL_FRAMES, B);
-  hipLaunchKernelGGL(mel_frontend_kernel, grid, dim3(MEL_THREADS), lds, s, audio, basis_ri, melb, out, energy, mag_out,
-                     n_samples, n_frames, n_fft, hop, nb_pad, n_bins, n_mels, apply_log, chunk_tiles, lens);
+  if (int rc = launch_with_lds(mel_frontend_kernel, grid, dim3(MEL_THREADS), lds, s, audio, basis_ri, melb, out, energy, mag_out, n_samples,
+                               n_frames, n_fft, hop, nb_pad, n_bins, n_mels, apply_log, chunk_tiles, lens))
+    return rc;
   EVMI_LAUNCH_CHECK("mel_frontend");
   return EVMI_OK;
 }

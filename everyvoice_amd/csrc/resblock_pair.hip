@@ -1,5 +1,4 @@
 // Instantiations and launcher of the fused residual-pair kernel (resblock_pair_kernel.h).
-#include <cstdlib>
 
 #include "resblock_branch_kernel.h"
 #include "resblock_pair_chunked_kernel.h"
@@ -39,10 +38,7 @@ static const PairLaunch* pair_table(int* n) {
 
 const PairLaunch* find_resblock_pair(int c, int ks, int dil) {
   // A/B switch: EVMI_PAIR_C128=0 routes the 128-channel k = 3 pairs to two LDS-DMA convolution launches instead
-  static const bool c128_pairs = [] {
-    const char* e = getenv("EVMI_PAIR_C128");
-    return !(e && e[0] == '0');
-  }();
+  static const bool c128_pairs = env_int("EVMI_PAIR_C128", 1) != 0;
   if (c >= 128 && !c128_pairs) return nullptr;
   int n = 0;
   const PairLaunch* t = pair_table(&n);
@@ -52,18 +48,6 @@ const PairLaunch* find_resblock_pair(int c, int ks, int dil) {
 }
 
 int launch_resblock_pair(const PairLaunch* L, PairArgs a, int B, int n_cu, hipStream_t stream) {
-  static thread_local const void* configured_dev[kMaxDevices][32];
-  static thread_local int n_configured_dev[kMaxDevices] = {};
-  const int dev_slot = device_slot();
-  const void** configured = configured_dev[dev_slot];
-  int& n_configured = n_configured_dev[dev_slot];
-  bool seen = false;
-  for (int i = 0; i < n_configured; ++i) seen |= (configured[i] == (const void*)L->kernel);
-  if (!seen) {
-    EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)L->kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)L->lds_bytes));
-    if (n_configured < 32) configured[n_configured++] = (const void*)L->kernel;
-  }
   a.tiles_per_item = (a.T + L->tt - 1) / L->tt;
   a.n_tiles = a.tiles_per_item * B;
   // persistent: one workgroup per CU (LDS-bound residency), a multiple of 8 so every XCD gets the
@@ -72,7 +56,7 @@ int launch_resblock_pair(const PairLaunch* L, PairArgs a, int B, int n_cu, hipSt
   grid = (grid + 7) / 8 * 8;
   const int needed = (a.n_tiles + 7) / 8 * 8;
   if (grid > needed) grid = needed;
-  hipLaunchKernelGGL(L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a);
+  if (int rc = launch_with_lds(L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
   EVMI_LAUNCH_CHECK(L->name);
   return EVMI_OK;
 }
@@ -107,10 +91,7 @@ static int branch_valid_rows(const BranchLaunch& L, int np, const int* dil) {
 
 const BranchLaunch* find_resblock_branch(int c, int ks, int np, const int* dil) {
   // A/B switch: EVMI_BRANCH=0 keeps the pair kernels (same bits: tests/test_gpu_generator.py compares the two)
-  static const bool enabled = [] {
-    const char* e = getenv("EVMI_BRANCH");
-    return !(e && e[0] == '0');
-  }();
+  static const bool enabled = env_int("EVMI_BRANCH", 1) != 0;
   if (!enabled) return nullptr;
   int n = 0;
   const BranchLaunch* t = branch_table(&n);
@@ -120,17 +101,6 @@ const BranchLaunch* find_resblock_branch(int c, int ks, int np, const int* dil) 
 }
 
 int launch_resblock_branch(const BranchLaunch* L, BranchArgs a, int B, int n_cu, hipStream_t stream) {
-  static thread_local const void* configured_dev[kMaxDevices][8];
-  static thread_local int n_configured_dev[kMaxDevices] = {};
-  const int dev_slot = device_slot();
-  const void** configured = configured_dev[dev_slot];
-  int& n_configured = n_configured_dev[dev_slot];
-  bool seen = false;
-  for (int i = 0; i < n_configured; ++i) seen |= (configured[i] == (const void*)L->kernel);
-  if (!seen) {
-    EVMI_HIP_CHECK(hipFuncSetAttribute((const void*)L->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L->lds_bytes));
-    if (n_configured < 8) configured[n_configured++] = (const void*)L->kernel;
-  }
   a.tt = branch_valid_rows(*L, a.np, a.dil);
   if (a.tt <= 0) return fail(EVMI_ERR_UNSUPPORTED, "resblock_branch: dilations beyond the LDS tiles");
   a.tiles_per_item = (a.T + a.tt - 1) / a.tt;
@@ -139,7 +109,7 @@ int launch_resblock_branch(const BranchLaunch* L, BranchArgs a, int B, int n_cu,
   grid = (grid + 7) / 8 * 8;
   const int needed = (a.n_tiles + 7) / 8 * 8;
   if (grid > needed) grid = needed;
-  hipLaunchKernelGGL(L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a);
+  if (int rc = launch_with_lds(L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
   EVMI_LAUNCH_CHECK(L->name);
   return EVMI_OK;
 }
