@@ -7,7 +7,9 @@ Mirrors (paths relative to the reference):
                            gate, the default SoX effect "channels 1" (mix-down), resampling, peak normalise to 0.95, truncate
                            to a multiple of the hop).  Loudness, resampling and normalisation run on the device
                            (csrc/preprocess_ops.hip; torchaudio's algorithms restated, parity unpinned: torchaudio is not in
-                           the image); other SoX effect chains are not reproduced
+                           the image).  A dataset's SoX effect chain (``sox_effects``: channels 1, norm, reverse, silence) runs
+                           on the device after the mix-down, before resampling (sox.py, csrc/sox_effects.hip); any other effect
+                           is refused with a ValueError before a file is read
   preprocess / .config-lock  preprocessor.py:974-1082 (what the lock records, when a run refuses to continue)
   compute_stats / normalize_stats  preprocessor.py:378-490 (dataset statistics of energy / pitch -> Stats, files rewritten normalised)
   create_path naming       everyvoice/preprocessor/preprocessor.py:502-508, 529-533, 633-639
@@ -31,6 +33,7 @@ import numpy as np
 import torch
 
 from .config import AudioConfig
+from .sox import DEFAULT_CHAIN, Effect, apply_sox_effects, parse_sox_effects
 from .spectral import MelSpectrogram, get_spectral_transform
 
 SEP = "--"
@@ -214,12 +217,23 @@ def gate_audio(wav_path, cfg: AudioConfig):
     return audio, sr
 
 
-def process_audio_batch(wavs: list[torch.Tensor], sr: int, cfg: AudioConfig, device, normalize: bool = True, resample_rate: int | None = None):
-    """The device part of process_audio for a batch of gated utterances at one source rate: loudness gate -> mix-down -> resample
-    -> peak normalise -> truncate to a multiple of the hop.  wavs: [channels_i, S_i] host tensors.
+def _effects(sox_effects) -> list[Effect]:
+    """A chain as written in a config (``list[list[str]]``, None) or already parsed -> effect records (ValueError if not reproduced)."""
+    if sox_effects and all(isinstance(e, Effect) for e in sox_effects):
+        return list(sox_effects)
+    return parse_sox_effects(sox_effects)
+
+
+def process_audio_batch(wavs: list[torch.Tensor], sr: int, cfg: AudioConfig, device, normalize: bool = True, resample_rate: int | None = None,
+                        sox_effects=None):
+    """The device part of process_audio for a batch of gated utterances at one source rate: loudness gate -> mix-down -> the SoX
+    effect chain ``sox_effects`` (sox.py; None, [] and the default ``[["channels", "1"]]`` are the mix-down alone) -> resample
+    -> peak normalise -> truncate to a multiple of the hop.  wavs: [channels_i, S_i] host tensors.  An utterance the chain leaves
+    shorter than one hop is skipped and counted under "audio_empty".
     -> (audio [n, t_max] on the device, lens [n] python ints (multiples of the hop), kept indices, {reason: count})."""
     from . import _lib
 
+    effects = _effects(sox_effects)
     counters: dict[str, int] = {}
     n = len(wavs)
     if n == 0:
@@ -248,6 +262,10 @@ def process_audio_batch(wavs: list[torch.Tensor], sr: int, cfg: AudioConfig, dev
         mono[j, : wavs[i].shape[1]] = wavs[i].mean(0)  # SoX "channels 1" (the reference's default effect): the channels' mean
     x = mono.to(device)
     lens = [wavs[i].shape[1] for i in kept_idx]
+    if effects:  # at the file's own rate, before resampling (preprocessor.py:187-198); lengths are read back once, here
+        x, lens_dev = apply_sox_effects(x, torch.tensor(lens, dtype=torch.int32), sr, effects)
+        lens = lens_dev.cpu().tolist()
+        x = x[:, : max(1, max(lens))].contiguous()
     if target_sr != sr:
         x = resample(x, sr, target_sr)
         g = math.gcd(sr, target_sr)
@@ -259,16 +277,26 @@ def process_audio_batch(wavs: list[torch.Tensor], sr: int, cfg: AudioConfig, dev
                                                        _lib.current_stream_ptr(x.device)), "evmi_peak_normalize_f32")
         x = y
     lens = [L // cfg.fft_hop_size * cfg.fft_hop_size for L in lens]
+    if effects and min(lens) == 0:  # trimmed to less than one hop (the reference fails there: torch.max of an empty tensor)
+        rows = [j for j, L in enumerate(lens) if L > 0]
+        counters["audio_empty"] = counters.get("audio_empty", 0) + len(lens) - len(rows)
+        if not rows:
+            return None, [], [], counters
+        x = x[torch.tensor(rows, device=x.device)].contiguous()
+        lens, kept_idx = [lens[j] for j in rows], [kept_idx[j] for j in rows]
     return x, lens, kept_idx, counters
 
 
-def process_audio(wav_path, cfg: AudioConfig, normalize: bool = True, device="cuda:0", resample_rate: int | None = None):
+def process_audio(wav_path, cfg: AudioConfig, normalize: bool = True, device="cuda:0", resample_rate: int | None = None, sox_effects=None):
     """(audio [S'] on the host, sr) with S' a multiple of the hop, or (None, reason) when the file is skipped
-    (everyvoice/preprocessor/preprocessor.py:131-218)."""
+    (everyvoice/preprocessor/preprocessor.py:131-218).  ``sox_effects``: the dataset's SoX chain (see process_audio_batch),
+    parsed before the file is read."""
+    effects = _effects(sox_effects)
     audio, info = gate_audio(wav_path, cfg)
     if audio is None:
         return None, info
-    x, lens, kept, counters = process_audio_batch([audio], info, cfg, torch.device(device), normalize, resample_rate or cfg.input_sampling_rate)
+    x, lens, kept, counters = process_audio_batch([audio], info, cfg, torch.device(device), normalize, resample_rate or cfg.input_sampling_rate,
+                                                  effects)
     if not kept:
         return None, next(iter(counters))
     return x[0, : lens[0]].cpu(), resample_rate or cfg.input_sampling_rate
@@ -308,6 +336,7 @@ class GpuPreprocessor:
                                                   self.cfg.input_sampling_rate, self.cfg.n_mels, self.cfg.f_min, self.cfg.f_max)
         self.counters: dict[str, int] = {}
         self._interp = None
+        self._source_data: dict = {}  # label -> the source_data entry of the current process() call (the .config-lock records it)
 
     def features(self, audio: torch.Tensor):
         """audio [S] (host or device) -> (log-mel [n_mels, S // hop], energy [S // hop]) on the device."""
@@ -323,16 +352,38 @@ class GpuPreprocessor:
     def get_config_lock(self, in_progress: bool = True) -> dict:
         return {"info": "This file has the configuration that was used to preprocess files. Do not edit.",
                 "status": "in progress" if in_progress else "completed",
-                "preprocessing.audio": self.cfg.model_dump(mode="json"), "preprocessing.source_data": {}, "text": {}}
+                "preprocessing.audio": self.cfg.model_dump(mode="json"), "preprocessing.source_data": dict(self._source_data), "text": {}}
 
-    def save_config_lock(self, save_dir, in_progress: bool):
+    def set_source(self, source: dict | None) -> list[Effect]:
+        """Make ``source`` (a ``preprocessing.source_data`` entry: ``label``, ``sox_effects`` (default ``[["channels", "1"]]``), ...)
+        the dataset of the next run and return its parsed chain; None: no dataset entry, the mix-down alone."""
+        if source is None:
+            self._source_data = {}
+            return []
+        if "label" not in source:
+            raise ValueError("a source_data entry needs a 'label'")
+        entry = {k: v for k, v in source.items() if k not in ("data_dir", "filelist")}  # as preprocessor.py:985-988 records it
+        entry.setdefault("sox_effects", DEFAULT_CHAIN)
+        effects = parse_sox_effects(entry["sox_effects"])
+        self._source_data = {str(source["label"]): json.loads(json.dumps(entry, default=str))}
+        return effects
+
+    def save_config_lock(self, save_dir, in_progress: bool, merge: bool = True):
+        """Write the lock; with ``merge`` the entries of the other labels an earlier run recorded there are kept."""
         save_dir = Path(save_dir)
         save_dir.mkdir(parents=True, exist_ok=True)
         lock = save_dir / ".config-lock"
+        data = self.get_config_lock(in_progress)
         if lock.exists():
+            if merge:
+                try:
+                    saved = json.loads(lock.read_text(encoding="utf8")).get("preprocessing.source_data") or {}
+                except (json.JSONDecodeError, AttributeError):
+                    saved = {}
+                data["preprocessing.source_data"] = {**saved, **data["preprocessing.source_data"]}
             lock.chmod(0o666)
         with open(lock, "w", encoding="utf8") as f:
-            json.dump(self.get_config_lock(in_progress), f, indent=2, ensure_ascii=False)
+            json.dump(data, f, indent=2, ensure_ascii=False)
             f.write("\n")
         lock.chmod(0o444)  # read-only: discourages edits
 
@@ -346,16 +397,24 @@ class GpuPreprocessor:
             return True
         if saved.get("status") != "completed":  # an interrupted run's partial results cannot be trusted
             return True
-        return saved.get("preprocessing.audio") != self.get_config_lock()["preprocessing.audio"] or saved.get("text") != {}
+        current = self.get_config_lock()
+        if saved.get("preprocessing.audio") != current["preprocessing.audio"] or saved.get("text") != {}:
+            return True
+        locked = saved.get("preprocessing.source_data") or {}  # entries of a label in both must be equal (preprocessor.py:1072-1081)
+        return any(locked[k] != v for k, v in current["preprocessing.source_data"].items() if k in locked)
 
-    def process(self, items: list[dict], save_dir, overwrite: bool = False) -> list[dict]:
+    def process(self, items: list[dict], save_dir, overwrite: bool = False, source: dict | None = None) -> list[dict]:
         """items: dicts with ``basename``, ``speaker``, ``language``, ``wav``.  Returns the items that were kept.  Utterances are
         gated on the host (file IO), then run through the device pipeline in ragged batches of ``batch_items``: loudness gate,
-        mix-down, resampling to input_sampling_rate, peak normalisation, STFT -> mel -> log + energy in ONE launch per batch."""
+        mix-down, the dataset's SoX effect chain, resampling to input_sampling_rate, peak normalisation, STFT -> mel -> log + energy
+        in ONE launch per batch.  ``source``: the ``preprocessing.source_data`` entry the items belong to (``label``,
+        ``sox_effects``, ...; preprocessor.py:591): its chain is applied and the lock records it under its label.  The chain is
+        parsed (and refused with a ValueError) before anything is read or written."""
+        effects = self.set_source(source)
         if self.config_lock_has_conflicts(save_dir) and not overwrite:
-            raise ConfigLockMismatch(f"{save_dir}/.config-lock records another audio configuration or an interrupted run; "
-                                     "preprocess into a new directory or pass overwrite=True")
-        self.save_config_lock(save_dir, in_progress=True)
+            raise ConfigLockMismatch(f"{save_dir}/.config-lock records another audio configuration, another configuration of the same "
+                                     "source_data label or an interrupted run; preprocess into a new directory or pass overwrite=True")
+        self.save_config_lock(save_dir, in_progress=True, merge=not overwrite)
         kept = []
         sr_tag, spec_fn = self.cfg.input_sampling_rate, f"spec-{self.cfg.input_sampling_rate}-{self.cfg.spec_type}.pt"
         hop = self.cfg.fft_hop_size
@@ -365,7 +424,7 @@ class GpuPreprocessor:
             group = pending.pop(sr, [])
             if not group:
                 return
-            x, lens, kept_idx, counters = process_audio_batch([a for _, a in group], sr, self.cfg, self.device, True, sr_tag)
+            x, lens, kept_idx, counters = process_audio_batch([a for _, a in group], sr, self.cfg, self.device, True, sr_tag, effects)
             for k, v in counters.items():
                 self.counters[k] = self.counters.get(k, 0) + v
             if not kept_idx:

@@ -668,6 +668,21 @@ int evmi_loudness_lkfs_f32(const float* x_dev, const int* lens_dev, float* y2_sc
 long long evmi_loudness_scratch_elems(int items, int channels, int t_max, int sample_rate);
 int evmi_peak_normalize_f32(const float* src_dev, float* dst_dev, const int* lens_dev, int items, int t_max, float target,
                             void* stream);
+/* A dataset's SoX effect chain (preprocessor.py:187-194; everyvoice_amd/sox.py parses it), run after the loudness gate and the
+ * mix-down, before resampling, on a zero-padded batch x [items][t_max] fp32 with lens [items] int32, all on the device.  `norm dB`
+ * is evmi_peak_normalize_f32 with target 10^(dB/20).  y must not alias x; y is zero past each new length.
+ * evmi_sox_reverse_f32: y[t] = x[lens - 1 - t] per utterance.
+ * evmi_sox_silence_f32: SoX 14.4's `silence` (DESIGN.md "SoX effect chains"; tests/sox_oracle.py restates it sample by sample):
+ * RMS over the last `window` (= rate / 50) samples on SoX's int32 scale, a sample is above a threshold when the truncated RMS is
+ * >= its *_rms_min (the host's translation of the % / dB test); above_periods 0|1 with start_duration samples, below_periods
+ * 0 (none) | 1 | -1 with stop_duration samples.  Rewrites lens with the kept lengths; reverse != 0 writes the kept samples in
+ * reverse order (a following `reverse` effect in the same pass).  ws: evmi_sox_silence_ws_bytes(items, t_max, window,
+ * stop_duration or 0) bytes, 8-byte aligned; window <= 4096, items <= 65535. */
+long long evmi_sox_silence_ws_bytes(int items, int t_max, int window, int stop_duration);
+int evmi_sox_silence_f32(const float* x_dev, float* y_dev, int* lens_dev, void* ws_dev, long long ws_bytes, int items, int t_max,
+                         int window, int above_periods, int start_duration, long long start_rms_min, int below_periods,
+                         int stop_duration, long long stop_rms_min, int reverse, void* stream);
+int evmi_sox_reverse_f32(const float* x_dev, float* y_dev, const int* lens_dev, int items, int t_max, void* stream);
 /* Frame-level F0 for FastSpeech2's pitch targets (call site everyvoice/preprocessor/preprocessor.py:244-285).
  * The reference's estimator is pyworld's dio + stonemask (third-party CPU code) and is NOT reproduced: this is a
  * normalised-autocorrelation tracker with the same interface -- f0 [items][t_max / hop + 1] in Hz at t = f * hop, 0 where
