@@ -108,6 +108,18 @@ __device__ __forceinline__ u32x4 swap_quads_bf16(u32x4 d) {
   o[3] = r1[1];
   return o;
 }
+// The same for two 16 x 16 chains (mfma16_layout.h): d = (two packed-bf16 dwords of this lane's quad of row tile 2p | two of tile
+// 2p + 1, same channel tile); one v_permlane16_swap per dword pair leaves the lane with 8 consecutive channels of one row.
+__device__ __forceinline__ u32x4 swap_quads16_bf16(u32x4 d) {
+  const auto r0 = __builtin_amdgcn_permlane16_swap(d[0], d[2], false, false);
+  const auto r1 = __builtin_amdgcn_permlane16_swap(d[1], d[3], false, false);
+  u32x4 o;
+  o[0] = r0[0];
+  o[2] = r0[1];
+  o[1] = r1[0];
+  o[3] = r1[1];
+  return o;
+}
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
   bf16x2_t pk;

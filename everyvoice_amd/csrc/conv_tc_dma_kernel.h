@@ -8,6 +8,8 @@
 //     ds_read_b128 read 16 consecutive rows (mod 16) at one channel vector: 16 distinct 16-byte slots of the 256-byte bank row.
 //     The permutation is applied on the SOURCE side (each lane picks the global vector that belongs in its slot; the weight
 //     images are stored pre-swizzled by the host) and again on the fragment read.
+//     (That is the 32 x 32 MFMA shape.  The 16 x 16 x 32 shape, the default, reads 16 rows x two channel vectors per group and
+//     needs the activation tile swizzled by r & 6 instead; the weight images keep the layout above: mfma16_layout.h.)
 //   * weights: one 16 KB image per (channel chunk, tap), double buffered; the image of step s + 1 is requested right after
 //     the barrier that opens step s and has a whole step of MFMAs to land: no staging registers, no ds_write pass.
 //   * activations: the (BN + (KS-1)*dil) x 64 tile of a channel chunk is requested in 8-row pieces; rows outside the
@@ -19,6 +21,7 @@
 #include <type_traits>
 
 #include "conv_tc_mfma.h"
+#include "mfma16_layout.h"
 
 namespace evmi {
 
@@ -42,9 +45,13 @@ __device__ __forceinline__ void lds_dma_b128(const void* g, void* l) {
 // WN_ = 8: sixteen waves on 512 rows, ONE workgroup per CU (every weight image feeds twice the MFMAs); A/B variant
 // WN_ = 2: four waves on 128 rows -- the NARROW tile for problems too small to fill the chip with 256-row tiles (one utterance; the GAN
 // step's generator at 16 x 256 .. 2048 rows: 32 .. 128 workgroups of 256 rows on 256 CUs); same K order per output: same bits
-template <int CIN_, int KS_, int MAXDIL_, int DBG_ = 0, int VAR_ = 0, int WN_ = 4>
+// MFMA_ = 16: v_mfma_f32_16x16x32_bf16, 4 x 4 tiles per wave (mfma16_layout.h); 32: v_mfma_f32_32x32x16_bf16, 2 x 2 tiles per wave.
+// Same 64 x 64 wave tile, same 64 accumulator registers, same weight images, same K order of (chunk, tap).  The chip holds a higher
+// clock on the 16 x 16 shape: 9-10 % less wall time at c128 / c256 k11; 32 stays for A/B runs (EVMI_CONV_MFMA).
+template <int CIN_, int KS_, int MAXDIL_, int DBG_ = 0, int VAR_ = 0, int WN_ = 4, int MFMA_ = 16>
 struct ConvDmaCfg {
-  static constexpr int CIN = CIN_, KS = KS_, MAXDIL = MAXDIL_, DBG = DBG_, VAR = VAR_;
+  static constexpr int CIN = CIN_, KS = KS_, MAXDIL = MAXDIL_, DBG = DBG_, VAR = VAR_, MFMA = MFMA_;
+  static_assert(MFMA == 32 || MFMA == 16, "MFMA shape: 32 (32x32x16) or 16 (16x16x32)");
   static constexpr int KC = 64, BM = 128, WM = 2, WN = WN_, MT = 2, NT = 2, BN = WN * NT * 32;
   static constexpr int NTHREADS = WM * WN * 64, NWAVES = WM * WN;
   static constexpr int NCHUNK = CIN / KC, NSTEP = NCHUNK * KS;
@@ -95,37 +102,48 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
   // v_permlane32_swap per dword between quads 2p and 2p + 1 leaves lane (n, 0) with channels 16p .. 16p + 7 and lane (n, 1) with
   // 16p + 8 .. 16p + 15 of its row: 16 bytes per lane, stored (and, for the residual / running sum, loaded) straight from / to
   // registers -- no LDS staging pass, no barrier, every wave retires its tile on its own while the others keep the MFMAs going.
+  //
+  // After a 16 x 16 chain (C::MFMA == 16) lane (n, g) holds channels 4g .. 4g + 3 of row n per tile; one v_permlane16_swap per dword
+  // between the tiles (mt, 2 np) and (mt, 2 np + 1) leaves the lane with channels 8 (g >> 1) .. + 7 of row n + 16 (g & 1) of the
+  // pair (mfma16_layout.h): with h = g >> 1 the SAME row (lane & 31 of a 32-row pair) and channel offset 8h as above, one vector
+  // per 16 channels instead of two per 32.
+  constexpr bool M16 = C::MFMA == 16;
+  constexpr int MTT = C::MT * 32 / C::MFMA, NTT = C::NT * 32 / C::MFMA;  // MFMA tiles per wave
   const int h = lane >> 5;
   const long long ob = (long long)b * a.out_batch_stride;
-  // flat index of (row of n-tile nt, channel m0 + wm*64 + 8h); which of the row's vectors are stored is decided per vector:
-  // in the polyphase (transposed convolution) placement the channels of one GEMM row are different output rows
-  long long flat_nt[C::NT];
-  bool row_ok[C::NT];
-#pragma unroll
-  for (int nt = 0; nt < C::NT; ++nt) {
-    const int r = r0 + wn * (C::NT * 32) + nt * 32 + (lane & 31);
-    flat_nt[nt] = (long long)r * a.out_row_stride + m0 + wm * (C::MT * 32) + 8 * h + a.out_shift;
-    row_ok[nt] = r < a.n_rows;
-  }
-  // vector (nt, channel offset co): its flat index, or -1 (offsets and limits are multiples of 8: a vector never straddles)
+  // vector (32-row pair nt, channel offset co): flat index of (row lane & 31 of the pair, channel m0 + wm*64 + 8h + co), or -1 (offsets
+  // and limits are multiples of 8: a vector never straddles).  Which of a row's vectors are stored is decided per vector: in the
+  // polyphase (transposed convolution) placement the channels of one GEMM row are different output rows.  Computed where it is
+  // used, after the k-loop: nothing of it stays live in registers across the MFMAs.
   auto vec_index = [&](int nt, int co) -> long long {
-    const long long f = flat_nt[nt] + co;
-    return (row_ok[nt] && f >= 0 && f + 8 <= a.out_limit) ? f : -1;
+    const int r = r0 + wn * (C::NT * 32) + nt * 32 + (lane & 31);
+    const long long f = (long long)r * a.out_row_stride + m0 + wm * (C::MT * 32) + 8 * h + a.out_shift + co;
+    return (r < a.n_rows && f >= 0 && f + 8 <= a.out_limit) ? f : -1;
   };
-  auto swap_quads = [](u32x4 d) -> u32x4 { return swap_quads_bf16(d); };
+  auto swap_quads = [](u32x4 d) -> u32x4 { return M16 ? swap_quads16_bf16(d) : swap_quads_bf16(d); };
 
   // accumulators start at the bias: the direct epilogue only scales, activates and stores
-  f32x16 acc[C::MT][C::NT];
+  using acc_t = std::conditional_t<M16, f32x4, f32x16>;
+  acc_t acc[MTT][NTT];
+  if constexpr (M16) {
 #pragma unroll
-  for (int mt = 0; mt < C::MT; ++mt)
+    for (int mt = 0; mt < MTT; ++mt) {
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + m0 + wm * (C::MT * 32) + mt * 16 + mfma16::acc_channel(lane, 0));
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + m0 + wm * (C::MT * 32) + mt * 32 + 8 * q + 4 * h);
-#pragma unroll
-      for (int nt = 0; nt < C::NT; ++nt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[mt][nt][4 * q + i] = bv[i];
+      for (int nt = 0; nt < NTT; ++nt) acc[mt][nt] = bv;
     }
+  } else {
+#pragma unroll
+    for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + m0 + wm * (C::MT * 32) + mt * 32 + 8 * q + 4 * h);
+#pragma unroll
+        for (int nt = 0; nt < C::NT; ++nt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[mt][nt][4 * q + i] = bv[i];
+      }
+  }
   const int rows_needed = C::BN + (C::KS - 1) * a.dil;
   const int x_pieces = (rows_needed + 7) >> 3;
   const float pre = a.pre_slope;
@@ -158,7 +176,7 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
     for (int p = wave; p < x_pieces; p += C::NWAVES) {
       const int row = p * 8 + (lane >> 3);
       const int rr = r0 - a.pad + row;
-      const int c8 = slot ^ ((row >> 1) & 7);
+      const int c8 = slot ^ (M16 ? mfma16::x_swizzle(row) : (row >> 1) & 7);  // the swizzle belongs to the shape that reads the tile
       const bf16_t* src = (row < rows_needed && rr >= 0 && rr < a.t_in) ? xb + (long long)rr * C::CIN + chunk * C::KC + c8 * 8
                                                                         : g_conv_dma_zero_row + slot * 8;
       lds_dma_b128(src, Xs + p * 1024);
@@ -166,40 +184,76 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
   };
 
   // ---- fragment addresses (bytes): row * 128 + ((channel vector ^ ((row >> 1) & 7)) << 4) --------------------------
-  const int row_a = wm * (C::MT * 32) + (lane & 31);
+  // 16 x 16 shape: row lane & 15, channel vectors g and g + 4 (mfma16_layout.h); the activation tile swizzled by row & 6
+  const int row_a = wm * (C::MT * 32) + (lane & (C::MFMA - 1));
   const int s_a = (row_a >> 1) & 7;
-  int off_a[4];
+  constexpr int NKS = M16 ? 2 : 4;  // k-steps per 64-channel image
+  int off_a[NKS];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) off_a[ks] = row_a * 128 + (((2 * ks + h) ^ s_a) << 4);
+  for (int ks = 0; ks < NKS; ++ks)
+    off_a[ks] = M16 ? mfma16::frag_offset(row_a, mfma16::frag_vec(lane, ks), mfma16::w_swizzle(row_a)) : row_a * 128 + (((2 * ks + h) ^ s_a) << 4);
 
+  // One image of the 16 x 16 shape: 2 k-steps x 4 channel tiles x 4 row tiles.  A 32-deep k-step needs 4 + 4 fragments (32
+  // registers), so nothing is double buffered whole.  The source states a staging that fits (the B fragments of k-step 1 read under
+  // the MFMAs of k-step 0, the A fragments rotating through three registers two groups ahead); the compiler's scheduler settles on
+  // 24 fragment registers and a read batch per 8 MFMAs, as it does for the 32 x 32 body, and the two workgroups of a CU cover each
+  // other's waits.  Pinning the stated order (VAR 2) costs registers the kernel does not have (scratch) and measured slower
+  // (DESIGN.md section 2.5).
   auto mma_step = [&](const char* Ab, int tap, int next_step) {
-    const int q = wn * (C::NT * 32) + (lane & 31) + tap * a.dil;  // this lane's activation row (n-tile 0)
-    const int s_b = (q >> 1) & 7;
-    int off_b[4];
+    if constexpr (M16) {
+      const int q = wn * (C::NT * 32) + (lane & 15) + tap * a.dil;  // this lane's activation row (row tile 0)
+      const int s_b = mfma16::x_swizzle(q);
+      int off_b[2];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) off_b[ks] = q * 128 + (((2 * ks + h) ^ s_b) << 4);
-    bf16x8 af[2][C::MT], bfr[2][C::NT];
-    auto load = [&](int ks, int buf) {
+      for (int s = 0; s < 2; ++s) off_b[s] = mfma16::frag_offset(q, mfma16::frag_vec(lane, s), s_b);
+      bf16x8 af[3], bfr[2][NTT];
+      auto load_a = [&](int grp) {  // group = k-step * 4 + channel tile
+        af[grp % 3] = *reinterpret_cast<const bf16x8*>(Ab + off_a[grp >> 2] + (grp & 3) * (16 * 128));
+      };
+      auto load_b = [&](int s, int nt) { bfr[s][nt] = *reinterpret_cast<const bf16x8*>(Xs + off_b[s] + nt * (16 * 128)); };
+      load_a(0);
 #pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt) af[buf][mt] = *reinterpret_cast<const bf16x8*>(Ab + off_a[ks] + mt * (32 * 128));
+      for (int nt = 0; nt < NTT; ++nt) load_b(0, nt);
+      load_a(1);
 #pragma unroll
-      for (int nt = 0; nt < C::NT; ++nt) bfr[buf][nt] = *reinterpret_cast<const bf16x8*>(Xs + off_b[ks] + nt * (32 * 128));
-    };
-    load(0, 0);
+      for (int grp = 0; grp < 8; ++grp) {
+        if (grp + 2 < 8) load_a(grp + 2);
+        if (grp < 4) load_b(1, grp);
+        if (C::VAR & 2) __builtin_amdgcn_sched_barrier(0);  // keep the reads in front of the MFMAs they run under
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int cur = (C::VAR & 32) ? 0 : (ks & 1);
-      if (ks + 1 < 4 && !(C::VAR & 32)) load(ks + 1, cur ^ 1);
-      if ((C::VAR & 2048) && ks == 0 && next_step >= 0) issue_a(next_step);  // requests among the MFMAs instead of behind the barrier
-      if (C::VAR & 2) __builtin_amdgcn_sched_barrier(0);
-      if (C::VAR & 4) __builtin_amdgcn_s_setprio(1);
+        for (int nt = 0; nt < NTT; ++nt)
+          acc[grp & 3][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[grp % 3], bfr[grp >> 2][nt], acc[grp & 3][nt], 0, 0, 0);
+        if (C::VAR & 2) __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      const int q = wn * (C::NT * 32) + (lane & 31) + tap * a.dil;  // this lane's activation row (n-tile 0)
+      const int s_b = (q >> 1) & 7;
+      int off_b[4];
 #pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt)
+      for (int ks = 0; ks < 4; ++ks) off_b[ks] = q * 128 + (((2 * ks + h) ^ s_b) << 4);
+      bf16x8 af[2][C::MT], bfr[2][C::NT];
+      auto load = [&](int ks, int buf) {
 #pragma unroll
-        for (int nt = 0; nt < C::NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mt], bfr[cur][nt], acc[mt][nt], 0, 0, 0);
-      if (C::VAR & 4) __builtin_amdgcn_s_setprio(0);
-      if (C::VAR & 2) __builtin_amdgcn_sched_barrier(0);
+        for (int mt = 0; mt < C::MT; ++mt) af[buf][mt] = *reinterpret_cast<const bf16x8*>(Ab + off_a[ks] + mt * (32 * 128));
+#pragma unroll
+        for (int nt = 0; nt < C::NT; ++nt) bfr[buf][nt] = *reinterpret_cast<const bf16x8*>(Xs + off_b[ks] + nt * (32 * 128));
+      };
+      load(0, 0);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int cur = (C::VAR & 32) ? 0 : (ks & 1);
+        if (ks + 1 < 4 && !(C::VAR & 32)) load(ks + 1, cur ^ 1);
+        if ((C::VAR & 2048) && ks == 0 && next_step >= 0) issue_a(next_step);  // requests among the MFMAs instead of behind the barrier
+        if (C::VAR & 2) __builtin_amdgcn_sched_barrier(0);
+        if (C::VAR & 4) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < C::NT; ++nt)
+            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mt], bfr[cur][nt], acc[mt][nt], 0, 0, 0);
+        if (C::VAR & 4) __builtin_amdgcn_s_setprio(0);
+        if (C::VAR & 2) __builtin_amdgcn_sched_barrier(0);
+      }
     }
   };
   if ((C::VAR & 1) && wave >= C::NWAVES / 2) __builtin_amdgcn_s_setprio(1);
@@ -245,11 +299,11 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
   if (C::VAR & 128) {
     float sacc = 0.f;
 #pragma unroll
-    for (int mt = 0; mt < C::MT; ++mt)
+    for (int mt = 0; mt < MTT; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < C::NT; ++nt)
+      for (int nt = 0; nt < NTT; ++nt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sacc += acc[mt][nt][r];
+        for (int r = 0; r < (M16 ? 4 : 16); ++r) sacc += acc[mt][nt][r];
     if (sacc == 12345.678f) a.out[0] = (bf16_t)sacc;  // keep the accumulators live
     return;
   }
@@ -260,20 +314,35 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
     // instruction) they cost 17-21k cycles per tile (measured), against 3-5k for the staged pass.
     __syncthreads();
     bf16_t* Os = reinterpret_cast<bf16_t*>(smem);
+    if constexpr (M16) {
 #pragma unroll
-    for (int mt = 0; mt < C::MT; ++mt)
+      for (int mt = 0; mt < MTT; ++mt) {
+        const int c = wm * C::MT * 32 + mt * 16 + mfma16::acc_channel(lane, 0);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = wm * C::MT * 32 + mt * 32 + 8 * q + 4 * h;
-#pragma unroll
-        for (int nt = 0; nt < C::NT; ++nt) {
-          const int n = wn * C::NT * 32 + nt * 32 + (lane & 31);
+        for (int nt = 0; nt < NTT; ++nt) {
+          const int n = wn * C::NT * 32 + nt * 16 + mfma16::acc_row(lane);
           bf16x4 pk;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)acc[mt][nt][4 * q + i];
+          for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)acc[mt][nt][i];
           *reinterpret_cast<bf16x4*>(Os + n * C::OS + c) = pk;
         }
       }
+    } else {
+#pragma unroll
+      for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int c = wm * C::MT * 32 + mt * 32 + 8 * q + 4 * h;
+#pragma unroll
+          for (int nt = 0; nt < C::NT; ++nt) {
+            const int n = wn * C::NT * 32 + nt * 32 + (lane & 31);
+            bf16x4 pk;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)acc[mt][nt][4 * q + i];
+            *reinterpret_cast<bf16x4*>(Os + n * C::OS + c) = pk;
+          }
+        }
+    }
     __syncthreads();
     const float scale = a.out_scale, post = a.post_slope;
     constexpr int VPR = C::BM / 8;
@@ -345,7 +414,7 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
     auto body = [&](auto has_acc) {
       constexpr bool ACC = decltype(has_acc)::value;
 #pragma unroll
-      for (int mt = 0; mt < C::MT; ++mt) {
+      for (int mt = 0; mt < C::MT; ++mt) {  // 32 channels at a time, either shape: four 16-byte vectors per lane
         u32x4 pv[C::NT][2];
         if (ACC) {
 #pragma unroll
@@ -360,9 +429,14 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
         for (int nt = 0; nt < C::NT; ++nt)
 #pragma unroll
           for (int p2 = 0; p2 < 2; ++p2) {
-            float f[8];  // quads 2p and 2p + 1 of this lane
+            // 32 x 32: quads 2p and 2p + 1 of this lane; 16 x 16: this lane's quads of channel tile 2 mt + p2 in the row tiles
+            // 2 nt and 2 nt + 1
+            float f[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = acc[mt][nt][8 * p2 + e] * scale;
+            for (int e = 0; e < 8; ++e) {
+              if constexpr (M16) f[e] = acc[2 * mt + p2][2 * nt + (e >> 2)][e & 3] * scale;
+              else f[e] = acc[mt][nt][8 * p2 + e] * scale;
+            }
             if (ACC) {
               const u32x4 d = swap_quads(pv[nt][p2]);
 #pragma unroll

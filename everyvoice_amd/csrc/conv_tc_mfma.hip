@@ -78,13 +78,16 @@ static const ConvTcEntry* conv_tc_table(int* n) {
 // workgroups give -- 1 x 400 frames 1.13 ms with 256-row tiles, 1.00 ms with 128-row tiles, 1.14-1.23 ms with 64-row tiles.)
 #define EVMI_CONV_DMA_NARROW_TABLE(X) X(256, 3, 5) X(256, 7, 5) X(256, 11, 5) X(128, 3, 5) X(128, 7, 5) X(128, 11, 5)
 
+// MFMA: the instruction shape of the whole table, 32 (v_mfma_f32_32x32x16_bf16) or 16 (v_mfma_f32_16x16x32_bf16): same tiles, same
+// launches, same weight images and kernel names (EVMI_CONV_MFMA, read once by find_conv_tc)
+template <int MFMA>
 static const ConvTcEntry* conv_dma_table(int* n) {
 #define X(cin, ks, md)                                                                          \
-  ConvTcEntry{cin, ks, md, 64, make_conv_dma_launch<ConvDmaCfg<cin, ks, md>>("conv_tc_dma<c" #cin ",k" #ks ",bm128,bn256,kc64>")},
+  ConvTcEntry{cin, ks, md, 64, make_conv_dma_launch<ConvDmaCfg<cin, ks, md, 0, 0, 4, MFMA>>("conv_tc_dma<c" #cin ",k" #ks ",bm128,bn256,kc64>")},
   static ConvTcEntry table[] = {EVMI_CONV_DMA_TABLE(X)};
 #undef X
 #define X(cin, ks, md)                                                                                                                   \
-  ConvTcEntry{cin, ks, md, 64, make_conv_dma_launch<ConvDmaCfg<cin, ks, md, 0, 0, 2>>("conv_tc_dma<c" #cin ",k" #ks ",bm128,bn128,kc64>")},
+  ConvTcEntry{cin, ks, md, 64, make_conv_dma_launch<ConvDmaCfg<cin, ks, md, 0, 0, 2, MFMA>>("conv_tc_dma<c" #cin ",k" #ks ",bm128,bn128,kc64>")},
   static const ConvTcEntry narrow[] = {EVMI_CONV_DMA_NARROW_TABLE(X)};
 #undef X
   static const bool linked = [] {
@@ -101,8 +104,10 @@ static const ConvTcEntry* conv_dma_table(int* n) {
 const ConvTcLaunch* find_conv_tc(int c_in, int c_out, int ks, int dil) {
   static const bool use_dma = env_int("EVMI_CONV_DMA", 1) != 0;
   if (use_dma) {
+    // EVMI_CONV_MFMA=32: the LDS-DMA kernels on the 32x32x16 instruction (A/B)
+    static const int mfma = env_int("EVMI_CONV_MFMA", 16);
     int nd = 0;
-    const ConvTcEntry* d = conv_dma_table(&nd);
+    const ConvTcEntry* d = mfma == 32 ? conv_dma_table<32>(&nd) : conv_dma_table<16>(&nd);
     for (int i = 0; i < nd; ++i)
       if (d[i].c_in == c_in && d[i].ks == ks && dil <= d[i].max_dil && c_out % d[i].launch.bm == 0) return &d[i].launch;
   }

@@ -117,10 +117,10 @@ static const std::vector<Variant>& variants() {
   Variant{name, cin, ks, md, make_conv_tc_launch<ConvTcCfg<cin, kc, bm, bn, wm, wn, ks, taps, md, abl>>(name)},
       EVMI_VARIANTS(X)
 #undef X
-#define X(name, cin, ks, md, dbg, var) Variant{name, cin, ks, md, make_conv_dma_launch<ConvDmaCfg<cin, ks, md, dbg, var>>(name)},
-      Variant{"c128k11_dma_w16", 128, 11, 5, make_conv_dma_launch<ConvDmaCfg<128, 11, 5, 0, 0, 8>>("c128k11_dma_w16")},
-      Variant{"c256k11_dma_w16", 256, 11, 5, make_conv_dma_launch<ConvDmaCfg<256, 11, 5, 0, 0, 8>>("c256k11_dma_w16")},
-      Variant{"c128k3_dma_w16", 128, 3, 5, make_conv_dma_launch<ConvDmaCfg<128, 3, 5, 0, 0, 8>>("c128k3_dma_w16")},
+#define X(name, cin, ks, md, dbg, var) Variant{name, cin, ks, md, make_conv_dma_launch<ConvDmaCfg<cin, ks, md, dbg, var, 4, 32>>(name)},
+      Variant{"c128k11_dma_w16", 128, 11, 5, make_conv_dma_launch<ConvDmaCfg<128, 11, 5, 0, 0, 8, 32>>("c128k11_dma_w16")},
+      Variant{"c256k11_dma_w16", 256, 11, 5, make_conv_dma_launch<ConvDmaCfg<256, 11, 5, 0, 0, 8, 32>>("c256k11_dma_w16")},
+      Variant{"c128k3_dma_w16", 128, 3, 5, make_conv_dma_launch<ConvDmaCfg<128, 3, 5, 0, 0, 8, 32>>("c128k3_dma_w16")},
       X("c128k11_dma", 128, 11, 5, 0, 0) X("c128k7_dma", 128, 7, 5, 0, 0) X("c128k3_dma", 128, 3, 5, 0, 0)
       X("c256k11_dma", 256, 11, 5, 0, 0) X("c256k7_dma", 256, 7, 5, 0, 0) X("c256k3_dma", 256, 3, 5, 0, 0)
       X("c128k11_dma_tl", 128, 11, 5, 1, 0)
@@ -133,6 +133,12 @@ static const std::vector<Variant>& variants() {
       X("c128k11_dma_v2048", 128, 11, 5, 0, 2048) X("c256k11_dma_v2048", 256, 11, 5, 0, 2048)
       X("c128k11_dma_a208", 128, 11, 5, 0, 208) X("c128k11_dma_a256", 128, 11, 5, 0, 256) X("c128k11_dma_a512", 128, 11, 5, 0, 512)
       X("c256k11_dma_v1", 256, 11, 5, 0, 1) X("c256k11_dma_v2", 256, 11, 5, 0, 2) X("c256k11_dma_v3", 256, 11, 5, 0, 3)
+#undef X
+      // the same kernels on v_mfma_f32_16x16x32_bf16 (4 x 4 tiles per wave, activation tile swizzled by row & 6): mfma16_layout.h
+#define X(name, cin, ks, md, var) Variant{name, cin, ks, md, make_conv_dma_launch<ConvDmaCfg<cin, ks, md, 0, var, 4, 16>>(name)},
+      X("c128k11_dma_m16", 128, 11, 5, 0) X("c128k7_dma_m16", 128, 7, 5, 0) X("c128k3_dma_m16", 128, 3, 5, 0)
+      X("c256k11_dma_m16", 256, 11, 5, 0) X("c256k7_dma_m16", 256, 7, 5, 0) X("c256k3_dma_m16", 256, 3, 5, 0)
+      X("c128k11_dma_m16_v2", 128, 11, 5, 2) X("c256k11_dma_m16_v2", 256, 11, 5, 2)
 #undef X
 #define X(name, cin, ks, md, dbg, var) Variant{name, cin, ks, md, make_conv_pp_launch<ConvPpCfg<cin, ks, md, dbg, var>>(name)},
       X("c128k11_pp", 128, 11, 5, 0, 0) X("c128k7_pp", 128, 7, 5, 0, 0) X("c256k11_pp", 256, 11, 5, 0, 0) X("c256k7_pp", 256, 7, 5, 0, 0)

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Sweep conv_tc tuning variants / ablations (bench_kernels.hip) at the bench shapes.
 Variants are interleaved over several rounds in ONE process and the median is reported (run-to-run and
-clock noise is several percent: single numbers from separate runs are not comparable)."""
+clock noise is several percent: single numbers from separate runs are not comparable).
+
+The MFMA-shape gate: <c>k<ks>_dma is the LDS-DMA kernel on 32x32x16, <c>k<ks>_dma_m16 the same on 16x16x32:
+  python tools/sweep_conv.py --exact --rounds=7 c128k11_dma c128k11_dma_m16 c256k11_dma c256k11_dma_m16"""
 import ctypes as C
 import statistics
 import sys
