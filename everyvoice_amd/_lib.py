@@ -270,6 +270,14 @@ SYMBOLS = {
     "evmi_spectral_norm_grad_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
     "evmi_ratio_accumulate_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "evmi_adamw_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
+    "evmi_gst_conv2d_fwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
+    "evmi_gst_conv2d_dgrad_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "evmi_gst_conv2d_wgrad_ws_elems": (C.c_longlong, [C.c_int] * 5),
+    "evmi_gst_conv2d_wgrad_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong] + [C.c_int] * 6 + [C.c_void_p]),
+    "evmi_gst_gru_fwd_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
+    "evmi_gst_gru_bwd_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
+    "evmi_gst_attention_fwd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "evmi_gst_attention_bwd_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p]),
     "evmi_generator_create": (C.c_int, [C.POINTER(GeneratorConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "evmi_generator_destroy": (None, [C.c_void_p]),
     "evmi_generator_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),

@@ -201,11 +201,13 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
 __device__ __forceinline__ float bn_act(float z, int act) {
   if (act == 2) return z * sigmoidf_(z);
   if (act == 4) return tanhf(z);
+  if (act == 3) return fmaxf(z, 0.f);
   return z;
 }
 __device__ __forceinline__ float bn_act_grad(float z, int act) {
   if (act == 2) { const float s = sigmoidf_(z); return s * (1.f + z * (1.f - s)); }
   if (act == 4) { const float t = tanhf(z); return 1.f - t * t; }
+  if (act == 3) return z > 0.f ? 1.f : 0.f;
   return 1.f;
 }
 
@@ -647,7 +649,7 @@ int evmi_batchnorm_fwd_cbt_f32(const float* x, const float* gamma, const float* 
   if (!x || !gamma || !beta || !y || !mean_out || !rstd_out) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd: null pointer");
   if ((running_mean == nullptr) != (running_var == nullptr)) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd: running_mean and running_var go together");
   if (C < 1 || n_cols < 1) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd: empty input");
-  if (act != 0 && act != 2 && act != 4) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd: act must be 0 (none), 2 (SiLU) or 4 (tanh)");
+  if (act != 0 && act != 2 && act != 3 && act != 4) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd: act must be 0 (none), 2 (SiLU), 3 (ReLU) or 4 (tanh)");
   if (momentum < 0.f && (!running_mean || !running_var)) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd: evaluation mode (momentum < 0) needs the running statistics");
   if (n_cols >= BN_LONG_ROW)
     hipLaunchKernelGGL(batchnorm_fwd_cbt_kernel<1024>, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, gamma, beta, y, mean_out, rstd_out,
@@ -663,7 +665,7 @@ int evmi_batchnorm_bwd_cbt_f32(const float* x, const float* gamma, const float* 
                                const float* dy, float* dx, float* dgamma, float* dbeta, int C, long long n_cols, int act, void* stream) {
   if (!x || !gamma || !beta || !mean || !rstd || !dy || !dx || !dgamma || !dbeta) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd: null pointer");
   if (C < 1 || n_cols < 1) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd: empty input");
-  if (act != 0 && act != 2 && act != 4) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd: act must be 0 (none), 2 (SiLU) or 4 (tanh)");
+  if (act != 0 && act != 2 && act != 3 && act != 4) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd: act must be 0 (none), 2 (SiLU), 3 (ReLU) or 4 (tanh)");
   if (n_cols >= BN_LONG_ROW)
     hipLaunchKernelGGL(batchnorm_bwd_cbt_kernel<1024>, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, gamma, beta, mean, rstd, dy, dx, dgamma,
                        dbeta, n_cols, act);

@@ -93,6 +93,15 @@ class FastSpeech2ModelConfig:
     postnet_layers: int = 5
     n_speakers: int = 0   # table sizes when multispeaker / multilingual (len(speaker2id) / len(lang2id) in the reference)
     n_languages: int = 0
+    # everyvoice-text-to-spec-0.5.json:279-284: the Global Style Token module (arXiv 1803.09017) -- see StyleTokens below
+    use_global_style_token_module: bool = False
+    # not in the reference's schema (fixed inside the absent module; the GST paper's / GST-Tacotron's values)
+    gst_num_heads: int = 8
+    gst_num_tokens: int = 10
+    gst_ref_enc_filters: tuple = (32, 32, 64, 64, 128, 128)
+
+    def __post_init__(self):
+        self.gst_ref_enc_filters = tuple(int(v) for v in self.gst_ref_enc_filters)  # (a list after a JSON round trip)
 
 
 N_PHONOLOGICAL_FEATURES = 43  # everyvoice/text/features.py:7
@@ -155,6 +164,75 @@ def _fold_bn(w, b, sd, prefix):
     """Eval-mode BatchNorm1d after a convolution: y = (conv - mean) / sqrt(var + eps) * gamma + beta."""
     s = sd[prefix + ".weight"].float() / torch.sqrt(sd[prefix + ".running_var"].float() + _BN_EPS)
     return w * s.view(-1, *([1] * (w.dim() - 1))), (b - sd[prefix + ".running_mean"].float()) * s + sd[prefix + ".bias"].float()
+
+
+def gst_state_dict_shapes(c: "FastSpeech2ModelConfig") -> dict:
+    """THE key-name table of the Global Style Token module: every tensor of its state dict except ``num_batches_tracked`` (which the
+    trainer adds for each ``bns.{i}``), in declaration order.  The module lives in the absent FastSpeech2_lightning submodule, so the
+    names and the layout follow the public lineage (KinglittleQ/GST-Tacotron, mozilla/TTS); to load a real checkpoint, map its keys
+    HERE -- the inference model and the trainer both take their names from this function.
+    With E = encoder.input_dim: reference encoder = len(filters) x [Conv2d(k 3, stride 2, padding 1) -> BatchNorm2d -> ReLU] over the mel
+    as a one-channel image [B, 1, T, n_mels], then GRU(filters[-1] * n_mels' -> E / 2), last hidden state; style token layer = `tokens`
+    embeddings of E / heads, keys and values from tanh(embed), bias-free W_query (E / 2 -> E), W_key, W_value (E / heads -> E)."""
+    E, heads = c.encoder.input_dim, c.gst_num_heads
+    if E % 2 or E % heads:
+        raise ValueError(f"Global Style Token module: encoder.input_dim {E} must be even and a multiple of gst_num_heads {heads}")
+    # what csrc/gst.hip is built for: the GRU keeps W_hh in registers at a hidden size of 32, 64 or 128; at most 16 tokens
+    if E not in (64, 128, 256):
+        raise ValueError(f"Global Style Token module: encoder.input_dim {E} is not supported (the GRU kernels exist for a hidden size "
+                         "E / 2 of 32, 64 or 128, i.e. encoder.input_dim 64, 128 or 256)")
+    if not 1 <= c.gst_num_tokens <= 16:
+        raise ValueError(f"Global Style Token module: gst_num_tokens {c.gst_num_tokens} is not supported (1 to 16 tokens)")
+    if not c.gst_ref_enc_filters:
+        raise ValueError("Global Style Token module: gst_ref_enc_filters is empty")
+    shapes, cin, bins = {}, 1, c.n_mels
+    for i, cout in enumerate(c.gst_ref_enc_filters):
+        shapes[f"gst.encoder.convs.{i}.weight"], shapes[f"gst.encoder.convs.{i}.bias"] = (cout, cin, 3, 3), (cout,)
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            shapes[f"gst.encoder.bns.{i}.{leaf}"] = (cout,)
+        cin, bins = cout, (bins - 1) // 2 + 1
+    H = E // 2
+    shapes.update({"gst.encoder.gru.weight_ih_l0": (3 * H, cin * bins), "gst.encoder.gru.weight_hh_l0": (3 * H, H),
+                   "gst.encoder.gru.bias_ih_l0": (3 * H,), "gst.encoder.gru.bias_hh_l0": (3 * H,),
+                   "gst.stl.embed": (c.gst_num_tokens, E // heads), "gst.stl.attention.W_query.weight": (E, H),
+                   "gst.stl.attention.W_key.weight": (E, E // heads), "gst.stl.attention.W_value.weight": (E, E // heads)})
+    return shapes
+
+
+class StyleTokens:
+    """Global Style Token module, inference: a reference mel [B, T, n_mels] -> a style embedding [B, E] that is added to the encoder
+    output at every non-padded text position (where the speaker / language embeddings go).  Eval-mode BatchNorm is folded into the
+    convolutions at load time and the keys / values of the (constant) tokens are computed once; everything runs in fp32 in both
+    precision modes.  The mel is consumed as given, zero padding included (no length masking: ``torch.nn`` semantics)."""
+
+    def __init__(self, c: "FastSpeech2ModelConfig", sd: dict, dev):
+        put = lambda t: t.to(dev, torch.float32).contiguous()
+        self.heads, self.n_mels = c.gst_num_heads, c.n_mels
+        self.convs = []
+        for i in range(len(c.gst_ref_enc_filters)):
+            w, b = _fold_bn(sd[f"gst.encoder.convs.{i}.weight"].float(), sd[f"gst.encoder.convs.{i}.bias"].float(), sd, f"gst.encoder.bns.{i}")
+            self.convs.append((put(w), put(b)))
+        g = "gst.encoder.gru."
+        self.w_ih, self.b_ih = put(sd[g + "weight_ih_l0"].unsqueeze(-1)), put(sd[g + "bias_ih_l0"])
+        self.w_hh, self.b_hh = put(sd[g + "weight_hh_l0"]), put(sd[g + "bias_hh_l0"])
+        a = "gst.stl.attention."
+        tokens = torch.tanh(sd["gst.stl.embed"].float().cpu())
+        self.keys = put(sd[a + "W_key.weight"].float().cpu() @ tokens.t())      # [E, tokens]
+        self.values = put(sd[a + "W_value.weight"].float().cpu() @ tokens.t())
+        self.w_q = put(sd[a + "W_query.weight"].unsqueeze(-1))
+
+    def forward(self, mel: torch.Tensor) -> torch.Tensor:
+        B, T, F = mel.shape
+        x = mel.view(1, B, T, F)
+        for w, b in self.convs:
+            x = ops.gst_conv2d_fwd(x, w, b, ops.ACT_RELU)
+        C, _, T2, F2 = x.shape
+        seq = x.permute(0, 3, 1, 2).reshape(C * F2, 1, B * T2)  # the GRU's input features: channel-major (c, bin), one column per (item, step)
+        with ops.exact_f32():
+            gi = ops.conv1d_fwd(seq, self.w_ih, self.b_ih).view(-1, B, T2)
+            h, _ = ops.gst_gru_fwd(gi, self.w_hh, self.b_hh, save=False)
+            q = ops.conv1d_fwd(h.view(-1, 1, B), self.w_q, None).view(-1, B)
+        return ops.gst_attention_fwd(q, self.keys, self.values, self.heads, save=False)[0]
 
 
 class _Conformer:
@@ -257,6 +335,9 @@ class FastSpeech2:
         self.stats = stats or Stats()
         self.device = torch.device(device)
         self.lang2id, self.speaker2id = lang2id or {}, speaker2id or {}
+        self.audio_config = None  # the model's preprocessing.audio, where the caller knows it: the synthesis helpers make a style reference's mel with it
+        if self.config.use_global_style_token_module:
+            gst_state_dict_shapes(self.config)  # (refuses a size the kernels are not built for here, not inside the first forward)
         if self.device.type != "cuda":
             raise RuntimeError("FastSpeech2 runs on libevmi_hip (MI355X) only; there is no CPU path")
         _lib.load()
@@ -272,6 +353,7 @@ class FastSpeech2:
         self.decoder = _Conformer(c.decoder, sd, "decoder", dev)
         self.speaker_table = put(sd["speaker_embedding.weight"]) if c.multispeaker else None
         self.language_table = put(sd["language_embedding.weight"]) if c.multilingual else None
+        self.gst = StyleTokens(c, sd, dev) if c.use_global_style_token_module else None
         vp = c.variance_predictors
         self.duration_predictor = _VariancePredictor(vp.duration, sd, "duration_predictor", dev)
         self.pitch_predictor = _VariancePredictor(vp.pitch, sd, "pitch_predictor", dev)
@@ -328,6 +410,8 @@ class FastSpeech2:
             shapes["speaker_embedding.weight"] = (max(1, c.n_speakers), d)
         if c.multilingual:
             shapes["language_embedding.weight"] = (max(1, c.n_languages), d)
+        if c.use_global_style_token_module:
+            shapes.update(gst_state_dict_shapes(c))
         shapes.update({"pitch_embedding.weight": (vp.pitch.n_bins, d), "energy_embedding.weight": (vp.energy.n_bins, d),
                        "mel_linear.weight": (c.n_mels, c.decoder.input_dim), "mel_linear.bias": (c.n_mels,)})
         if c.use_postnet:
@@ -391,23 +475,32 @@ class FastSpeech2:
     # -- forward --------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, ids: torch.Tensor, lens: torch.Tensor, duration_control=1.0, pitch_control=1.0, energy_control=1.0,
-                 durations: torch.Tensor | None = None, speakers: torch.Tensor | None = None, languages: torch.Tensor | None = None):
+                 durations: torch.Tensor | None = None, speakers: torch.Tensor | None = None, languages: torch.Tensor | None = None,
+                 style_mel: torch.Tensor | None = None):
         """ids [B, L] (0 = padding), lens [B] -> (mel [B, T, n_mels], postnet mel, durations [B, L], pitch [B, L],
-        energy [B, L], mel_lens [B]) on the device."""
+        energy [B, L], mel_lens [B]) on the device.  ``style_mel`` (a model with the Global Style Token module needs it, any other
+        refuses it): the style reference's mel [B, Ts, n_mels], or [1, Ts, n_mels] for one reference serving the whole batch."""
         if not self._ready:
             raise RuntimeError("load_state_dict() or init_random() first")
         prev = ops.CONV_BACKEND["operands"]
         ops.CONV_BACKEND["operands"] = self.precision
         try:
-            return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages)
+            return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel)
         finally:
             ops.CONV_BACKEND["operands"] = prev
 
-    def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages):
+    def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None):
         lib, dev, c = _lib.load(), self.device, self.config
         B, L = ids.shape[:2]
         if L > c.max_length:
             raise ValueError(f"text of {L} symbols exceeds max_length {c.max_length}")
+        if self.gst is None and style_mel is not None:
+            raise ValueError("`style_mel` given to a model without the Global Style Token module (model.use_global_style_token_module)")
+        if self.gst is not None:
+            if style_mel is None:
+                raise ValueError("this model needs `style_mel` [B, Ts, n_mels]: it was trained with the Global Style Token module")
+            if style_mel.dim() != 3 or style_mel.shape[0] not in (1, B) or style_mel.shape[1] < 1 or style_mel.shape[2] != c.n_mels:
+                raise ValueError(f"style_mel: expected [{B} or 1, Ts, {c.n_mels}], got {tuple(style_mel.shape)}")
         D = c.encoder.input_dim
         lens32 = lens.to(dev, torch.int32).contiguous()
         if c.target_text_representation_level == "phonological_features":
@@ -431,6 +524,12 @@ class FastSpeech2:
                 item32 = item_ids.to(dev, torch.int32).contiguous()
                 _chk(lib.evmi_fs2_add_item_embedding_f32(x.data_ptr(), item32.data_ptr(), lens32.data_ptr(), table.data_ptr(), B, L, D, _s(x)),
                      "evmi_fs2_add_item_embedding_f32")
+        if self.gst is not None:
+            # the style matrix [B or 1, E] is the "table" of the same masked add; one reference: every item takes row 0 (computed once)
+            style = self.gst.forward(style_mel.to(dev, torch.float32).contiguous())
+            rows = torch.arange(B, device=dev, dtype=torch.int32) if style.shape[0] == B else torch.zeros(B, device=dev, dtype=torch.int32)
+            _chk(lib.evmi_fs2_add_item_embedding_f32(x.data_ptr(), rows.data_ptr(), lens32.data_ptr(), style.data_ptr(), B, L, D, _s(x)),
+                 "evmi_fs2_add_item_embedding_f32")
         log_d = self.duration_predictor.forward(x, lens32)
         pitch = self.pitch_predictor.forward(x, lens32)
         vp = c.variance_predictors

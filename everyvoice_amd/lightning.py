@@ -303,7 +303,9 @@ class FastSpeech2(_Module):
         unseen shapes run eagerly twice first.  ``graph_buckets=(symbols, frames)`` (e.g. (16, 64)) pads batches up to multiples so that
         the variable-length batches of a real loader fall on a small set of shapes -- OFF by default since round 5: the
         Conformer's BatchNorm takes its batch statistics over every column, padded ones included (as torchaudio's does), so extra
-        padding shifts mean / variance and the running statistics away from a run padded to the batch maximum only; opt in where
+        padding shifts mean / variance and the running statistics away from a run padded to the batch maximum only -- and with the Global
+        Style Token module the effect is much stronger: the reference encoder sees the extra zero frames and the GRU runs extra steps over
+        them, so the style embedding itself depends on the bucket size; opt in where
         replay rate matters more than that drift.  ``model_kwargs`` of ``train_base_command`` reach here."""
         super().__init__()
         from .fs2 import Stats

@@ -598,15 +598,64 @@ class Scaler:
         return {"sample_size": len(self), **{f: float(getattr(self, f)) for f in self._FIELDS}}
 
 
+def _has_style_tokens(model) -> bool:
+    cfg = getattr(model, "config", None)
+    cfg = getattr(cfg, "model", cfg)  # (a FastSpeech2Config holds the model's configuration under .model)
+    return bool(getattr(cfg, "use_global_style_token_module", False))
+
+
+def _style_audio_config(model, audio_config=None, vocoder_config=None) -> AudioConfig:
+    """The front end the model's training mels were made with: the caller's ``audio_config``, else the model's own (``model.audio_config``,
+    or ``model.config.preprocessing.audio`` of a module that carries its whole FastSpeech2Config), else the vocoder configuration's -- the
+    two are trained on the same features -- else the defaults."""
+    if audio_config is not None:
+        return audio_config
+    own = getattr(model, "audio_config", None) or getattr(getattr(getattr(model, "config", None), "preprocessing", None), "audio", None)
+    if own is not None:
+        return own
+    return vocoder_config.preprocessing.audio if vocoder_config is not None else AudioConfig()
+
+
+def style_reference_mel(style_reference, cfg: AudioConfig | None = None, device="cuda:0", sampling_rate: int | None = None) -> torch.Tensor:
+    """The style reference of a Global Style Token model -> its mel [1, T, n_mels] on the device, through the front end the training mels
+    were made with (``cfg``: the model's ``preprocessing.audio``): load -> mono -> resample to ``input_sampling_rate`` -> log-mel.
+    ``style_reference``: the path of a wav file (what the reference's demo passes, ``demo/app.py:410-431``) or a 1-D float waveform at
+    ``sampling_rate`` (default: ``cfg.input_sampling_rate``)."""
+    cfg = cfg or AudioConfig()
+    if torch.is_tensor(style_reference) or isinstance(style_reference, np.ndarray):
+        audio = torch.as_tensor(style_reference, dtype=torch.float32)
+        if audio.dim() != 1:
+            raise ValueError(f"style_reference: a 1-D waveform or the path of a wav file, got a tensor of shape {tuple(audio.shape)}")
+        sr = int(sampling_rate or cfg.input_sampling_rate)
+    else:
+        audio, sr, _ = load_wav(style_reference)
+        audio = audio.mean(0)  # mono, as the default `channels 1` of preprocessing mixes down
+    x = audio.to(device)[None]
+    if sr != cfg.input_sampling_rate:
+        x = resample(x, sr, cfg.input_sampling_rate)
+    mel, _ = GpuPreprocessor(cfg, device=device, pitch=False).features(x[0])
+    if mel.shape[-1] < 1:
+        raise ValueError(f"style_reference: {audio.numel()} samples at {sr} Hz give no mel frame (hop {cfg.fft_hop_size})")
+    return mel.transpose(0, 1)[None].contiguous()
+
+
 def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, out_dir, basenames: list[str], speaker: str = "default",
                          language: str = "default", output_types=("wav", "spec"), sr: int = 22050, hop: int = 256,
-                         duration_control: float = 1.0, global_step: int | None = None) -> list[dict]:
+                         duration_control: float = 1.0, global_step: int | None = None, style_reference=None,
+                         audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None) -> list[dict]:
     """The device part of ``everyvoice synthesize from-text`` (``fs2.cli.synthesize.synthesize_helper``,
     ``everyvoice/demo/app.py:84-106``): token ids -> FastSpeech2 (postnet mel) -> HiFiGAN -> files named as the reference's
     prediction writers name them (``everyvoice/base_cli/prediction_writing_callback.py:35-41``):
     ``<out_dir>/wav/<basename>--<speaker>--<language>--pred.wav`` and ``<out_dir>/synthesized_spec/...--spec-pred....pt``
-    holding ``[n_mels, T]``.  Text normalisation / g2p (CPU string work) stays with the caller: ``ids`` are symbol ids, 0 pads."""
-    mel, post, durations, _, _, mel_lens = fs2(ids, lens, duration_control=duration_control)
+    holding ``[n_mels, T]``.  Text normalisation / g2p (CPU string work) stays with the caller: ``ids`` are symbol ids, 0 pads.
+    ``style_reference`` (a wav path, or a 1-D waveform at ``style_reference_sampling_rate``; ``audio_config``: the model's
+    ``preprocessing.audio``, default as in ``synthesize_helper``): a model with the Global Style Token module needs it, any other refuses it."""
+    kw = {}
+    if style_reference is not None:
+        if not _has_style_tokens(fs2):
+            raise ValueError("style_reference given, but this model has no Global Style Token module (model.use_global_style_token_module)")
+        kw["style_mel"] = style_reference_mel(style_reference, _style_audio_config(fs2, audio_config), fs2.device, style_reference_sampling_rate)
+    mel, post, durations, _, _, mel_lens = fs2(ids, lens, duration_control=duration_control, **kw)
     wav = vocoder(post.transpose(1, 2).contiguous()) if "wav" in output_types else None
     results = []
     for i, base in enumerate(basenames):
@@ -651,7 +700,7 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                       text_representation=None, accelerator: str = "auto", devices: str = "1", device=None, batch_size: int = 16, num_workers: int = 0,
                       filelist=None, filelist_data=None, output_dir: Path = Path("synthesis_output"), teacher_forcing_directory: Path | None = None,
                       vocoder_model=None, vocoder_config=None, vocoder_global_step: int | None = None, style_reference=None, return_scores: bool = False,
-                      text_to_ids=None):
+                      text_to_ids=None, audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None):
     """``fs2.cli.synthesize.synthesize_helper`` (call site ``everyvoice/demo/app.py:84-106``, same keyword names) for the path this
     library accelerates: texts -> symbol ids -> FastSpeech2 -> (vocoder) -> files through per-format writers.
     Returns ``(config, device, predictions, callbacks)`` with ``callbacks`` keyed by output format ("wav", "spec").
@@ -659,7 +708,13 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
     ``texts`` are strings mapped to ids by ``text_to_ids`` (the reference's TextProcessor: CPU string work, out of scope) or already
     lists / tensors of symbol ids; ``filelist_data`` rows (dicts with basename / ids / speaker / language) replace ``texts``.
     ``teacher_forcing_directory``: read ``duration/<basename>--<speaker>--<language>--duration.pt`` from there and synthesise with
-    those durations -- how the spectrograms for vocoder matching are produced (docs/guides/finetune.md:18-43)."""
+    those durations -- how the spectrograms for vocoder matching are produced (docs/guides/finetune.md:18-43).
+    ``style_reference``: the path of a wav file (the demo's ``gr.Audio(type="filepath")``) or a 1-D float waveform (at
+    ``style_reference_sampling_rate``, default the front end's input rate), for a model with the Global Style Token module: it goes through
+    the front end the training mels were made with (``audio_config``; default: the model's own ``audio_config`` /
+    ``config.preprocessing.audio``, else the vocoder configuration's, else the defaults) and ONE style embedding serves every text of the call.  A model without the module refuses it; a model with the module refuses a call without it."""
+    if style_reference is not None and not _has_style_tokens(model):
+        raise ValueError("style_reference given, but this model has no Global Style Token module (model.use_global_style_token_module)")
     formats = [getattr(f, "value", f) for f in (output_type if isinstance(output_type, (list, tuple)) else [output_type])]
     unsupported = [f for f in formats if f not in ("wav", "spec")]
     if unsupported:
@@ -687,6 +742,9 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
             rows.append({"basename": f"utt-{i:04d}" if not isinstance(t, str) else "".join(c if c.isalnum() else "-" for c in t)[:20] or f"utt-{i:04d}",
                          "ids": ids, "speaker": speaker, "language": language})
     predictions = []
+    style_mel = None
+    if style_reference is not None:
+        style_mel = style_reference_mel(style_reference, _style_audio_config(model, audio_config, vocoder_config), dev, style_reference_sampling_rate)
     for lo in range(0, len(rows), batch_size):
         chunk = rows[lo : lo + batch_size]
         lens = torch.tensor([len(r["ids"]) for r in chunk])
@@ -706,6 +764,8 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                 d = torch.load(Path(teacher_forcing_directory) / "duration" / SEP.join([r["basename"], spk[j], lang[j], "duration.pt"]), weights_only=True)
                 durs[j, : lens[j]] = d[: lens[j]].long()
             kw["durations"] = durs
+        if style_mel is not None:
+            kw["style_mel"] = style_mel
         _, post, durations, _, _, mel_lens = model(ids, lens, duration_control=1.0 if duration_control is None else duration_control, **kw)
         wav = vocoder_model(post.transpose(1, 2).contiguous()) if "wav" in formats else None
         for j, r in enumerate(chunk):

@@ -668,6 +668,123 @@ class _AlignerT:
         return join
 
 
+class _StyleTokensT:
+    """The Global Style Token module in training (architecture and key names: ``everyvoice_amd.fs2.gst_state_dict_shapes``): the
+    utterance's own target mel is the style reference.  The module consumes the zero-padded batch tensor exactly as ``torch.nn`` would
+    (an unpinned choice, like the Conformer's BatchNorm): no length masking, BatchNorm statistics over every position.  fp32 in both
+    precision modes; its weight gradients are issued in place (``ops.exact_f32``), every sum in a fixed order."""
+
+    def __init__(self, g: ParamGroup, c):
+        from ..fs2 import gst_state_dict_shapes
+
+        shapes = gst_state_dict_shapes(c)
+        self.group, self.heads = g, c.gst_num_heads
+        self.convs = []
+        for i in range(len(c.gst_ref_enc_filters)):
+            p = f"gst.encoder.convs.{i}"
+            shape = shapes[p + ".weight"]
+            self.convs.append((g.declare(p + ".weight", shape), g.declare(p + ".bias", shape[:1]), shape,
+                               Affine(g, f"gst.encoder.bns.{i}", shape[0], batchnorm=True)))
+        r = "gst.encoder.gru."
+        h3, cin = shapes[r + "weight_ih_l0"]
+        self.H = h3 // 3
+        self.ih = Dense(g, r + "weight_ih_l0", r + "bias_ih_l0", cin, h3, linear=True)
+        self.hh = Dense(g, r + "weight_hh_l0", r + "bias_hh_l0", self.H, h3, linear=True)
+        self.embed_shape = shapes["gst.stl.embed"]
+        self.i_embed = g.declare("gst.stl.embed", self.embed_shape)
+        a = "gst.stl.attention."
+        E, dk = shapes[a + "W_key.weight"]
+        self.wq = Dense(g, a + "W_query.weight", None, self.H, E, linear=True)
+        self.wk = Dense(g, a + "W_key.weight", None, dk, E, linear=True)
+        self.wv = Dense(g, a + "W_value.weight", None, dk, E, linear=True)
+
+    def batchnorms(self):
+        return [bn for _, _, _, bn in self.convs]
+
+    @staticmethod
+    def _dense(tape: Tape, x: Var, layer: Dense) -> Var:
+        w, dw_sink = layer.effective(True)
+        with ops.exact_f32():
+            y = Var(ops.conv1d_fwd(x.data, w, layer.bias_data(), 1, 0, 1, 1))
+
+        def bwd():
+            if y.grad is None:
+                return
+            with ops.exact_f32():
+                dx, _, _ = ops.conv1d_bwd(x.data, w, y.grad, 1, 0, 1, 1, need_dx=x.needs_grad, dw_out=dw_sink, db_out=layer.db_sink(), accumulate=True)
+            if dx is not None:
+                x.accumulate(dx)
+
+        tape.record(bwd)
+        return y
+
+    def _conv(self, tape: Tape, x: Var, H: int, W: int, i_w: int, i_b: int, shape) -> Var:
+        """x [Cin, B, H * W] -> [Cout, B, OH * OW] (the BatchNorm's [C, B, columns] view of the channel-major tensor)."""
+        g = self.group
+        cin, B = x.data.shape[:2]
+        w, dw, b, db = g.data(i_w).view(shape), g.gradient(i_w).view(shape), g.data(i_b), g.gradient(i_b)
+        y = Var(ops.gst_conv2d_fwd(x.data.view(cin, B, H, W), w, b).view(shape[0], B, -1))
+
+        def bwd():
+            if y.grad is None:
+                return
+            dy = y.grad.view(shape[0], B, ops.gst_conv_out(H), ops.gst_conv_out(W))
+            ops.gst_conv2d_wgrad(x.data.view(cin, B, H, W), dy, dw, db, accumulate=True)
+            if x.needs_grad:
+                x.accumulate(ops.gst_conv2d_dgrad(dy, w, H, W).view(cin, B, -1))
+
+        tape.record(bwd)
+        return y
+
+    def forward(self, tape: Tape, mel: torch.Tensor) -> Var:
+        """mel [B, T, n_mels] (zero padded) -> style embeddings [B, E]."""
+        g = self.group
+        B, H, W = mel.shape
+        x = Var(mel.reshape(1, B, H * W), needs_grad=False)
+        for i_w, i_b, shape, bn in self.convs:
+            x = batchnorm(tape, self._conv(tape, x, H, W, i_w, i_b, shape), bn, ops.ACT_RELU)
+            H, W = ops.gst_conv_out(H), ops.gst_conv_out(W)
+        C, T2 = x.data.shape[0], H
+        # the GRU's input features, channel-major: row c * W + bin, one column per (item, step)
+        seq = Var(x.data.view(C, B, T2, W).permute(0, 3, 1, 2).reshape(C * W, 1, B * T2))
+        tape.record(lambda: seq.grad is not None and x.accumulate(seq.grad.view(C, W, B, T2).permute(0, 2, 3, 1).reshape(C, B, T2 * W)))
+        gi = self._dense(tape, seq, self.ih)
+        whh = self.hh.effective(True)[0].view(3 * self.H, self.H)
+        hlast, saved = ops.gst_gru_fwd(gi.data.view(-1, B, T2), whh, self.hh.bias_data(), save=not _EVAL[0])
+        h = Var(hlast.view(self.H, 1, B))
+
+        def gru_bwd():
+            if h.grad is None:
+                return
+            dgi, dgh = ops.gst_gru_bwd(saved, whh, h.grad.reshape(self.H, B))
+            with ops.exact_f32():  # dW_hh = dgh . hprev^T, db_hh = row sums of dgh: a dense layer's weight gradient
+                ops.conv1d_bwd(saved[2].view(self.H, 1, B * T2), whh.view(3 * self.H, self.H, 1), dgh.view(3 * self.H, 1, B * T2), 1, 0, 1, 1,
+                               need_dx=False, dw_out=self.hh.effective(True)[1], db_out=self.hh.db_sink(), accumulate=True)
+            gi.accumulate(dgi.view(3 * self.H, 1, B * T2))
+
+        tape.record(gru_bwd)
+        q = self._dense(tape, h, self.wq)
+        N, dk = self.embed_shape
+        emb, demb = g.data(self.i_embed).view(N, dk), g.gradient(self.i_embed).view(N, dk)
+        tok = Var(ops.tanh(emb.t().contiguous()).view(dk, 1, N))  # tanh(embed)^T: the tokens as channel-major columns
+        tape.record(lambda: tok.grad is not None and ops.axpby(1.0, demb, 1.0, ops.tanh_bwd(tok.grad, tok.data).view(dk, N).t().contiguous(), out=demb))
+        keys, values = self._dense(tape, tok, self.wk), self._dense(tape, tok, self.wv)
+        E = keys.data.shape[0]
+        style_t, probs = ops.gst_attention_fwd(q.data.view(E, B), keys.data.view(E, N), values.data.view(E, N), self.heads, save=not _EVAL[0])
+        style = Var(style_t)
+
+        def att_bwd():
+            if style.grad is None:
+                return
+            dq, dk_, dv = ops.gst_attention_bwd(style.grad, q.data.view(E, B), keys.data.view(E, N), values.data.view(E, N), probs, self.heads)
+            q.accumulate(dq.view(E, 1, B))
+            keys.accumulate(dk_.view(E, 1, N))
+            values.accumulate(dv.view(E, 1, N))
+
+        tape.record(att_bwd)
+        return style
+
+
 class FastSpeech2Trainer:
     """``tr = FastSpeech2Trainer(config, stats); losses = tr.training_step(batch)``.
 
@@ -713,6 +830,7 @@ class FastSpeech2Trainer:
         self.encoder = _ConformerT(g, c.encoder, "encoder")
         self.speaker_table = Table(g, "speaker_embedding.weight", max(1, c.n_speakers), d) if c.multispeaker else None
         self.language_table = Table(g, "language_embedding.weight", max(1, c.n_languages), d) if c.multilingual else None
+        self.gst = _StyleTokensT(g, c) if c.use_global_style_token_module else None
         vp = c.variance_predictors
         self.duration_predictor = _VariancePredictorT(g, vp.duration, "duration_predictor")
         self.pitch_predictor = _VariancePredictorT(g, vp.pitch, "pitch_predictor")
@@ -735,7 +853,7 @@ class FastSpeech2Trainer:
         # effective weights, norms and gradient sinks of the 30 weight-normed layers in three flat buffers: ONE launch per step computes
         # w = g v / ||v|| for all of them and one turns the sinks into (dg, dv) -- 90 launches of ~4 us at the two ends of the step otherwise
         self._wn_batch = WNBatch(self.params, self._wn)
-        self._bn = self.encoder.batchnorms() + self.decoder.batchnorms() + [bn for _, bn in self.postnet]
+        self._bn = self.encoder.batchnorms() + self.decoder.batchnorms() + [bn for _, bn in self.postnet] + (self.gst.batchnorms() if self.gst else [])
         self.global_step = 0
         self.current_epoch = 0  # the driver advances it; only the binarisation-loss warm-up reads it
         self._prior = None
@@ -783,12 +901,13 @@ class FastSpeech2Trainer:
         self.load_state_dict(sd, strict=False)
 
     def load_state_dict(self, sd: dict, strict: bool = True):
-        names = set(self.params.names())
+        names = self.params.names()
+        missing = [name for name in names if name not in sd]
+        if strict and missing:  # (before anything is copied: a refused state dict leaves the trainer as it was)
+            raise KeyError(f"missing parameter {missing[0]}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
         for name in names:
             if name in sd:
                 self.params.load(name, sd[name])
-            elif strict:
-                raise KeyError(f"missing parameter {name}")
         for bn in self._bn:
             if bn.prefix + ".running_mean" in sd:
                 bn.running_mean.copy_(sd[bn.prefix + ".running_mean"])
@@ -893,6 +1012,8 @@ class FastSpeech2Trainer:
         if not learn:
             d["durations"] = fit(up(dur_host, torch.int32), {1: Lp}).contiguous()
         d["mel_t"] = fit(up(batch["mel"], torch.float32), {1: Tp}).permute(2, 0, 1).contiguous()  # [n_mels, B, T]
+        if self.gst is not None:  # the style reference = the utterance's own target mel, as the one-channel image [B, T, n_mels]
+            d["mel_btf"] = d["mel_t"].permute(1, 2, 0).contiguous()  # (from the copy already on the device: no second upload)
         if learn and batch.get("attn_prior") is not None:
             d["attn_prior"] = fit(up(batch["attn_prior"], torch.float64), {1: Tp, 2: Lp}).contiguous()
         for key in ("pitch", "energy"):
@@ -1099,6 +1220,8 @@ class FastSpeech2Trainer:
         for table, key in ((self.speaker_table, "speakers"), (self.language_table, "languages")):
             if table is not None:
                 x = self._add_item_embedding(tape, x, table, batch[key], lens)
+        if self.gst is not None:
+            x = self._add_style_embedding(tape, x, self.gst.forward(tape, batch["mel_btf"]), lens)
 
         w = tr.duration_loss_weight
         # The three variance predictors are side branches under teacher forcing (the decoder takes the TARGETS' embeddings): ~170 launches
@@ -1269,6 +1392,28 @@ class FastSpeech2Trainer:
                 return
             _chk(lib.evmi_fs2_item_embedding_bwd_f32(y.grad.data_ptr(), item_ids.data_ptr(), lens.data_ptr(), table.grad().data_ptr(), table.rows, B, L, D, _s(out)),
                  "evmi_fs2_item_embedding_bwd_f32")
+            x.accumulate(y.grad)
+
+        tape.record(bwd)
+        return y
+
+    def _add_style_embedding(self, tape, x: Var, style: Var, lens):
+        """x[:, b, l] += style[b] at the non-padded positions: the item-embedding kernels with the style matrix [B, D] as the table."""
+        lib = _lib.load()
+        D, B, L = x.data.shape
+        rows = torch.arange(B, device=x.data.device, dtype=torch.int32)
+        out = x.data.clone()
+        _chk(lib.evmi_fs2_add_item_embedding_f32(out.data_ptr(), rows.data_ptr(), lens.data_ptr(), style.data.data_ptr(), B, L, D, _s(out)),
+             "evmi_fs2_add_item_embedding_f32")
+        y = Var(out)
+
+        def bwd():
+            if y.grad is None:
+                return
+            ds = torch.zeros(B, D, device=out.device, dtype=torch.float32)
+            _chk(lib.evmi_fs2_item_embedding_bwd_f32(y.grad.data_ptr(), rows.data_ptr(), lens.data_ptr(), ds.data_ptr(), B, B, L, D, _s(out)),
+                 "evmi_fs2_item_embedding_bwd_f32")
+            style.accumulate(ds)
             x.accumulate(y.grad)
 
         tape.record(bwd)

@@ -1386,3 +1386,100 @@ def align_attention_bwd(q, k, soft, logprob, prior, hard, dlogprob, text_lens32,
     _chk(lib.evmi_align_qk_grad_f32(q.data_ptr(), rs.data_ptr(), dq.data_ptr(), A, B * T, -2.0 * temperature, _s(q)), "evmi_align_qk_grad_f32")
     _chk(lib.evmi_align_qk_grad_f32(k.data_ptr(), cs.data_ptr(), dk.data_ptr(), A, B * L, -2.0 * temperature, _s(q)), "evmi_align_qk_grad_f32")
     return dq, dk
+
+
+# ---- Global Style Token module (csrc/gst.hip): fp32 in both precision modes -------------------------------------------------------
+class exact_f32:
+    """``with exact_f32():`` the dense operators inside run on exact fp32 operands whatever the model's precision mode (the style
+    module is tiny and recurrent: the wrong place to save bits) and issue their weight gradients in place: a launch collected for the
+    sibling stream (``side_wgrad``) would run later, under whatever mode holds then."""
+
+    def __enter__(self):
+        self.prev = CONV_BACKEND["operands"], SIDE_WGRAD["on"]
+        CONV_BACKEND["operands"], SIDE_WGRAD["on"] = "f32", False
+
+    def __exit__(self, *exc):
+        CONV_BACKEND["operands"], SIDE_WGRAD["on"] = self.prev
+        return False
+
+
+def gst_conv_out(n: int) -> int:
+    """Output length of the reference encoder's convolution (k = 3, stride 2, padding 1) on an axis of n."""
+    return (n - 1) // 2 + 1
+
+
+def gst_conv2d_fwd(x, w, bias, act=ACT_NONE):
+    """x [Cin, B, H, W], w [Cout, Cin, 3, 3] -> y [Cout, B, OH, OW]; act: ACT_NONE or ACT_RELU (inference: folded BatchNorm + ReLU)."""
+    cin, B, H, W = x.shape
+    cout = w.shape[0]
+    y = torch.empty(cout, B, gst_conv_out(H), gst_conv_out(W), device=x.device, dtype=torch.float32)
+    _chk(_lib.load().evmi_gst_conv2d_fwd_f32(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), y.data_ptr(), cin, cout, B, H, W, act, _s(x)),
+         "evmi_gst_conv2d_fwd_f32")
+    _FLOPS[0] += 2.0 * y.numel() * cin * 9
+    return y
+
+
+def gst_conv2d_dgrad(dy, w, H, W):
+    """-> dx [Cin, B, H, W] of dy [Cout, B, OH, OW]."""
+    cout, cin = w.shape[:2]
+    B = dy.shape[1]
+    dx = torch.empty(cin, B, H, W, device=dy.device, dtype=torch.float32)
+    _chk(_lib.load().evmi_gst_conv2d_dgrad_f32(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), cin, cout, B, H, W, _s(dy)), "evmi_gst_conv2d_dgrad_f32")
+    _FLOPS[0] += 2.0 * dy.numel() * cin * 9
+    return dx
+
+
+def gst_conv2d_wgrad(x, dy, dw, db, accumulate=True):
+    """dw [Cout, Cin, 3, 3] and db [Cout] (or None) (+)= the weight / bias gradient (fixed summation order)."""
+    cin, B, H, W = x.shape
+    cout = dy.shape[0]
+    lib = _lib.load()
+    elems = lib.evmi_gst_conv2d_wgrad_ws_elems(cin, cout, B, H, W)
+    ws = WS.get("gst_wgrad", elems, x.device)
+    _chk(lib.evmi_gst_conv2d_wgrad_f32(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _lib.ptr(db), ws.data_ptr(), elems, cin, cout, B, H, W,
+                                       int(accumulate), _s(x)), "evmi_gst_conv2d_wgrad_f32")
+    _FLOPS[0] += 2.0 * dy.numel() * cin * 9
+
+
+def gst_gru_fwd(gi, whh, bhh, save=True):
+    """gi [3H, B, T] (x W_ih^T + b_ih of every step) -> (last hidden state [H, B], what the backward needs or None)."""
+    H3, B, T = gi.shape
+    H = H3 // 3
+    dev = gi.device
+    hlast = torch.empty(H, B, device=dev, dtype=torch.float32)
+    saved = (torch.empty(H3, B, T, device=dev, dtype=torch.float32), torch.empty(H, B, T, device=dev, dtype=torch.float32),
+             torch.empty(H, B, T, device=dev, dtype=torch.float32)) if save else None
+    _chk(_lib.load().evmi_gst_gru_fwd_f32(gi.data_ptr(), whh.data_ptr(), bhh.data_ptr(), *([t.data_ptr() for t in saved] if save else [0, 0, 0]),
+                                          hlast.data_ptr(), B, T, H, _s(gi)), "evmi_gst_gru_fwd_f32")
+    return hlast, saved
+
+
+def gst_gru_bwd(saved, whh, dhlast):
+    """-> (dgi [3H, B, T], dgh [3H, B, T]); saved[2] is hprev [H, B, T]: dW_hh = dgh . hprev^T, db_hh = row sums of dgh."""
+    rzn, hn, hprev = saved
+    H3, B, T = rzn.shape
+    dgi, dgh = torch.empty_like(rzn), torch.empty_like(rzn)
+    _chk(_lib.load().evmi_gst_gru_bwd_f32(rzn.data_ptr(), hn.data_ptr(), hprev.data_ptr(), whh.data_ptr(), dhlast.data_ptr(), dgi.data_ptr(),
+                                          dgh.data_ptr(), B, T, H3 // 3, _s(rzn)), "evmi_gst_gru_bwd_f32")
+    return dgi, dgh
+
+
+def gst_attention_fwd(q, keys, values, heads, save=True):
+    """q [E, B], keys / values [E, N] -> (style [B, E], probabilities [B, heads, N] or None)."""
+    E, B = q.shape
+    N = keys.shape[1]
+    style = torch.empty(B, E, device=q.device, dtype=torch.float32)
+    probs = torch.empty(B, heads, N, device=q.device, dtype=torch.float32) if save else None
+    _chk(_lib.load().evmi_gst_attention_fwd_f32(q.data_ptr(), keys.data_ptr(), values.data_ptr(), style.data_ptr(), _lib.ptr(probs), B, N, E, heads,
+                                                _s(q)), "evmi_gst_attention_fwd_f32")
+    return style, probs
+
+
+def gst_attention_bwd(dstyle, q, keys, values, probs, heads):
+    """-> (dq [E, B], dkeys [E, N], dvalues [E, N])."""
+    E, B = q.shape
+    N = keys.shape[1]
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(keys), torch.empty_like(values)
+    _chk(_lib.load().evmi_gst_attention_bwd_f32(dstyle.data_ptr(), q.data_ptr(), keys.data_ptr(), values.data_ptr(), probs.data_ptr(), dq.data_ptr(),
+                                                dk.data_ptr(), dv.data_ptr(), B, N, E, heads, _s(q)), "evmi_gst_attention_bwd_f32")
+    return dq, dk, dv

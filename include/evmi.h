@@ -799,7 +799,7 @@ typedef struct evmi_ln_partials {
   long long n_cols;    /* of that call */
 } evmi_ln_partials;
 int evmi_layernorm_bwd_partials_reduce(int n_jobs, const evmi_ln_partials* jobs, void* stream);
-/* BatchNorm1d in training mode over every column of a channel row, followed by act (0 none, 2 SiLU, 4 tanh):
+/* BatchNorm1d in training mode over every column of a channel row, followed by act (0 none, 2 SiLU, 3 ReLU, 4 tanh):
  * writes the batch mean / 1/sqrt(var + eps) [C] and, when given, updates the running statistics (unbiased variance).
  * momentum < 0: evaluation mode (model.eval() in the reference's validation loop) -- the running statistics normalise and are
  * not updated. */
@@ -891,6 +891,38 @@ int evmi_align_attention_bwd_f32(const float* soft_dev, const float* logprob_dev
  * and dk (m = Q . da, coef = -2 temp with the sign folded: dk = 2 temp (m - k * colsum)). */
 int evmi_align_qk_grad_f32(const float* x_dev, const float* sums_dev, float* m_dev, int A, long long BN, float coef,
                            void* stream);
+
+/* Global Style Token module of FastSpeech2 (csrc/gst.hip), fp32.
+ * Reference encoder: 3 x 3 convolution with stride 2 and padding 1 on channel-major x [Cin][B][H][W] -> y [Cout][B][OH][OW],
+ * O = (n - 1) / 2 + 1 on both axes, w [Cout][Cin][3][3], bias [Cout] or NULL; act 0 (none) or 3 (ReLU: the folded eval-mode
+ * BatchNorm + ReLU of inference).  H, W are the INPUT sizes in all three entry points. */
+int evmi_gst_conv2d_fwd_f32(const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, int Cin, int Cout,
+                            int B, int H, int W, int act, void* stream);
+/* dx [Cin][B][H][W] = the input gradient of dy [Cout][B][OH][OW] (written, not accumulated). */
+int evmi_gst_conv2d_dgrad_f32(const float* dy_dev, const float* w_dev, float* dx_dev, int Cin, int Cout, int B, int H, int W,
+                              void* stream);
+/* dw [Cout][Cin][3][3] and db [Cout] (or NULL) = (accumulate ? themselves : 0) + the gradients; partial sums over slices of the
+ * positions in ws (evmi_gst_conv2d_wgrad_ws_elems floats), added in a fixed order. */
+long long evmi_gst_conv2d_wgrad_ws_elems(int Cin, int Cout, int B, int H, int W);
+int evmi_gst_conv2d_wgrad_f32(const float* x_dev, const float* dy_dev, float* dw_dev, float* db_dev, float* ws_dev,
+                              long long ws_elems, int Cin, int Cout, int B, int H, int W, int accumulate, void* stream);
+/* The recurrence of a single-layer GRU (torch gate order r, z, n; h_0 = 0) in one launch: gi [3H][B][T] = x W_ih^T + b_ih of every
+ * step, whh [3H][H], bhh [3H] -> hlast [H][B].  Training also saves rzn [3H][B][T] (activated gates), hn [H][B][T] (W_hn h + b_hn)
+ * and hprev [H][B][T] (the state each step started from); all three NULL for inference.  H = 32, 64 or 128. */
+int evmi_gst_gru_fwd_f32(const float* gi_dev, const float* whh_dev, const float* bhh_dev, float* rzn_dev, float* hn_dev,
+                         float* hprev_dev, float* hlast_dev, int B, int T, int H, void* stream);
+/* Backward through all steps in one launch from dhlast [H][B]: dgi [3H][B][T] (gradient of the projected inputs) and dgh [3H][B][T]
+ * (gradient of W_hh h + b_hh: dW_hh = dgh . hprev^T and db_hh = its row sums, a dense layer's weight gradient). */
+int evmi_gst_gru_bwd_f32(const float* rzn_dev, const float* hn_dev, const float* hprev_dev, const float* whh_dev,
+                         const float* dhlast_dev, float* dgi_dev, float* dgh_dev, int B, int T, int H, void* stream);
+/* Style-token attention: one query per item q [E][B] against keys / values [E][N] (N <= 16 tokens), `heads` heads of E / heads,
+ * scores q.k / sqrt(E / heads), softmax over the tokens -> style [B][E]; probs [B][heads][N] (or NULL) is saved for the backward. */
+int evmi_gst_attention_fwd_f32(const float* q_dev, const float* keys_dev, const float* values_dev, float* style_dev,
+                               float* probs_dev, int B, int N, int E, int heads, void* stream);
+/* dq [E][B], dkeys / dvalues [E][N] (sums over the items in item order) from dstyle [B][E]. */
+int evmi_gst_attention_bwd_f32(const float* dstyle_dev, const float* q_dev, const float* keys_dev, const float* values_dev,
+                               const float* probs_dev, float* dq_dev, float* dkeys_dev, float* dvalues_dev, int B, int N, int E,
+                               int heads, void* stream);
 
 #ifdef __cplusplus
 }
