@@ -779,6 +779,17 @@ using namespace evmi;
 
 #define EVMI_NONNULL(p, what) \
   if (!(p)) return fail(EVMI_ERR_INVALID_ARG, what ": null pointer")
+// Argument refusals come BEFORE any HIP call: they cost nothing, need no device and can never reach one.
+#define EVMI_REQUIRE(cond, msg) \
+  if (!(cond)) return fail(EVMI_ERR_INVALID_ARG, msg)
+
+// Operands an elementwise op code reads besides `a` (bit 0: b, bit 1: c), from the table above ew_kernel:
+//   b: 1 3 4 6 7 10 11 12 15 17 18 19 22      c: 12 20 21 22 24
+static int ew_reads(int op) {
+  static const unsigned char reads[25] = {/*0*/ 0, 1, 0, 1, 1, /*5*/ 0, 1, 1, 0, 0, /*10*/ 1, 1, 3, 0, 0,
+                                          /*15*/ 1, 0, 1, 1, 1, /*20*/ 2, 2, 3, 0, 2};
+  return op >= 0 && op < 25 ? reads[op] : 0;
+}
 
 extern "C" {
 
@@ -842,6 +853,7 @@ int evmi_fold_cbt_f32(const float* dcol_dev, float* dx_dev, int C, int B, int t_
 
 int evmi_bias_add_rows_f32(float* y_dev, const float* bias_dev, int rows, long long n_per_row, void* stream) {
   EVMI_NONNULL(y_dev && bias_dev, "bias_add_rows");
+  EVMI_REQUIRE(rows >= 1 && n_per_row >= 1, "bias_add_rows: rows and n_per_row must be positive");
   const long long n = (long long)rows * n_per_row;
   hipLaunchKernelGGL(bias_add_rows_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, y_dev, bias_dev, n_per_row, n);
   EVMI_LAUNCH_CHECK("bias_add_rows");
@@ -852,6 +864,9 @@ int evmi_bias_add_rows_f32(float* y_dev, const float* bias_dev, int rows, long l
 int evmi_row_reduce_f32(int mode, const float* a_dev, const float* b_dev, float* out_dev, int rows, long long n_per_row,
                         float scale, int accumulate, void* stream) {
   EVMI_NONNULL(a_dev && out_dev, "row_reduce");
+  EVMI_REQUIRE(mode >= 0 && mode <= 2, "row_reduce: mode");
+  EVMI_REQUIRE(mode != 1 || b_dev, "row_reduce: mode 1 (a * b) needs b");
+  EVMI_REQUIRE(rows >= 1 && n_per_row >= 1, "row_reduce: rows and n_per_row must be positive");
   hipStream_t s = (hipStream_t)stream;
   // few long rows: split every row into segments so the chip is busy (two passes, fixed summation order)
   constexpr int MAXSEG = 64;
@@ -874,6 +889,7 @@ int evmi_row_reduce_f32(int mode, const float* a_dev, const float* b_dev, float*
 int evmi_lrelu_bwd_rowsum_f32(const float* dy_dev, const float* y_dev, float* dpre_dev, float* db_dev, int rows, long long n_per_row,
                               float slope, int accumulate, void* stream) {
   EVMI_NONNULL(dy_dev && y_dev && dpre_dev && db_dev, "lrelu_bwd_rowsum");
+  EVMI_REQUIRE(rows >= 1 && n_per_row >= 1, "lrelu_bwd_rowsum: rows and n_per_row must be positive");
   hipStream_t s = (hipStream_t)stream;
   constexpr int MAXSEG = 64;
   float* part = nullptr;
@@ -892,6 +908,10 @@ int evmi_lrelu_bwd_rowsum_f32(const float* dy_dev, const float* y_dev, float* dp
 int evmi_elementwise_f32(int op, const float* a_dev, const float* b_dev, const float* c_dev, float* y_dev, long long n,
                          float p0, float p1, void* stream) {
   EVMI_NONNULL(a_dev && y_dev, "elementwise");
+  EVMI_REQUIRE(op >= 0 && op <= 24, "elementwise: unknown op");
+  EVMI_REQUIRE(n >= 1, "elementwise: n must be positive");
+  EVMI_REQUIRE(!(ew_reads(op) & 1) || b_dev, "elementwise: this op reads b");
+  EVMI_REQUIRE(!(ew_reads(op) & 2) || c_dev, "elementwise: this op reads c");
   hipStream_t s = (hipStream_t)stream;
 #define EW(OPN) case OPN: hipLaunchKernelGGL(ew_kernel<OPN>, grid1d(n), dim3(256), 0, s, a_dev, b_dev, c_dev, y_dev, n, p0, p1); break;
   switch (op) {
@@ -907,6 +927,9 @@ int evmi_elementwise_f32(int op, const float* a_dev, const float* b_dev, const f
 int evmi_scalar_reduce_f32(int mode, const float* a_dev, const float* b_dev, float* out_dev, long long n, float scale,
                            float p, int accumulate, void* stream) {
   EVMI_NONNULL(a_dev && out_dev, "scalar_reduce");
+  EVMI_REQUIRE(mode >= 0 && mode <= 2, "scalar_reduce: mode");
+  EVMI_REQUIRE(mode != 0 || b_dev, "scalar_reduce: mode 0 (|a - b|) needs b");
+  EVMI_REQUIRE(n >= 1, "scalar_reduce: n must be positive");
   hipStream_t s = (hipStream_t)stream;
   constexpr int MAXB = 1024;
   float* part_f = nullptr;
@@ -927,6 +950,7 @@ int evmi_scalar_reduce_f32(int mode, const float* a_dev, const float* b_dev, flo
 
 int evmi_avgpool4s2_f32(const float* x_dev, float* y_dev, long long rows, int t_in, int backward, void* stream) {
   EVMI_NONNULL(x_dev && y_dev, "avgpool4s2");
+  EVMI_REQUIRE(rows >= 1 && t_in >= 1, "avgpool4s2: rows and t_in must be positive");
   const int t_out = t_in / 2 + 1;  // (t_in + 2*2 - 4) / 2 + 1
   const long long n = rows * (backward ? t_in : t_out);
   hipLaunchKernelGGL(avgpool4s2_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, x_dev, y_dev, t_in, t_out, n, backward);
@@ -936,7 +960,10 @@ int evmi_avgpool4s2_f32(const float* x_dev, float* y_dev, long long rows, int t_
 
 int evmi_period_view_f32(const float* x_dev, float* x2_dev, int B, int T, int period, int backward, void* stream) {
   EVMI_NONNULL(x_dev && x2_dev, "period_view");
+  EVMI_REQUIRE(B >= 1 && T >= 1 && period >= 1, "period_view: B, T and period must be positive");
   const int H = (T + period - 1) / period;
+  // reflect padding mirrors around the last sample: a pad of T or more would read in front of the row
+  EVMI_REQUIRE((long long)H * period - T < T, "period_view: the reflect padding (to a multiple of period) must be shorter than T");
   if (!backward) {
     const long long n = (long long)B * period * H;
     hipLaunchKernelGGL(period_view_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, x_dev, x2_dev, T, H, period, n);
@@ -950,6 +977,8 @@ int evmi_period_view_f32(const float* x_dev, float* x2_dev, int B, int T, int pe
 
 int evmi_stft_frames_f32(const float* x_dev, float* frames_dev, int B, int T, int n_fft, int hop, int backward, void* stream) {
   EVMI_NONNULL(x_dev && frames_dev, "stft_frames");
+  EVMI_REQUIRE(B >= 1 && T >= 1 && n_fft >= 1 && hop >= 1, "stft_frames: B, T, n_fft and hop must be positive");
+  EVMI_REQUIRE(n_fft / 2 < T, "stft_frames: the reflect padding n_fft / 2 must be shorter than T");
   const int F = 1 + T / hop;
   if (!backward) {
     const long long n = (long long)n_fft * B * F;
@@ -965,6 +994,7 @@ int evmi_stft_frames_f32(const float* x_dev, float* frames_dev, int B, int T, in
 int evmi_weight_norm_fwd_f32(const float* g_dev, const float* v_dev, float* w_dev, float* norm_dev, int rows, int n_per_row,
                              void* stream) {
   EVMI_NONNULL(g_dev && v_dev && w_dev && norm_dev, "weight_norm_fwd");
+  EVMI_REQUIRE(rows >= 1 && n_per_row >= 1, "weight_norm_fwd: rows and n_per_row must be positive");
   hipLaunchKernelGGL(weight_norm_fwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, g_dev, v_dev, w_dev, norm_dev, n_per_row);
   EVMI_LAUNCH_CHECK("weight_norm_fwd");
   return EVMI_OK;
@@ -973,6 +1003,7 @@ int evmi_weight_norm_fwd_f32(const float* g_dev, const float* v_dev, float* w_de
 int evmi_weight_norm_bwd_f32(const float* g_dev, const float* v_dev, const float* norm_dev, const float* dw_dev, float* dg_dev,
                              float* dv_dev, int rows, int n_per_row, void* stream) {
   EVMI_NONNULL(g_dev && v_dev && norm_dev && dw_dev && dg_dev && dv_dev, "weight_norm_bwd");
+  EVMI_REQUIRE(rows >= 1 && n_per_row >= 1, "weight_norm_bwd: rows and n_per_row must be positive");
   hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, g_dev, v_dev, norm_dev, dw_dev, dg_dev, dv_dev, n_per_row);
   EVMI_LAUNCH_CHECK("weight_norm_bwd");
   return EVMI_OK;
@@ -1025,6 +1056,7 @@ int evmi_reflect_pad_left1_f32(const float* src_dev, float* dst_dev, long long r
 
 int evmi_normalize_vec_f32(const float* x_dev, float* y_dev, int n, float eps, void* stream) {
   EVMI_NONNULL(x_dev && y_dev, "normalize_vec");
+  EVMI_REQUIRE(n >= 1, "normalize_vec: n must be positive");
   hipLaunchKernelGGL(normalize_vec_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x_dev, y_dev, n, eps);
   EVMI_LAUNCH_CHECK("normalize_vec");
   return EVMI_OK;
@@ -1071,8 +1103,9 @@ int evmi_store_u64(unsigned long long* dst_dev, unsigned long long value, void* 
 static int optimizer_step_impl(int kind, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, long long n, float lr, float beta1,
                                float beta2, float eps, float weight_decay, int step, const int* step_dev, float clip, const float* lr_dev,
                                void* stream) {
-  EVMI_NONNULL(p_dev && g_dev && v_dev && (kind == 2 || m_dev), "optimizer_step");
   if (kind < 0 || kind > 2) return fail(EVMI_ERR_INVALID_ARG, "optimizer_step: kind (0 AdamW, 1 Adam, 2 RMSprop)");
+  EVMI_NONNULL(p_dev && g_dev && v_dev && (kind == 2 || m_dev), "optimizer_step");
+  EVMI_REQUIRE(n >= 1, "optimizer_step: n must be positive");
   if ((reinterpret_cast<uintptr_t>(p_dev) | reinterpret_cast<uintptr_t>(g_dev) | reinterpret_cast<uintptr_t>(m_dev) | reinterpret_cast<uintptr_t>(v_dev)) & 15)
     return fail(EVMI_ERR_INVALID_ARG, "optimizer_step: buffers must be 16-byte aligned");
   hipLaunchKernelGGL(optimizer_step_kernel, grid1d((n >> 2) + 3), dim3(256), 0, (hipStream_t)stream, kind, p_dev, g_dev, m_dev, v_dev, n, lr, beta1,
@@ -1083,6 +1116,7 @@ static int optimizer_step_impl(int kind, float* p_dev, const float* g_dev, float
 
 int evmi_transpose_bct_cbt_f32(const float* in_dev, float* out_dev, int B, int C, int T, void* stream) {
   EVMI_NONNULL(in_dev && out_dev, "transpose_bct_cbt");
+  EVMI_REQUIRE(B >= 1 && C >= 1 && T >= 1, "transpose_bct_cbt: B, C and T must be positive");
   const long long n = (long long)B * C * T;
   hipLaunchKernelGGL(transpose_bct_cbt_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, B, C, T, n);
   EVMI_LAUNCH_CHECK("transpose_bct_cbt");
@@ -1099,6 +1133,7 @@ int evmi_counter_add_i32(int* counter_dev, int delta, void* stream) {
 int evmi_spectral_norm_grad_f32(float* gw_dev, const float* dw_dev, const float* u_dev, const float* v_dev, const float* sigma_dev,
                                 const float* dot_dev, int rows, int cols, void* stream) {
   EVMI_NONNULL(gw_dev && dw_dev && u_dev && v_dev && sigma_dev && dot_dev, "spectral_norm_grad");
+  EVMI_REQUIRE(rows >= 1 && cols >= 1, "spectral_norm_grad: rows and cols must be positive");
   const long long n = (long long)rows * cols;
   hipLaunchKernelGGL(sn_grad_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, gw_dev, dw_dev, u_dev, v_dev, sigma_dev, dot_dev, cols, n);
   EVMI_LAUNCH_CHECK("spectral_norm_grad");
@@ -1115,6 +1150,7 @@ int evmi_ratio_accumulate_f32(float* out_dev, const float* sq_dev, float weight,
 int evmi_adamw_f32(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, long long n, float lr, float beta1, float beta2,
                    float eps, float weight_decay, int step, void* stream) {
   EVMI_NONNULL(p_dev && g_dev && m_dev && v_dev, "adamw");
+  EVMI_REQUIRE(n >= 1, "adamw: n must be positive");
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adamw_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, p_dev, g_dev, m_dev, v_dev, n, lr, beta1, beta2, eps,
                      weight_decay, bc1, bc2);

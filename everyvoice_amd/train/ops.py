@@ -111,6 +111,8 @@ def fold(dcol, C, B, t_in, t_out, k, stride, pad, dil, out=None, accumulate=Fals
 def elementwise(op, a, b=None, c=None, out=None, p0=0.0, p1=0.0):
     if out is None:
         out = torch.empty_like(a)
+    if a.numel() == 0:  # nothing to do (a zero-element bias, an empty buffer to clear): the library refuses n < 1
+        return out
     _chk(_lib.load().evmi_elementwise_f32(op, a.data_ptr(), _lib.ptr(b), _lib.ptr(c), out.data_ptr(), a.numel(), p0, p1, _s(a)), "evmi_elementwise_f32")
     return out
 

@@ -548,6 +548,17 @@ int evmi_conv1d_wgrad_cbt_f32(const float* x_dev, const float* dy_dev, float* dw
  * wt[c_in][c_out/groups][M], M = ceil((k - phi) / stride), wt[g*cin_g+ci][co][m] = w[g*cout_g+co][ci][phi + stride*(M-1-m)]. */
 int evmi_dgrad_weights_f32(const float* w_dev, float* wt_dev, int c_in, int c_out, int k, int groups,
                            int stride, int phi, void* stream);
+/* Preconditions of the fp32 training primitives below (evmi_gemm_batched_f32 ... evmi_adamw_f32).  They are checked on the host
+ * and a call that breaks one returns EVMI_ERR_INVALID_ARG before anything is launched (evmi_last_error() names the entry point):
+ *   - every size (rows, n, n_per_row, B, C, T, period, n_fft, hop, ...) is at least 1; an empty problem is the caller's to skip;
+ *   - a mode / op / kind outside its documented range is refused, never mapped to a default;
+ *   - optional operands are required where the mode or op code reads them: b for evmi_row_reduce_f32 mode 1 and
+ *     evmi_scalar_reduce_f32 mode 0; b and / or c for the evmi_elementwise_f32 op codes that read them (table beside the op list
+ *     in csrc/train_ops.hip); m for optimiser kinds 0 and 1;
+ *   - reflect padding must be shorter than T: evmi_period_view_f32 needs ceil(T / period) * period - T < T and
+ *     evmi_stft_frames_f32 needs n_fft / 2 < T (a longer pad would mirror to a position in front of the row);
+ *   - evmi_optimizer_step_f32 / evmi_optimizer_step_lrdev_f32 work in 16-byte vectors: p, g, m and v must be 16-byte aligned
+ *     (any n; the last n % 4 elements are updated one by one).  evmi_adamw_f32 has no alignment requirement. */
 /* `batch` such GEMMs at fixed element strides (the groups of a grouped convolution). */
 int evmi_gemm_batched_f32(int trans_a, int trans_b, int M, int N, int K, float alpha,
                           const float* a_dev, int lda, long long stride_a, const float* b_dev, int ldb,
@@ -577,10 +588,11 @@ int evmi_scalar_reduce_f32(int mode, const float* a_dev, const float* b_dev, flo
 /* AvgPool1d(4, 2, padding=2) on [rows][t_in] (MSD) and its adjoint. */
 int evmi_avgpool4s2_f32(const float* x_dev, float* y_dev, long long rows, int t_in, int backward,
                         void* stream);
-/* MPD view: reflect-pad [B][T] on the right to a multiple of `period`, then [B*period][T'/period]. */
+/* MPD view: reflect-pad [B][T] on the right to a multiple of `period`, then [B*period][T'/period].  The pad must be shorter
+ * than T. */
 int evmi_period_view_f32(const float* x_dev, float* x2_dev, int B, int T, int period, int backward,
                          void* stream);
-/* frames[k][b][f] = reflect_pad(x)[b][f*hop + k] -> [n_fft][B*(1 + T/hop)] (centred STFT) / adjoint. */
+/* frames[k][b][f] = reflect_pad(x)[b][f*hop + k] -> [n_fft][B*(1 + T/hop)] (centred STFT) / adjoint.  n_fft / 2 < T. */
 int evmi_stft_frames_f32(const float* x_dev, float* frames_dev, int B, int T, int n_fft, int hop,
                          int backward, void* stream);
 /* torch.nn.utils.weight_norm (dim 0): w = g * v / ||v|| per row, and its backward. */
@@ -613,7 +625,7 @@ int evmi_normalize_vec_f32(const float* x_dev, float* y_dev, int n, float eps, v
  * torch.optim.RMSprop (beta1 = alpha; m unused) -- the optimiser union of the reference's training config
  * (everyvoice/.schema/everyvoice-spec-to-wav-0.5.json:434-622).  `step` is the 1-based step number, read from
  * step_dev[0] instead when given (HIP-graph replay); clip > 0 clamps the updated parameters to +-clip (gan_type "wgan",
- * wgan_clip_value, same schema :573-605). */
+ * wgan_clip_value, same schema :573-605).  p, g, m, v: 16-byte aligned (EVMI_ERR_INVALID_ARG otherwise), n >= 1, kind 0..2. */
 int evmi_optimizer_step_f32(int kind, float* p_dev, const float* g_dev, float* m_dev, float* v_dev, long long n, float lr,
                             float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
                             float clip, void* stream);
