@@ -482,12 +482,8 @@ class FastSpeech2:
         refuses it): the style reference's mel [B, Ts, n_mels], or [1, Ts, n_mels] for one reference serving the whole batch."""
         if not self._ready:
             raise RuntimeError("load_state_dict() or init_random() first")
-        prev = ops.CONV_BACKEND["operands"]
-        ops.CONV_BACKEND["operands"] = self.precision
-        try:
+        with ops.mode(operands=self.precision):
             return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel)
-        finally:
-            ops.CONV_BACKEND["operands"] = prev
 
     def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None):
         lib, dev, c = _lib.load(), self.device, self.config

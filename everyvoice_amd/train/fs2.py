@@ -30,6 +30,7 @@ from ..fs2 import N_PHONOLOGICAL_FEATURES, FastSpeech2ModelConfig, Stats
 from . import ops
 from .autograd import _ACTIVATION_ELEMS, Tape, Var
 from .layers import ParamGroup, WNBatch, WNConv
+from .step import EAGER, BucketReducer, CapturedStep, on_own_stream, step_scope
 
 
 @dataclass
@@ -785,7 +786,7 @@ class _StyleTokensT:
         return style
 
 
-class FastSpeech2Trainer:
+class FastSpeech2Trainer(CapturedStep):
     """``tr = FastSpeech2Trainer(config, stats); losses = tr.training_step(batch)``.
 
     batch: ``ids [B, L]`` (0 = padding), ``lens [B]``, ``durations [B, L]`` (frames per symbol), ``mel [B, T, n_mels]`` (zero padded,
@@ -810,7 +811,8 @@ class FastSpeech2Trainer:
         self.last_step_branch_on_stream = False
         self.use_graph = bool(use_graph)
         self.graph_buckets = tuple(int(v) for v in graph_buckets) if graph_buckets else None  # (symbols, frames) multiples to pad to
-        self._graphs, self._graph_warm, self._graph_failed, self.last_step_was_graph = {}, {}, None, False
+        self._graph_init()
+        self.last_step_was_graph = False
         self.config = c = config or FastSpeech2ModelConfig()
         self.stats = stats or Stats()
         self.training = training or FastSpeech2TrainingConfig()
@@ -1074,12 +1076,8 @@ class FastSpeech2Trainer:
         """Forward in training mode + every loss + backward; gradients are left in ``self.params.grad``."""
         d, meta = self._prepare(batch)
         self._store_step_scalars(meta)
-        prev = ops.SEED_BASE[0]
-        ops.SEED_BASE[0] = self._seed_base
-        try:
+        with ops.mode(seed_base=self._seed_base):
             return self._forward_backward(d, meta)
-        finally:
-            ops.SEED_BASE[0] = prev
 
     def _forward_backward(self, batch: dict, meta: dict, segmented: bool = False):
         """The launch sequence of one step on a prepared (device) batch: no host read, no host-dependent argument.
@@ -1162,14 +1160,10 @@ class FastSpeech2Trainer:
                 main = torch.cuda.current_stream(dev)
                 self._align_fork.record(main)
                 self._pred_stream.wait_event(self._align_fork)
-                with torch.cuda.stream(self._pred_stream):
-                    side_on, ops.SIDE_WGRAD["on"] = ops.SIDE_WGRAD["on"], False
+                with torch.cuda.stream(self._pred_stream), ops.mode(side_wgrad=False):
                     pjoin["akeep"] = _held_tensors(pjoin["atape"]._ops)  # (outlive the KERNELS: the aligner's forward ran on the main stream)
-                    try:
-                        pjoin["atape"].backward()
-                        self._align_done.record(self._pred_stream)
-                    finally:
-                        ops.SIDE_WGRAD["on"] = side_on
+                    pjoin["atape"].backward()
+                    self._align_done.record(self._pred_stream)
                 pjoin["adone"] = self._align_done
             else:
                 pjoin["atape"].backward()
@@ -1299,14 +1293,10 @@ class FastSpeech2Trainer:
             main = torch.cuda.current_stream(dev)
             self._pred_fork.record(main)
             self._pred_stream.wait_event(self._pred_fork)
-            with torch.cuda.stream(self._pred_stream):
-                side_on, ops.SIDE_WGRAD["on"] = ops.SIDE_WGRAD["on"], False  # (their weight gradients stay on this stream: it is a side chain already)
+            with torch.cuda.stream(self._pred_stream), ops.mode(side_wgrad=False):  # (their weight gradients stay here: it is a side chain already)
                 keep = _held_tensors(pjoin["tape"]._ops)
-                try:
-                    pjoin["tape"].backward()
-                    self._pred_done.record(self._pred_stream)
-                finally:
-                    ops.SIDE_WGRAD["on"] = side_on
+                pjoin["tape"].backward()
+                self._pred_done.record(self._pred_stream)
             pjoin["done"] = self._pred_done
             if not torch.cuda.is_current_stream_capturing():
                 for t in [v for v in losses.values() if torch.is_tensor(v)]:
@@ -1358,14 +1348,12 @@ class FastSpeech2Trainer:
         """The losses of a batch in evaluation mode (the reference validates under ``model.eval()``): dropout off, BatchNorm
         normalising with its running statistics and leaving them (and ``num_batches_tracked``) untouched, no backward, no
         gradients written, no optimiser state touched."""
-        prev = ops.CONV_BACKEND["operands"]
-        ops.CONV_BACKEND["operands"] = self.precision
         _EVAL[0] = True
         try:
-            return self.forward_backward(batch)
+            with ops.mode(operands=self.precision):
+                return self.forward_backward(batch)
         finally:
             _EVAL[0] = False
-            ops.CONV_BACKEND["operands"] = prev
 
     def _phone_level(self, batch, key, cum, dur, pad, T):
         """Phone-level variance targets [B, L]: given as such (``pitch``), or frame-level (``pitch_frames`` [B, T]) averaged over
@@ -1455,33 +1443,22 @@ class FastSpeech2Trainer:
         as the reference's own padding does).  Eager and replayed steps are bit for bit the same arithmetic."""
         if self._stream is None:
             return self._training_step(batch)
-        caller = torch.cuda.current_stream(self.device)
-        self._stream.wait_stream(caller)
-        with torch.cuda.stream(self._stream):
-            losses = self._training_step(batch)
-        caller.wait_stream(self._stream)
+        losses, caller = on_own_stream(self._stream, self.device, self._training_step, batch)
         for v in losses.values():
             v.record_stream(caller)
         return losses
 
-    GRAPH_WARMUP_STEPS = 2
     GRAPH_CACHE = 24  # captured shapes kept (least recently used out first)
+    GRAPH_WARM_KEYS = 4096
 
     def _training_step(self, batch: dict) -> dict:
-        prev, prev_side, prev_base, prev_ln = ops.CONV_BACKEND["operands"], ops.SIDE_WGRAD["on"], ops.SEED_BASE[0], ops.LN_DEFER["on"]
-        ops.CONV_BACKEND["operands"] = self.precision
-        ops.SIDE_WGRAD["on"] = self.side_wgrad and self.device.type == "cuda"
-        ops.LN_DEFER["on"] = self.device.type == "cuda"  # (reduced where the backward chains end: ops.wgrad_join)
-        ops.SEED_BASE[0] = self._seed_base
-        ops.side_reset()  # nothing an aborted step left collected reaches this one (ops.side_reset)
-        try:
+        # (ln_defer: LayerNorm parameter gradients reduced where the backward chains end: ops.wgrad_join)
+        with step_scope(self.device, operands=self.precision, side_wgrad=self.side_wgrad, seed_base=self._seed_base, ln_defer=True):
             d, meta = self._prepare_on_upload_stream(batch)
             self._store_step_scalars(meta)
             self.last_step_was_graph = False
-            entry = None
-            if self.use_graph and self._graph_failed is None:
-                entry = self._graph_entry(d, meta)
-            if entry is None:
+            entry = self._graph_entry(self._graph_key(d, meta), lambda cap: self._capture(cap, d, meta)) if self.use_graph else EAGER
+            if entry is EAGER:
                 losses = self._step_body(d, meta)
             else:
                 # into the captured step's static inputs (same shapes and types by construction of the key): one multi-tensor launch
@@ -1492,26 +1469,14 @@ class FastSpeech2Trainer:
                 # losses across steps (running means, deferred logging) -- eager steps hand out fresh tensors too
                 losses = {k: v.clone() for k, v in entry["losses"].items()}
                 self.last_step_was_graph = True
-        except BaseException:
-            ops.side_reset(abort=True)
-            raise
-        finally:
-            ops.CONV_BACKEND["operands"] = prev
-            ops.SIDE_WGRAD["on"] = prev_side
-            ops.SEED_BASE[0] = prev_base
-            ops.LN_DEFER["on"] = prev_ln
-        ops.side_check_drained()
         self.global_step += 1
         return losses
 
     def _step_body(self, d: dict, meta: dict) -> dict:
         """Forward + backward + gradient exchange + clipping + optimiser on a prepared batch (eager; also what gets captured)."""
-        from .hifigan import BucketReducer
-
         # data parallel (SURVEY.md 8e): utterances are sharded across ranks, gradients averaged by a bucketed all-reduce that
         # overlaps backward (two buckets: see _forward_backward)
-        self._reducer = (BucketReducer(self.params.grad, self.pg if self.pg is not True else None,
-                                       lambda t, sc: ops.elementwise(ops.EW_SCALE, t, out=t, p0=sc)) if self.pg is not None else None)
+        self._reducer = BucketReducer(self.params.grad, self.pg if self.pg is not True else None) if self.pg is not None else None
         losses = self._forward_backward(d, meta)
         if self._reducer is not None:  # the head of the buffer (everything in front of the decoder), then wait + 1/world scaling
             self._reducer.launch(0, self._tail_offset())
@@ -1536,64 +1501,25 @@ class FastSpeech2Trainer:
         # (the binarisation weight itself is a device scalar: only whether the term exists shapes the launch sequence)
         return (meta["B"], meta["L"], meta["T"], tuple(sorted(d)), self.precision, self._bin_weight() > 0.0, tr.gradient_clip_val, self.pg is not None)
 
-    def _graph_entry(self, d: dict, meta: dict):
-        """The captured step for this batch's padded shape, or None (not seen often enough yet, or capturing failed: eager)."""
-        key = self._graph_key(d, meta)
-        entry = self._graphs.get(key)
-        if entry is not None:
-            self._graphs[key] = self._graphs.pop(key)  # most recently used last
-            return entry
-        n = self._graph_warm.get(key, 0)
-        if n < self.GRAPH_WARMUP_STEPS:  # eager steps grow the per-stream workspaces and set the kernels' launch attributes
-            self._graph_warm[key] = n + 1
-            if len(self._graph_warm) > 4096:
-                self._graph_warm.clear()
-            return None
-        try:
-            entry = self._capture(d, meta)
-        except Exception as e:  # noqa: BLE001 -- whatever the runtime objected to: the eager path is always available
-            self._graph_failed = f"{type(e).__name__}: {e}"
-            torch.cuda.synchronize(self.device)
-            ops.side_reset()  # the aborted capture's collected weight-gradient launches and its events must not reach the eager step
-            return None
-        self._graphs[key] = entry
-        while len(self._graphs) > self.GRAPH_CACHE:
-            self._graphs.pop(next(iter(self._graphs)))
-        return entry
+    def _capture(self, cap, d: dict, meta: dict) -> dict:
+        """Record the step on static copies of the inputs."""
+        inputs, holder = {k: v.clone() for k, v in d.items()}, {}
+        if self.pg is None:
+            cap(lambda: holder.__setitem__("losses", self._step_body(inputs, meta)))
+        else:
+            self._capture_data_parallel(cap, inputs, meta, holder)
+        return dict(inputs=inputs, losses=holder["losses"])
 
-    def _capture(self, d: dict, meta: dict) -> dict:
-        """Record the step on static copies of the inputs.  Capturing executes nothing: host-side counters the step's code bumps
-        (optimiser step, BatchNorm batch counts) are put back -- `_replay` advances them."""
-        inputs = {k: v.clone() for k, v in d.items()}
-        step0, batches0 = self.params._step, [bn.batches for bn in self._bn]
-        torch.cuda.synchronize(self.device)
-        graphs, holder = [], {}
-        pool = torch.cuda.graph_pool_handle()
+    def _host_counters(self):
+        return self.params._step, [bn.batches for bn in self._bn]
 
-        def cap(fn):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, stream=self._stream, capture_error_mode="thread_local"):
-                fn()
-            graphs.append(g)
+    def _set_host_counters(self, state):
+        self.params._step, batches = state
+        for bn, b in zip(self._bn, batches):
+            bn.batches = b
+        self._reducer = None  # (of the step that was recorded, not run)
 
-        try:
-            if self.pg is None:
-                cap(lambda: holder.__setitem__("losses", self._step_body(inputs, meta)))
-            else:
-                self._capture_data_parallel(cap, inputs, meta, holder)
-        finally:
-            self.params._step = step0
-            for bn, b in zip(self._bn, batches0):
-                bn.batches = b
-            self._reducer = None
-        return dict(graphs=graphs, inputs=inputs, losses=holder["losses"], cuts=holder.get("cuts", []))
-
-    def _replay(self, entry: dict) -> None:
-        graphs, cuts = entry["graphs"], entry["cuts"]
-        for i, g in enumerate(graphs):
-            g.replay()
-            if i < len(cuts):
-                cuts[i]()  # the gradient exchange that sits between two captured stretches (RCCL calls are not captured)
+    def _count_replay(self, entry):
         self.params._step += 1
         for bn in self._bn:
             bn.batches += 1
@@ -1602,9 +1528,7 @@ class FastSpeech2Trainer:
         """Under data parallelism the step is three captured stretches with the two bucket all-reduces issued between them, the
         first one on a side stream so that it runs UNDER the second stretch (the backward of the variance adaptor, the aligner
         and the encoder): forward + backward down to the decoder | rest of the backward | clipping + optimiser."""
-        from .hifigan import BucketReducer
-
-        red = BucketReducer(self.params.grad, self.pg if self.pg is not True else None, lambda t, sc: ops.elementwise(ops.EW_SCALE, t, out=t, p0=sc))
+        red = BucketReducer(self.params.grad, self.pg if self.pg is not True else None)
         lo_tail, n_all = self._tail_offset(), self.params.grad.numel()
         state = {}
 
@@ -1617,7 +1541,6 @@ class FastSpeech2Trainer:
                 pass
             self._finish_backward(holder["losses"])
 
-        cap(part_a)
-        cap(part_b)
+        cap(part_a, lambda: red.launch(lo_tail, n_all))
+        cap(part_b, lambda: (red.launch(0, lo_tail), red.finish()))
         cap(self._clip_and_update)
-        holder["cuts"] = [lambda: red.launch(lo_tail, n_all), lambda: (red.launch(0, lo_tail), red.finish())]

@@ -34,6 +34,7 @@ from ..spectral import slaney_mel_filterbank, windowed_dft_basis
 from . import autograd as ag
 from . import ops
 from .layers import ParamGroup, SNConv, WNBatch, WNConv, kaiming_uniform_conv_init_
+from .step import EAGER, BucketReducer, CapturedStep, allreduce_mean_, on_own_stream, step_scope  # noqa: F401 -- (the reducers: also found here)
 
 
 def _to_cbt(x_bct: torch.Tensor) -> torch.Tensor:
@@ -397,76 +398,7 @@ class MultiResolutionSTFTLoss:
         return grad
 
 
-def allreduce_mean_(flat_grad: torch.Tensor, process_group, scale_fn) -> torch.Tensor:
-    """flat_grad <- mean over ranks (sum all-reduce, then ``scale_fn(flat_grad, 1 / world)``)."""
-    import torch.distributed as dist
-
-    dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=process_group)
-    scale_fn(flat_grad, 1.0 / dist.get_world_size(process_group))
-    return flat_grad
-
-
-class BucketReducer:
-    """Data-parallel gradient exchange overlapped with backward: the flat gradient buffer of one optimiser is
-    reduced in contiguous buckets, each launched -- asynchronously, on a side stream when the buffer lives on a GPU -- the
-    moment backward has finished the last layer that writes into it; ``finish()`` waits for all of them and applies the
-    1/world scaling.  Backward visits the layers in reverse declaration order, so finished gradients form a growing suffix
-    of the buffer: ``launch(lo, hi)`` is called with adjacent, descending ranges.  RCCL over xGMI under backend "nccl"."""
-
-    def __init__(self, flat_grad: torch.Tensor, process_group, scale_fn):
-        self.flat, self.pg, self.scale_fn = flat_grad, process_group, scale_fn
-        self.works = []
-        self.stream = torch.cuda.Stream(flat_grad.device) if flat_grad.is_cuda else None
-        self.timing = None  # a list: every launch appends (start, end) events on the side stream (bench.py: all-reduce ms per step)
-
-    def launch(self, lo: int, hi: int) -> None:
-        import torch.distributed as dist
-
-        if hi <= lo:
-            return
-        chunk = self.flat[lo:hi]
-        if self.stream is not None:
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(self.flat.device))  # gradients of this bucket are final from here on
-            with torch.cuda.stream(self.stream):
-                self.stream.wait_event(ready)
-                if self.timing is not None:
-                    e0 = torch.cuda.Event(enable_timing=True)
-                    e0.record(self.stream)
-                # RCCL: enqueued behind `ready` on the side stream, runs while the launching stream goes on with backward
-                work = dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-                if self.timing is not None:  # (measurement runs only: order the side stream behind the collective, then stamp)
-                    work.wait()
-                    e1 = torch.cuda.Event(enable_timing=True)
-                    e1.record(self.stream)
-                    self.timing.append((e0, e1))
-                else:
-                    self.works.append(work)
-        else:
-            self.works.append(dist.all_reduce(chunk, op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
-
-    def finish(self) -> None:
-        import torch.distributed as dist
-
-        for w in self.works:
-            w.wait()
-        self.works.clear()
-        if self.stream is not None:
-            torch.cuda.current_stream(self.flat.device).wait_stream(self.stream)
-        self.scale_fn(self.flat, 1.0 / dist.get_world_size(self.pg))
-
-    def comm_ms(self, reset: bool = True) -> float:
-        """Summed device time of the recorded all-reduces (synchronises)."""
-        if not self.timing:
-            return 0.0
-        self.timing[-1][1].synchronize()
-        ms = sum(a.elapsed_time(b) for a, b in self.timing)
-        if reset:
-            self.timing.clear()
-        return ms
-
-
-class HiFiGANTrainer:
+class HiFiGANTrainer(CapturedStep):
     """Generator + MPD + MSD with two optimisers; ``training_step`` is one full GAN step."""
 
     LOSS_KEYS = ("d", "g_adv", "g_fm", "g_mel", "g_stft")
@@ -524,8 +456,7 @@ class HiFiGANTrainer:
         # mode (bitwise the same step), but capturing a step that forks a stream from an already forked stream ends in a
         # segmentation fault inside hipStreamEndCapture on ROCm 7.0, and graph mode is the faster one
         self.side_wgrad = bool(side_wgrad) and parallel_streams and not self.use_graph
-        self._graphs, self._graph_warm = {}, {}
-        self._graph_failed = None
+        self._graph_init()
         import os
 
         self.phase_times = {} if os.environ.get("EVMI_PHASE_TIMES") else None
@@ -626,13 +557,9 @@ class HiFiGANTrainer:
     def generate(self, mel_bct: torch.Tensor) -> torch.Tensor:
         """The generator alone with the current training weights (validation / synthesis during training): mel [B, n_mels, F]
         -> wav [B, 1, F * hop], no tape kept."""
-        prev = ops.CONV_BACKEND["operands"]
-        ops.CONV_BACKEND["operands"] = self.precision
-        try:
+        with ops.mode(operands=self.precision):
             self._materialize(self.generator.layers())
             y = self.generator.forward(ag.Tape(), ag.Var(_to_cbt_kernel(mel_bct.to(self.device, torch.float32)), needs_grad=False))
-        finally:
-            ops.CONV_BACKEND["operands"] = prev
         return y.data.view(mel_bct.shape[0], 1, -1)  # [1, B, T] and [B, 1, T] are the same bytes
 
     def _materialize(self, layers):
@@ -658,8 +585,7 @@ class HiFiGANTrainer:
         """Bucketed all-reduce of one optimiser's flat gradient buffer, overlapped with backward (None on one GPU)."""
         if self.pg is None:
             return None
-        return BucketReducer(group.grad, self.pg if self.pg is not True else None,
-                             lambda t, sc: ops.elementwise(ops.EW_SCALE, t, out=t, p0=sc))
+        return BucketReducer(group.grad, self.pg if self.pg is not True else None)
 
     @staticmethod
     def _bucket_range(group: ParamGroup, layers):
@@ -810,31 +736,13 @@ class HiFiGANTrainer:
     def training_step(self, mel_bct: torch.Tensor, audio_bct: torch.Tensor, sync: bool = True):
         """mel [B, n_mels, T/hop], audio [B, 1, T] on the device.  Returns the scalar losses: python floats (ONE device-to-host
         read at the end of the step), or with ``sync=False`` a device tensor in LOSS_KEYS order (no host synchronisation)."""
-        prev, prev_side = ops.CONV_BACKEND["operands"], ops.SIDE_WGRAD["on"]
-        ops.CONV_BACKEND["operands"] = self.precision
-        ops.SIDE_WGRAD["on"] = self.side_wgrad and self.device.type == "cuda"
-        ops.side_reset()  # nothing an aborted step left collected reaches this one (ops.side_reset)
-        try:
+        with step_scope(self.device, operands=self.precision, side_wgrad=self.side_wgrad and self.device.type == "cuda"):
             if self.device.type != "cuda":
                 buf = self._eager_step(mel_bct, audio_bct)
             else:
                 # the step always runs on the trainer's own stream -- eagerly, while capturing and when replaying -- so that the
                 # per-stream scratch buffers grown by the eager warm-up are the ones the captured graph uses
-                caller = torch.cuda.current_stream(self.device)
-                self._stream.wait_stream(caller)
-                with torch.cuda.stream(self._stream):
-                    if self.use_graph and self._graph_failed is None:
-                        buf = self._graph_step(mel_bct, audio_bct)
-                    else:
-                        buf = self._eager_step(mel_bct, audio_bct)
-                caller.wait_stream(self._stream)
-        except BaseException:
-            ops.side_reset(abort=True)
-            raise
-        finally:
-            ops.CONV_BACKEND["operands"] = prev
-            ops.SIDE_WGRAD["on"] = prev_side
-        ops.side_check_drained()
+                buf, _ = on_own_stream(self._stream, self.device, self._graph_step if self.use_graph else self._eager_step, mel_bct, audio_bct)
         self.global_step += 1
         if not sync:
             return buf
@@ -1143,87 +1051,54 @@ class HiFiGANTrainer:
         self.g_params.optimizer_step(**self._opt_kw())
 
     # ---- HIP-graph execution of the step ----------------------------------------------------------------------------
-    GRAPH_WARMUP_STEPS = 2
-
     def _graph_step(self, mel_bct, audio_bct):
-        """Fixed-shape steps (vocoder segments are: batch x vocoder_segment_size) run as HIP graph replays: the first steps at a
-        shape run eagerly (workspaces grow, kernel attributes are set), the next one is captured -- on one GPU as ONE graph,
-        under data parallelism as three (up to the discriminators' gradients | their update and the generator's backward | the
-        generator's update) with the two gradient all-reduces issued between them -- and every later step replays.
-        Any failure while capturing falls back to eager execution for good (``_graph_failed`` holds the reason)."""
+        """Fixed-shape steps (vocoder segments are: batch x vocoder_segment_size) run as HIP graph replays (train/step.py:
+        CapturedStep) -- on one GPU as ONE graph, under data parallelism as three (up to the discriminators' gradients | their
+        update and the generator's backward | the generator's update) with the two gradient all-reduces issued between them."""
         warm = self.global_step < self.generator_warmup_steps
         key = (tuple(mel_bct.shape), tuple(audio_bct.shape), self.precision, warm, self.keep_grads)
-        entry = self._graphs.get(key)
-        if entry is None:
-            n = self._graph_warm.get(key, 0)
-            if n < self.GRAPH_WARMUP_STEPS or self.keep_grads:
-                self._graph_warm[key] = n + 1
-                return self._eager_step(mel_bct, audio_bct)
-            steps = (self.g_params.step, self.d_params.step)
-            failure = None
-            try:
-                if getattr(self, "_force_capture_failure", False):  # (tests/test_gpu_ddp.py: one rank eager beside one that replays)
-                    raise RuntimeError("capture failure forced by a test")
-                entry = self._capture(key, mel_bct, audio_bct, warm)
-            except Exception as e:  # noqa: BLE001 -- whatever the runtime objected to: the eager path is always available
-                failure = f"{type(e).__name__}: {e}"
-            # data parallel: the eager step runs the captured step's schedule (`_eager_data_parallel_step`: same stretches, same
-            # buckets, same collective sequence), so a rank whose capture failed goes on eagerly beside ranks that replay --
-            # no agreement between the ranks is needed (round 4 all-reduced a flag here, a collective only capturing ranks issued)
-            if failure is not None:
-                self._graph_failed = failure
-                torch.cuda.synchronize(self.device)
-                ops.side_reset()  # the aborted capture's collected weight-gradient launches and events must not reach the eager step
-                # nothing of the aborted capture has run, but its host-side bookkeeping has: the spectral-norm layers hold
-                # prepared (weight, sigma, u, v) tuples that live in the dead graph's pool and were never computed, and the
-                # optimisers' host counters were bumped.  Put both back before the eager step.
-                for layer in self._sn_layers():
-                    layer._ready.clear()
-                    layer._held.clear()
-                    layer._calls.clear()
-                self.g_params._step, self.d_params._step = steps
-                return self._eager_step(mel_bct, audio_bct)
-            self._graphs[key] = entry
+        entry = self._graph_entry(key, lambda cap: self._capture(cap, mel_bct, audio_bct, warm), keep_eager=self.keep_grads)
+        if entry is EAGER:
+            return self._eager_step(mel_bct, audio_bct)
         ops.copy(mel_bct.to(torch.float32).contiguous(), out=entry["mel"])
         ops.copy(audio_bct.to(torch.float32).contiguous(), out=entry["audio"])
-        for g, after in zip(entry["graphs"], entry["after"]):
-            g.replay()
-            if after is not None:
-                after()  # the gradient exchange at this bucket boundary: RCCL calls sit between the captured stretches
-        # the host-side step counters follow the device-side ones the graph increments
-        if not warm:
-            self.d_params._step += 1
-        self.g_params._step += 1
+        self._replay(entry)
         return self._loss_buf
 
-    def _allreduce_whole(self, group: ParamGroup):
-        if self.pg is not None:
-            allreduce_mean_(group.grad, self.pg if self.pg is not True else None, lambda t, sc: ops.elementwise(ops.EW_SCALE, t, out=t, p0=sc))
+    def _host_counters(self):
+        return self.g_params._step, self.d_params._step
+
+    def _set_host_counters(self, state):
+        self.g_params._step, self.d_params._step = state
+
+    def _count_replay(self, entry):
+        if not entry["warm"]:
+            self.d_params._step += 1
+        self.g_params._step += 1
+
+    def _capture_failed(self):
+        # nothing of the aborted capture has run, but its host-side bookkeeping has: the spectral-norm layers hold prepared
+        # (weight, sigma, u, v) tuples that live in the dead graph's pool and were never computed
+        for layer in self._sn_layers():
+            layer._ready.clear()
+            layer._held.clear()
+            layer._calls.clear()
 
     # smallest generator-side bucket (floats) worth a stretch boundary of its own: smaller ones ride with the next
     MIN_G_BUCKET = 1 << 20
 
-    def _capture(self, key, mel_bct, audio_bct, warm):
+    def _capture(self, cap, mel_bct, audio_bct, warm):
         """One GPU: the whole step is ONE graph.  Data parallel: the step is captured in stretches that end where a gradient
         bucket becomes final -- [generator forward + period discriminators] [scale discriminators] [discriminator update +
         generator-step discriminator pass + generator backward down to the first large bucket] ... [generator update] -- and
         between two stretches that bucket's all-reduce is launched on a side stream (RCCL calls are not captured), so it runs
         UNDER the next stretch; only an optimiser waits for its buckets (the reference: DDP buckets firing inside
         backward, base_cli/helpers.py:252-270)."""
+        if getattr(self, "_force_capture_failure", False):  # (tests/test_gpu_ddp.py: one rank eager beside one that replays)
+            raise RuntimeError("capture failure forced by a test")
         mel_s = mel_bct.to(torch.float32).contiguous().clone()
         audio_s = audio_bct.to(torch.float32).contiguous().clone()
-        steps = (self.g_params.step, self.d_params.step)
-        torch.cuda.synchronize(self.device)
-        pool = torch.cuda.graph_pool_handle()
-        graphs, after = [], []
         ctx = {}
-
-        def cap(fn, then=None):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, stream=self._stream, capture_error_mode="thread_local"):
-                fn()
-            graphs.append(g)
-            after.append(then)
 
         def whole():
             ctx.update(self._phase_generator_forward(mel_s, audio_s, d_step=not warm))
@@ -1240,9 +1115,7 @@ class HiFiGANTrainer:
                 self._capture_data_parallel(cap, ctx, mel_s, audio_s, warm)
         finally:
             ctx.clear()
-            # capturing does not execute: the host-side counters the phases bumped are put back (replay bumps them again)
-            self.g_params._step, self.d_params._step = steps
-        return dict(graphs=graphs, after=after, mel=mel_s, audio=audio_s)
+        return dict(mel=mel_s, audio=audio_s, warm=warm)
 
     def _capture_data_parallel(self, cap_raw, ctx, mel_s, audio_s, warm):
         """The data-parallel schedule with every stretch captured and every exchange stored for the replay loop."""
@@ -1272,9 +1145,8 @@ class HiFiGANTrainer:
     def _data_parallel_schedule(self, run, emit, ctx, mel_s, audio_s, warm):
         """``run(fn)``: execute (or capture) one stretch; ``emit(then)``: the exchange that follows it (called at once, or stored)."""
         if getattr(self, "_dp_reducers", None) is None:
-            scale = lambda t, sc: ops.elementwise(ops.EW_SCALE, t, out=t, p0=sc)  # noqa: E731
             pg = self.pg if self.pg is not True else None
-            self._dp_reducers = (BucketReducer(self.d_params.grad, pg, scale), BucketReducer(self.g_params.grad, pg, scale))  # (their side streams live across steps)
+            self._dp_reducers = (BucketReducer(self.d_params.grad, pg), BucketReducer(self.g_params.grad, pg))  # (their side streams live across steps)
         d_red, g_red = self._dp_reducers
 
         def first():

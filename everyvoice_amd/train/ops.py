@@ -290,7 +290,7 @@ def side_check_drained():
         raise RuntimeError(f"side_wgrad: {left} weight-gradient launches were never issued (a backward chain ended without wgrad_join on its stream)")
 
 
-def side_reset(abort: bool = False):
+def side_reset(abort: bool = False, device=None):
     """Forget every weight-gradient launch that was collected but not issued, and every pending event.  A step that aborts half way
     -- a graph capture that fails and falls back to the eager body, an out-of-memory error a caller retries -- leaves closures in
     ``queue`` whose tensors were never written (they live in the aborted capture's pool) and a ``pending`` event recorded inside that
@@ -298,10 +298,11 @@ def side_reset(abort: bool = False):
     weight-gradient buffers (silent gradient corruption; ``side_check_drained`` does not see it because the flush empties
     the queue).  Called at the start of every step, and where a step aborts -- there with ``abort=True``: weight-gradient kernels
     already ISSUED on a sibling stream may still be reading the tensors ``keep`` holds (allocated on the chain's stream); the device is
-    drained before they are let go, so the allocator cannot hand their blocks to the caller's retry under running kernels."""
-    if abort and _SIDE and torch.cuda.is_available():
+    drained before they are let go, so the allocator cannot hand their blocks to the caller's retry under running kernels.
+    ``device``: the one the aborted step ran on (None: the current one; a step on the CPU issued nothing)."""
+    if abort and _SIDE and torch.cuda.is_available() and (device is None or torch.device(device).type == "cuda"):
         try:
-            torch.cuda.synchronize()
+            torch.cuda.synchronize(device)
         except RuntimeError:  # (a capture that is still being torn down: nothing was issued)
             pass
     for st in _SIDE.values():
@@ -1391,18 +1392,35 @@ def align_attention_bwd(q, k, soft, logprob, prior, hard, dlogprob, text_lens32,
 
 
 # ---- Global Style Token module (csrc/gst.hip): fp32 in both precision modes -------------------------------------------------------
-class exact_f32:
+UNSET = object()  # "not given" where None is a value (SEED_BASE[0] is None outside a step)
+
+
+class mode:
+    """``with mode(operands="bf16", side_wgrad=True, seed_base=t, ln_defer=True):`` the operator switches that are given are set
+    (CONV_BACKEND["operands"], SIDE_WGRAD["on"], SEED_BASE[0], LN_DEFER["on"]) and exactly their previous values put back on the way
+    out, also when the body raises; the others are not touched.  Nests.  (A class, not a generator: a few per host-bound step.)"""
+
+    def __init__(self, operands=None, side_wgrad=None, seed_base=UNSET, ln_defer=None):
+        given = [(CONV_BACKEND, "operands", operands), (SIDE_WGRAD, "on", side_wgrad), (LN_DEFER, "on", ln_defer)]
+        self.new = [g for g in given if g[2] is not None] + ([(SEED_BASE, 0, seed_base)] if seed_base is not UNSET else [])
+
+    def __enter__(self):
+        self.old = [(box, key, box[key]) for box, key, _ in self.new]
+        for box, key, v in self.new:
+            box[key] = v
+        return self
+
+    def __exit__(self, *exc):
+        for box, key, v in self.old:
+            box[key] = v
+        return False
+
+
+def exact_f32():
     """``with exact_f32():`` the dense operators inside run on exact fp32 operands whatever the model's precision mode (the style
     module is tiny and recurrent: the wrong place to save bits) and issue their weight gradients in place: a launch collected for the
     sibling stream (``side_wgrad``) would run later, under whatever mode holds then."""
-
-    def __enter__(self):
-        self.prev = CONV_BACKEND["operands"], SIDE_WGRAD["on"]
-        CONV_BACKEND["operands"], SIDE_WGRAD["on"] = "f32", False
-
-    def __exit__(self, *exc):
-        CONV_BACKEND["operands"], SIDE_WGRAD["on"] = self.prev
-        return False
+    return mode(operands="f32", side_wgrad=False)
 
 
 def gst_conv_out(n: int) -> int:

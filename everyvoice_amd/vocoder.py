@@ -223,9 +223,7 @@ class Generator(nn.Module):
         m = self.config.model
         slope = ACTIVATION_SLOPES[m.activation_function]
         B, n_mels, T = mel.shape
-        prev = ops.CONV_BACKEND["operands"]
-        ops.CONV_BACKEND["operands"] = "f32"
-        try:
+        with ops.mode(operands="f32"):
             x = torch.empty(n_mels, B, T, device=mel.device, dtype=torch.float32)
             _lib.check(_lib.load().evmi_transpose_bct_cbt_f32(mel.data_ptr(), x.data_ptr(), B, n_mels, T, _lib.current_stream_ptr(mel.device)),
                        "evmi_transpose_bct_cbt_f32")
@@ -259,8 +257,6 @@ class Generator(nn.Module):
                 x = ops.elementwise(ops.EW_MUL, raw, consts.inv_envelope(B, x.shape[2]), out=raw)
             else:
                 x = ops.tanh(ops.conv1d_fwd(x, self.conv_post.weight, self.conv_post.bias, 1, 3, 1, 1))
-        finally:
-            ops.CONV_BACKEND["operands"] = prev
         return x.view(B, 1, -1)  # [1, B, T'] and [B, 1, T'] are the same bytes
 
     @torch.no_grad()
