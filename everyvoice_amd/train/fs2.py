@@ -193,7 +193,7 @@ def _row(t):
     """[C, B, T] -> [C, 1, B * T] (a view): a position-wise layer sees all its columns as ONE item, the form in which the packed bf16
     kernels share one packed copy of every operand between forward, input gradient and weight gradient for any B * T
     (csrc/conv_pk_common.h: pk_shared_items) -- with B items that needs B * T to be a multiple of 64."""
-    return t if (t.shape[1] == 1 or not ops._packed()) else t.reshape(t.shape[0], 1, -1)
+    return t if (t.shape[1] == 1 or not ops.packed_bf16()) else t.reshape(t.shape[0], 1, -1)
 
 
 def _held_tensors(fns, depth: int = 4) -> list:
@@ -232,10 +232,16 @@ def _held_tensors(fns, depth: int = 4) -> list:
 
 def _items(B, T):
     """(items, columns per item) as `_row` hands a [C, B, T] tensor to a position-wise layer."""
-    return (1, B * T) if ops._packed() else (B, T)
+    return (1, B * T) if ops.packed_bf16() else (B, T)
 
 
 _EVAL = [False]  # FastSpeech2Trainer.evaluate: dropout off, BatchNorm on its running statistics (and not updating them)
+
+
+def _record(tape: Tape, y: Var, bwd) -> Var:
+    """y's backward is ``bwd(y.grad)`` -- nothing where y never received a gradient.  Returns y."""
+    tape.record(lambda: y.grad is not None and bwd(y.grad))
+    return y
 
 
 def dense(tape: Tape, x: Var, layer, act=ops.ACT_NONE) -> Var:
@@ -247,10 +253,7 @@ def dense(tape: Tape, x: Var, layer, act=ops.ACT_NONE) -> Var:
     row = (lambda t: _row(t)) if layer.k == 1 else (lambda t: t)  # (pointwise: one item)
     y = Var(ops.conv1d_fwd(row(x.data), w, layer.bias_data(), 1, layer.pad, 1, 1, act=act, keep=packed).view(-1, shape[1], shape[2] + 2 * layer.pad - layer.k + 1))
 
-    def bwd():
-        if y.grad is None:
-            return
-        dy = y.grad
+    def bwd(dy):
         if act == ops.ACT_RELU:
             dy = ops.elementwise(ops.EW_RELU_BWD, dy, y.data)
         elif act == ops.ACT_TANH:
@@ -261,8 +264,7 @@ def dense(tape: Tape, x: Var, layer, act=ops.ACT_NONE) -> Var:
         if dx is not None:
             x.accumulate(dx.view(shape))
 
-    tape.record(bwd)
-    return y
+    return _record(tape, y, bwd)
 
 
 def silu(tape: Tape, x: Var) -> Var:
@@ -359,16 +361,13 @@ def dense_residual_dropout(tape: Tape, a: Var, h: Var, layer, p: float, seed: in
     packed = {}
     y = Var(ops.conv1d_fwd_resdrop(_row(h.data), w, layer.bias_data(), _row(a.data), p, seed, sb, packed).view(a.data.shape))
 
-    def bwd():
-        if y.grad is None:
-            return
-        dh = ops.conv1d_bwd_dropout_dy(_row(h.data), w, _row(y.grad), p, seed, sb, dw_sink, layer.db_sink(), packed)
+    def bwd(dy):
+        dh = ops.conv1d_bwd_dropout_dy(_row(h.data), w, _row(dy), p, seed, sb, dw_sink, layer.db_sink(), packed)
         packed.clear()
         h.accumulate(dh.view(h.data.shape))
-        a.accumulate(y.grad)
+        a.accumulate(dy)
 
-    tape.record(bwd)
-    return y
+    return _record(tape, y, bwd)
 
 
 def silu_dropout(tape: Tape, x: Var, p: float, seed: int) -> Var:
@@ -391,17 +390,14 @@ def ln_dense(tape: Tape, x: Var, ln: Affine, layer) -> Var:
     packed = {}
     y = Var(ops.layernorm_dense_fwd(_row(x.data), ln.gamma(), ln.beta(), w, layer.bias_data(), packed).view(-1, B, T))
 
-    def bwd():
-        if y.grad is None:
-            return
+    def bwd(dy):
         # (x.data stands in for the normalised tensor, which was never stored: only its shape is read -- the weight gradient takes the packed copy)
-        dh, _, _ = ops.conv1d_bwd(_row(x.data), w, _row(y.grad), 1, 0, 1, 1, need_dx=True, dw_out=dw_sink, db_out=layer.db_sink(), accumulate=True, packed=packed,
+        dh, _, _ = ops.conv1d_bwd(_row(x.data), w, _row(dy), 1, 0, 1, 1, need_dx=True, dw_out=dw_sink, db_out=layer.db_sink(), accumulate=True, packed=packed,
                                    x_standin=True)
         packed.clear()
         _ln_bwd_into(x, ln, dh.view(x.data.shape))
 
-    tape.record(bwd)
-    return y
+    return _record(tape, y, bwd)
 
 
 def ffn_core(tape: Tape, x: Var, ln: Affine, l1, l2, p: float, seed: int, res: Var | None = None, seed_out: int = 0, sb: float = 1.0) -> Var:
@@ -413,30 +409,42 @@ def ffn_core(tape: Tape, x: Var, ln: Affine, l1, l2, p: float, seed: int, res: V
     ``res``: the block's residual input -- the operator then returns res + sb * dropout(that, p) with the add and the mask (seed_out) in
     the second layer's epilogue and sb * dropout(dy) formed while dy is packed (dense_residual_dropout's fusion)."""
     C, B, T = x.data.shape
-    N = B * T  # (position-wise layers: all columns as one item, _row)
     if p <= 0.0 or _EVAL[0] or not ops.ffn_fused_supported(*_items(B, T), l1.cout, l2.cout):
         h = dense(tape, silu_dropout(tape, ln_dense(tape, x, ln, l1), p, seed), l2)
         return h if res is None else residual_dropout(tape, res, h, p, seed_out, sb)
+    if res is not None and ops.ffn_packed_supported(*_items(B, T), C, l1.cout, l2.cout):
+        return _ffn_packed_chain(tape, x, ln, l1, l2, p, seed, res, seed_out, sb)
+    return _ffn_fused_middle(tape, x, ln, l1, l2, p, seed, res, seed_out, sb)
+
+
+def _ffn_packed_chain(tape: Tape, x: Var, ln: Affine, l1, l2, p, seed, res: Var, seed_out, sb) -> Var:
+    """ffn_core as a packed chain: the c_mid-channel tensors (pre-activation, activated + masked, and its gradient) exist as packed bf16
+    only, written by the producing layers' epilogues (ops.ffn_packed_fwd)."""
+    _, B, T = x.data.shape
     w1, dw1 = l1.effective(True)
     w2, dw2 = l2.effective(True)
     xr = _row(x.data)
-    if res is not None and ops.ffn_packed_supported(*_items(B, T), C, l1.cout, l2.cout):
-        # the whole block as a packed chain: the c_mid-channel tensors (pre-activation, activated + masked, and its gradient) exist as
-        # packed bf16 only, written by the producing layers' epilogues (ops.ffn_packed_fwd)
-        keep = {}
-        yp = Var(ops.ffn_packed_fwd(xr, ln.gamma(), ln.beta(), w1, l1.bias_data(), w2, l2.bias_data(), _row(res.data), p, seed, seed_out, sb, keep).view(-1, B, T))
-        _ACTIVATION_ELEMS[0] += l1.cout * N  # (the pre-activation: the tensor the separate operators count as dense1's output)
+    keep = {}
+    y = Var(ops.ffn_packed_fwd(xr, ln.gamma(), ln.beta(), w1, l1.bias_data(), w2, l2.bias_data(), _row(res.data), p, seed, seed_out, sb, keep).view(-1, B, T))
+    _ACTIVATION_ELEMS[0] += l1.cout * B * T  # (the pre-activation: the tensor the separate operators count as dense1's output)
 
-        def bwd_packed():
-            if yp.grad is None:
-                return
-            dh = ops.ffn_packed_bwd(xr, w1, w2, _row(yp.grad), p, seed, seed_out, sb, dw1, l1.db_sink(), dw2, l2.db_sink(), keep)
-            keep.clear()
-            res.accumulate(yp.grad)  # (first: LayerNorm's backward then adds into it -- res is x in the Conformer's blocks)
-            _ln_bwd_into(x, ln, dh.view(x.data.shape))
+    def bwd(dy):
+        dh = ops.ffn_packed_bwd(xr, w1, w2, _row(dy), p, seed, seed_out, sb, dw1, l1.db_sink(), dw2, l2.db_sink(), keep)
+        keep.clear()
+        res.accumulate(dy)  # (first: LayerNorm's backward then adds into it -- res is x in the Conformer's blocks)
+        _ln_bwd_into(x, ln, dh.view(x.data.shape))
 
-        tape.record(bwd_packed)
-        return yp
+    return _record(tape, y, bwd)
+
+
+def _ffn_fused_middle(tape: Tape, x: Var, ln: Affine, l1, l2, p, seed, res: Var | None, seed_out, sb) -> Var:
+    """ffn_core with the activation and the mask applied while the second layer's input (backward: the first layer's output gradient) is
+    packed; LayerNorm in the first layer's pack and the residual + dropout in the second layer's epilogue where those fusions take the
+    shape, as operators of their own where not."""
+    C, B, T = x.data.shape
+    w1, dw1 = l1.effective(True)
+    w2, dw2 = l2.effective(True)
+    xr = _row(x.data)
     packed1, packed2 = {}, {}
     ln_fused = ops.ln_dense_fused_supported(*_items(B, T), C, l1.cout)
     if ln_fused:
@@ -452,27 +460,25 @@ def ffn_core(tape: Tape, x: Var, ln: Affine, l1, l2, p: float, seed: int, res: V
         y = Var(ops.conv1d_fwd_silu_dropout(a, w2, l2.bias_data(), p, seed, packed2).view(-1, B, T))
     _ACTIVATION_ELEMS[0] += a.numel()  # (the pre-activation: the tensor the separate operators count as dense1's output)
 
-    def bwd():
-        if y.grad is None:
-            return
+    def bwd(dy):
         # second layer: its packed input is the forward's (a stands in for the fp32 tensor that was never stored: only its shape is read)
         if fuse_out:
-            ds = ops.conv1d_bwd_dropout_dy(a, w2, _row(y.grad), p, seed_out, sb, dw2, l2.db_sink(), packed2, x_standin=True)
+            ds = ops.conv1d_bwd_dropout_dy(a, w2, _row(dy), p, seed_out, sb, dw2, l2.db_sink(), packed2, x_standin=True)
         else:
-            ds, _, _ = ops.conv1d_bwd(a, w2, _row(y.grad), 1, 0, 1, 1, need_dx=True, dw_out=dw2, db_out=l2.db_sink(), accumulate=True, packed=packed2,
+            ds, _, _ = ops.conv1d_bwd(a, w2, _row(dy), 1, 0, 1, 1, need_dx=True, dw_out=dw2, db_out=l2.db_sink(), accumulate=True, packed=packed2,
                                        x_standin=True)
         packed2.clear()
         # first layer: x.data / h.data only lend their shape (the weight gradient reads the packed copy)
         dh = ops.conv1d_bwd_silu_dropout_dy(xr if ln_fused else _row(h.data), w1, ds, a, p, seed, dw1, l1.db_sink(), packed1).view(x.data.shape)
         packed1.clear()
         if fuse_out:
-            res.accumulate(y.grad)
+            res.accumulate(dy)
         if ln_fused:
             _ln_bwd_into(x, ln, dh)
         else:
             h.accumulate(dh)
 
-    tape.record(bwd)
+    _record(tape, y, bwd)
     return y if (res is None or fuse_out) else residual_dropout(tape, res, y, p, seed_out, sb)
 
 

@@ -235,7 +235,7 @@ class GeneratorT:
 def _chain_for(disc, period: int, x: torch.Tensor):
     """The flat packed bf16 chain of a discriminator (train/disc_chain.py) when it applies: precision "bf16" on the packed kernels,
     on a GPU; ``EVMI_DISC_CHAIN=0`` keeps the op-by-op channel-major path (A/B switch; the tests run both)."""
-    if not (x.is_cuda and ops._packed() and _DISC_CHAIN):
+    if not (x.is_cuda and ops.packed_bf16() and _DISC_CHAIN):
         return None
     ch = getattr(disc, "_chain", None)
     if ch is None:

@@ -7,13 +7,80 @@ Forward functions return what their backward needs; nothing here uses torch auto
 
 from __future__ import annotations
 
+import ctypes
+import os
+
 import torch
 
 from .. import _lib
 
-# elementwise op codes (csrc/train_ops.hip)
+# elementwise op codes (csrc/train_ops.hip, csrc/fs2_train_ops.hip) and the convolutions' epilogue activations
 EW_LRELU, EW_LRELU_BWD, EW_TANH, EW_TANH_BWD, EW_AXPBY, EW_SCALE, EW_MUL = 0, 1, 2, 3, 4, 5, 6
 EW_SIGN_DIFF, EW_SQ_GRAD, EW_LOG_CLAMP, EW_DIV_MASK, EW_MAG, EW_MUL_DIV = 7, 8, 9, 10, 11, 12
+EW_SILU, EW_RELU, EW_GLU, EW_SILU_BWD, EW_RELU_BWD, EW_CLIP_SCALE = 13, 14, 15, 18, 19, 20
+EW_DIV_SCALAR, EW_STFT_GRAD_DEV, EW_FILL, EW_SCALE_DIV_SCALAR = 21, 22, 23, 24
+ACT_NONE, ACT_LRELU, ACT_SILU, ACT_RELU, ACT_TANH = 0, 1, 2, 3, 4
+_ACT_EW = {ACT_LRELU: EW_LRELU, ACT_SILU: EW_SILU, ACT_RELU: EW_RELU, ACT_TANH: EW_TANH}  # the epilogue activations as a pass of their own
+
+# ---- switches ------------------------------------------------------------------------------------------------------------
+# "mfma": the hand-written fp32 matrix-core convolution kernels; "gemm": unfold + the plain fp32 GEMM (A/B and reference variant).
+# wgrad "auto": implicit GEMM for grouped layers (2-5x over unfold + per-group GEMMs), unfold + ONE library GEMM for dense
+# ones in fp32 mode (one long-K product, split over K).
+# "operands": "f32" = exact fp32 fmaf chains on the fp32-input matrix cores; "bf16" = the same kernels round both operands to
+# bf16 on their way into v_mfma_f32_32x32x16_bf16 (fp32 accumulation, fp32 tensors in HBM, fp32 master weights).
+# "packed": bf16 operands go through the packed-input kernel (conv_cbt_bf16_pk.hip) where it takes the shape; False = always the
+# in-LDS rounding variant of the fp32 kernels (A/B switch).
+CONV_BACKEND = {"fwd": "mfma", "dgrad": "mfma", "wgrad": "mfma", "operands": "f32", "packed": True}
+SIDE_WGRAD = {"on": False}  # weight gradients on a sibling stream ("weight gradients beside the input-gradient chain" below)
+SIDE_GROUP = [int(os.environ.get("EVMI_SIDE_GROUP", "8"))]  # launches per fork of that stream (<= 1: a fork per layer)
+LN_DEFER = {"on": False}  # LayerNorm parameter gradients reduced once per backward chain (layernorm_flush)
+# A device-resident base added to every dropout seed ([1] int64 tensor, or None): the FastSpeech2 trainer stores
+# (seed, step, rank) << 16 there before each step and passes the draw's index as `seed`, so a step captured into a HIP graph
+# draws fresh masks on every replay (include/evmi.h: evmi_dropout_f32).
+SEED_BASE = [None]
+# A/B switches (tools/fs2_train_bench.py): the feed-forward blocks as packed chains (ffn_packed_fwd); the residual add and the dropout
+# in a layer's epilogue (conv1d_fwd_resdrop)
+FFN_PACKED = [os.environ.get("EVMI_FS2_FFN_PACKED", "1") != "0"]
+RESDROP_FUSION = [os.environ.get("EVMI_FS2_RESDROP", "1") != "0"]
+UNSET = object()  # "not given" where None is a value (SEED_BASE[0] is None outside a step)
+
+
+class mode:
+    """``with mode(operands="bf16", side_wgrad=True, seed_base=t, ln_defer=True):`` the operator switches that are given are set
+    (CONV_BACKEND["operands"], SIDE_WGRAD["on"], SEED_BASE[0], LN_DEFER["on"]) and exactly their previous values put back on the way
+    out, also when the body raises; the others are not touched.  Nests.  (A class, not a generator: a few per host-bound step.)"""
+
+    def __init__(self, operands=None, side_wgrad=None, seed_base=UNSET, ln_defer=None):
+        given = [(CONV_BACKEND, "operands", operands), (SIDE_WGRAD, "on", side_wgrad), (LN_DEFER, "on", ln_defer)]
+        self.new = [g for g in given if g[2] is not None] + ([(SEED_BASE, 0, seed_base)] if seed_base is not UNSET else [])
+
+    def __enter__(self):
+        self.old = [(box, key, box[key]) for box, key, _ in self.new]
+        for box, key, v in self.new:
+            box[key] = v
+        return self
+
+    def __exit__(self, *exc):
+        for box, key, v in self.old:
+            box[key] = v
+        return False
+
+
+def exact_f32():
+    """``with exact_f32():`` the dense operators inside run on exact fp32 operands whatever the model's precision mode (the style
+    module is tiny and recurrent: the wrong place to save bits) and issue their weight gradients in place: a launch collected for the
+    sibling stream (``side_wgrad``) would run later, under whatever mode holds then."""
+    return mode(operands="f32", side_wgrad=False)
+
+
+def packed_bf16() -> bool:
+    """bf16 operands on the packed kernels."""
+    return CONV_BACKEND["operands"] == "bf16" and CONV_BACKEND["packed"]
+
+
+def packed_serves_all() -> bool:
+    """The packed kernels serve forward, input gradient AND weight gradient (what every fused form below needs)."""
+    return packed_bf16() and CONV_BACKEND["fwd"] == "mfma" and CONV_BACKEND["dgrad"] == "mfma" and CONV_BACKEND["wgrad"] != "gemm"
 
 
 def _s(t: torch.Tensor) -> int:
@@ -117,9 +184,6 @@ def elementwise(op, a, b=None, c=None, out=None, p0=0.0, p1=0.0):
     return out
 
 
-EW_DIV_SCALAR, EW_STFT_GRAD_DEV, EW_FILL, EW_SCALE_DIV_SCALAR = 21, 22, 23, 24
-
-
 def fill_(x, value=0.0):
     """x[:] = value with a library kernel (x contiguous)."""
     return elementwise(EW_FILL, x, out=x, p0=value)
@@ -150,7 +214,6 @@ def scalar_reduce(mode, a, b, out, scale=1.0, p=0.0, accumulate=False):
 # sibling stream of the current one -- forked behind the tensors they read, joined by `wgrad_join` before anything consumes the
 # parameter gradients (every Tape.backward ends with it) -- so the chain does not wait for them.  The tensors a side launch reads
 # stay referenced until the join (see the allocator note in train/layers.py: SNConv.prepare).
-SIDE_WGRAD = {"on": False}
 _SIDE: dict = {}
 _SIDE_STREAMS: set = set()
 
@@ -183,9 +246,6 @@ def _side_state(device):
 # side chain after the main chain: 6.5 ms for two chains of 2.8 ms -- the FastSpeech2 step's weight gradients all ran behind its
 # backward, profiles/r04x_fs2_queues_before.txt), groups of 8 / 16 in 3.2 ms, eager 7.8 -> 3.9 ms (tools/microbench/graph_side_chain.py).
 # <= 1: the per-layer fork.
-import os as _os
-
-SIDE_GROUP = [int(_os.environ.get("EVMI_SIDE_GROUP", "8"))]
 
 
 def _side_flush(st, cur):
@@ -332,9 +392,6 @@ def wgrad_join(device=None):
 
 
 # ---- convolutions ---------------------------------------------------------------------------------------
-ACT_NONE, ACT_LRELU, ACT_SILU, ACT_RELU, ACT_TANH = 0, 1, 2, 3, 4
-
-
 def pk_pitch(B, t) -> int:
     """Units per channel-octet row of a shared packed operand (csrc/conv_pk_common.h: pk_shared_pitch): tight items, or -- one item -- its
     length rounded up to the weight gradient's K step (the units behind the last column are zero)."""
@@ -344,7 +401,12 @@ def pk_pitch(B, t) -> int:
 def shares_packed(B, t, k, stride, pad, dil, groups) -> bool:
     """True for the layers whose packed bf16 operands serve forward, input gradient AND weight gradient (pointwise, stride 1, B * t a
     multiple of the weight gradient's K step)."""
-    return bool(_packed() and _lib.load().evmi_conv1d_bf16pk_shares_packed(B, t, k, stride, pad, dil, groups))
+    return bool(packed_bf16() and _lib.load().evmi_conv1d_bf16pk_shares_packed(B, t, k, stride, pad, dil, groups))
+
+
+def _dx_buffer(cin, B, t_in, k, stride, device):
+    """Where an input-gradient kernel writes dx: zero-filled where k < stride (columns no tap reaches are not written)."""
+    return zeros(cin, B, t_in, device=device) if k < stride else torch.empty(cin, B, t_in, device=device, dtype=torch.float32)
 
 
 def conv1d_mfma(x, w, bias, stride=1, pad=0, dil=1, groups=1, out=None, n_out=None, out_stride=1, out_offset=0,
@@ -358,9 +420,9 @@ def conv1d_mfma(x, w, bias, stride=1, pad=0, dil=1, groups=1, out=None, n_out=No
     if out is None:
         out = torch.empty(cout, B, t_conv, device=x.device, dtype=torch.float32)
     lib = _lib.load()
-    _count_conv(B, t_conv if n_out is None else n_out, cout, cin_g, k)
-    if CONV_BACKEND["operands"] == "bf16" and CONV_BACKEND["packed"]:
-        n_eff = t_conv if n_out is None else n_out
+    n_eff = t_conv if n_out is None else n_out
+    _count_conv(B, n_eff, cout, cin_g, k)
+    if packed_bf16():
         pk_elems = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cin, t_in, cout, n_eff, k, stride, pad, dil, groups)
         if pk_elems > 0:  # packed bf16 copy of x + A fragments (conv_cbt_bf16_pk.hip)
             if keep is not None and n_out is None and shares_packed(B, t_in, k, stride, pad, dil, groups):
@@ -371,29 +433,24 @@ def conv1d_mfma(x, w, bias, stride=1, pad=0, dil=1, groups=1, out=None, n_out=No
                                             cout, out.shape[2], n_eff, k, stride, pad, dil, groups, out_stride, out_offset,
                                             int(accumulate), act, float(act_param), _s(x)), "evmi_conv1d_cbt_bf16pk")
             return out
-    wf_elems = lib.evmi_conv1d_cbt_f32_ws_elems(B, cin, cout, t_conv if n_out is None else n_out, k, groups)
+    wf_elems = lib.evmi_conv1d_cbt_f32_ws_elems(B, cin, cout, n_eff, k, groups)
     wf = WS.get("wfrag", wf_elems, x.device)
     fn = lib.evmi_conv1d_cbt_bf16 if CONV_BACKEND["operands"] == "bf16" else lib.evmi_conv1d_cbt_f32
     _chk(fn(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), out.data_ptr(), wf.data_ptr(), wf_elems, B, cin, t_in, cout,
-            out.shape[2], t_conv if n_out is None else n_out, k, stride, pad, dil, groups,
+            out.shape[2], n_eff, k, stride, pad, dil, groups,
             out_stride, out_offset, int(accumulate), act, float(act_param), _s(x)), "evmi_conv1d_cbt")
     return out
 
 
-
 # ---- fused forms (packed bf16 kernels take the neighbours of a convolution into their pack / epilogue; every other path runs
 # the same arithmetic as separate passes, so callers use ONE signature whatever kernel serves the shape) --------------------
-def _packed() -> bool:
-    return CONV_BACKEND["operands"] == "bf16" and CONV_BACKEND["packed"]
-
-
 def conv1d_fused_fwd(x, w, bias, stride=1, pad=0, dil=1, groups=1, act=ACT_NONE, act_param=0.0, pre_slope=1.0, residual=None):
     """y = act(conv(leaky_relu(x, pre_slope)) + bias) + residual."""
     cin, B, t_in = x.shape
     cout, _, k = w.shape
     t_out = conv_out_len(t_in, k, stride, pad, dil)
     lib = _lib.load()
-    if _packed() and CONV_BACKEND["fwd"] == "mfma":
+    if packed_bf16() and CONV_BACKEND["fwd"] == "mfma":
         pk = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cin, t_in, cout, t_out, k, stride, pad, dil, groups)
         if pk > 0:
             _count_conv(B, t_out, cout, cin // groups, k)
@@ -415,11 +472,11 @@ def conv1d_fused_dgrad(dy, w, t_in, stride=1, pad=0, dil=1, groups=1, dy_mask=No
     _, cin_g, k = w.shape
     cin = cin_g * groups
     lib = _lib.load()
-    if _packed() and CONV_BACKEND["dgrad"] == "mfma" and not ((dx_mask is not None or residual is not None) and k < stride):
+    if packed_bf16() and CONV_BACKEND["dgrad"] == "mfma" and not ((dx_mask is not None or residual is not None) and k < stride):
         pk = lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, cin, t_in, cout, t_out, k, stride, pad, dil, groups)
         if pk > 0:
             _count_conv(B, t_out, cout, cin_g, k)
-            dx = zeros(cin, B, t_in, device=dy.device) if k < stride else torch.empty(cin, B, t_in, device=dy.device, dtype=torch.float32)
+            dx = _dx_buffer(cin, B, t_in, k, stride, dy.device)
             ws = WS.get("pk", pk, dy.device)
             _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk_fused(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), ws.data_ptr(), pk, B, cin, t_in, cout, t_out, k, stride,
                                                         pad, dil, groups, 1.0, _lib.ptr(dy_mask), float(dy_mask_slope), _lib.ptr(dx_mask),
@@ -439,7 +496,7 @@ def conv1d_fused_wgrad(x, w_shape, dy, dw_out, stride=1, pad=0, dil=1, groups=1,
     cout, _, k = w_shape
     t_out = dy.shape[2]
     lib = _lib.load()
-    if _packed() and CONV_BACKEND["wgrad"] != "gemm":
+    if packed_bf16() and CONV_BACKEND["wgrad"] != "gemm":
         pk = lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, cin, t_in, cout, t_out, k, stride, pad, dil, groups)
         if pk > 0:
           _count_conv(B, t_out, cout, cin // groups, k)
@@ -472,7 +529,7 @@ def conv1d_bwd_data_mfma(dy, w, t_in, stride=1, pad=0, dil=1, groups=1, keep=Non
     _, cin_g, k = w.shape
     cin = cin_g * groups
     lib = _lib.load()
-    if CONV_BACKEND["operands"] == "bf16" and CONV_BACKEND["packed"]:
+    if packed_bf16():
         pk_elems = lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, cin, t_in, cout, t_out, k, stride, pad, dil, groups)
         if pk_elems > 0:
             _count_conv(B, t_out, cout, cin_g, k)
@@ -480,7 +537,7 @@ def conv1d_bwd_data_mfma(dy, w, t_in, stride=1, pad=0, dil=1, groups=1, keep=Non
                 ws = keep["dy_packed"] = torch.empty(pk_elems, device=dy.device, dtype=torch.float32)
             else:
                 ws = WS.get("pk", pk_elems, dy.device)
-            dx = zeros(cin, B, t_in, device=dy.device) if k < stride else torch.empty(cin, B, t_in, device=dy.device, dtype=torch.float32)
+            dx = _dx_buffer(cin, B, t_in, k, stride, dy.device)
             _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), ws.data_ptr(), pk_elems, B, cin, t_in, cout,
                                                   t_out, k, stride, pad, dil, groups, _s(dy)), "evmi_conv1d_dgrad_cbt_bf16pk")
             return dx
@@ -488,7 +545,7 @@ def conv1d_bwd_data_mfma(dy, w, t_in, stride=1, pad=0, dil=1, groups=1, keep=Non
     if ws_elems > 0:  # every phase in one launch, weight fragments straight from w
         _count_conv(B, t_out, cout, cin_g, k)
         ws = WS.get("wfrag", ws_elems, dy.device)
-        dx = zeros(cin, B, t_in, device=dy.device) if k < stride else torch.empty(cin, B, t_in, device=dy.device, dtype=torch.float32)
+        dx = _dx_buffer(cin, B, t_in, k, stride, dy.device)
         fn = lib.evmi_conv1d_dgrad_cbt_bf16 if CONV_BACKEND["operands"] == "bf16" else lib.evmi_conv1d_dgrad_cbt_f32
         _chk(fn(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), ws.data_ptr(), ws_elems, B, cin, t_in, cout, t_out,
                 k, stride, pad, dil, groups, _s(dy)), "evmi_conv1d_dgrad_cbt")
@@ -515,16 +572,6 @@ def conv1d_bwd_data_mfma(dy, w, t_in, stride=1, pad=0, dil=1, groups=1, keep=Non
     return dx
 
 
-# "mfma": the hand-written fp32 matrix-core convolution kernels; "gemm": unfold + the plain fp32 GEMM (A/B and reference variant).
-# wgrad "auto": implicit GEMM for grouped layers (2-5x over unfold + per-group GEMMs), unfold + ONE library GEMM for dense
-# ones in fp32 mode (one long-K product, split over K).
-# "operands": "f32" = exact fp32 fmaf chains on the fp32-input matrix cores; "bf16" = the same kernels round both operands to
-# bf16 on their way into v_mfma_f32_32x32x16_bf16 (fp32 accumulation, fp32 tensors in HBM, fp32 master weights).
-# "packed": bf16 operands go through the packed-input kernel (conv_cbt_bf16_pk.hip) where it takes the shape; False = always the
-# in-LDS rounding variant of the fp32 kernels (A/B switch).
-CONV_BACKEND = {"fwd": "mfma", "dgrad": "mfma", "wgrad": "mfma", "operands": "f32", "packed": True}
-
-
 def wgrad_takes_bf16(B, cin, t_in, cout, t_out, k, stride, pad, dil, groups) -> bool:
     """True where precision="bf16" computes this layer's weight gradient from bf16-rounded operands (conv_wgrad_bf16_pk.hip takes
     the shape); narrower groups keep exact fp32 operands.  The ONE statement of that rule: tests restating the arithmetic for
@@ -547,26 +594,17 @@ def mfma_conv_supported(B, cin, t_in, cout, n_out, k, stride, dil, groups) -> bo
     return bool(_lib.load().evmi_conv1d_cbt_f32_supported(B, cin, t_in, cout, n_out, k, stride, dil, groups))
 
 
-_ACT_EW = {ACT_SILU: 13, ACT_RELU: 14, ACT_TANH: EW_TANH}
-
-
 def conv1d_fwd(x, w, bias, stride=1, pad=0, dil=1, groups=1, lrelu_slope=None, act=ACT_NONE, keep=None):
     """x [Cin, B, T], w [Cout, Cin/groups, k] -> y [Cout, B, T_out] (leaky-relu applied in the epilogue when a slope is given;
     ``act``: one of the other epilogue activations)."""
     cin, B, t_in = x.shape
     cout, cin_g, k = w.shape
-    if act != ACT_NONE:
-        if CONV_BACKEND["fwd"] == "mfma" and mfma_conv_supported(B, cin, t_in, cout, conv_out_len(t_in, k, stride, pad, dil), k, stride, dil, groups):
-            return conv1d_mfma(x, w, bias, stride, pad, dil, groups, act=act, keep=keep)
-        y = conv1d_fwd(x, w, bias, stride, pad, dil, groups)
-        return elementwise(_ACT_EW[act], y, out=y)
+    if act == ACT_NONE and lrelu_slope is not None:
+        act, slope = ACT_LRELU, lrelu_slope
+    else:
+        slope = 0.0
     if CONV_BACKEND["fwd"] == "mfma" and mfma_conv_supported(B, cin, t_in, cout, conv_out_len(t_in, k, stride, pad, dil), k, stride, dil, groups):
-        if lrelu_slope is None:
-            return conv1d_mfma(x, w, bias, stride, pad, dil, groups, keep=keep)
-        return conv1d_mfma(x, w, bias, stride, pad, dil, groups, act=ACT_LRELU, act_param=lrelu_slope, keep=keep)
-    if lrelu_slope is not None:
-        y = conv1d_fwd(x, w, bias, stride, pad, dil, groups)
-        return elementwise(EW_LRELU, y, out=y, p0=lrelu_slope)
+        return conv1d_mfma(x, w, bias, stride, pad, dil, groups, act=act, act_param=slope, keep=keep)
     col, t_out = unfold(x, k, stride, pad, dil)
     y = torch.empty(cout, B, t_out, device=x.device, dtype=torch.float32)
     N = B * t_out
@@ -576,7 +614,7 @@ def conv1d_fwd(x, w, bias, stride=1, pad=0, dil=1, groups=1, lrelu_slope=None, a
     gemm_groups(w, col, y, groups, cout_g, N, kg, kg, N, N, cout_g * kg, kg * N, cout_g * N)
     if bias is not None:
         _chk(_lib.load().evmi_bias_add_rows_f32(y.data_ptr(), bias.data_ptr(), cout, N, _s(y)), "evmi_bias_add_rows_f32")
-    return y
+    return y if act == ACT_NONE else elementwise(_ACT_EW[act], y, out=y, p0=slope)  # (the activation as a pass of its own)
 
 
 def _weight_and_bias_grad(x, w_shape, dy, dw, db_out, stride, pad, dil, groups, accumulate, packed=None, x_standin=False):
@@ -590,7 +628,7 @@ def _weight_and_bias_grad(x, w_shape, dy, dw, db_out, stride, pad, dil, groups, 
     cout_g = cout // groups
     lib = _lib.load()
     pk_elems = (lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, cin, t_in, cout, t_out, k, stride, pad, dil, groups)
-                if CONV_BACKEND["operands"] == "bf16" and CONV_BACKEND["packed"] and CONV_BACKEND["wgrad"] != "gemm" else 0)
+                if packed_bf16() and CONV_BACKEND["wgrad"] != "gemm" else 0)
     ws_elems = 0
     if pk_elems == 0 and (CONV_BACKEND["wgrad"] == "mfma" or (CONV_BACKEND["wgrad"] == "auto" and groups > 1)):
         ws_elems = lib.evmi_conv1d_wgrad_cbt_f32_ws_elems(B, cin, t_in, cout, t_out, k, stride, pad, dil, groups)
@@ -686,36 +724,96 @@ def conv1d_bwd(x, w, dy, stride=1, pad=0, dil=1, groups=1, need_dx=True, dw_out=
     return dx, dw, db
 
 
-# ---- dense2(dropout(silu(a))) and its backward with the activation / mask applied while the operands are packed ---------------------
-def ffn_fused_supported(B, t, c_mid, c_out) -> bool:
-    """True where both halves below run on the packed bf16 kernels with shared packed operands (pointwise layers, B * t a multiple of
-    the weight gradient's K step): the FastSpeech2 feed-forward blocks at precision="bf16"."""
-    if not (_packed() and CONV_BACKEND["fwd"] == "mfma" and CONV_BACKEND["dgrad"] == "mfma" and CONV_BACKEND["wgrad"] != "gemm"):
+# ---- pointwise layers whose neighbours (LayerNorm, SiLU, dropout, the residual add) ride in the packs and epilogues of the packed bf16
+# kernels: the geometry, the support rule and the launches every such form shares -------------------------------------------------
+_PK_WS_ELEMS = {"fwd": "evmi_conv1d_cbt_bf16pk_ws_elems", "dgrad": "evmi_conv1d_dgrad_cbt_bf16pk_ws_elems", "wgrad": "evmi_conv1d_wgrad_cbt_bf16pk_ws_elems"}
+
+
+def pointwise_ws_elems(product, B, c_in, t, c_out) -> int:
+    """Workspace elements of one packed product ("fwd", "dgrad" or "wgrad") of a pointwise stride-1 layer c_in -> c_out on B items of t
+    columns; 0: the packed kernel does not take the shape."""
+    return getattr(_lib.load(), _PK_WS_ELEMS[product])(B, c_in, t, c_out, t, 1, 1, 0, 1, 1)
+
+
+def pointwise_shares_packed(B, t, *layers, dgrad=True) -> bool:
+    """True where every pointwise layer (c_in, c_out) of ``layers`` takes all three products on the packed bf16 kernels with shared packed
+    operands (B * t a multiple of the weight gradient's K step).  ``dgrad=False``: the input gradient is not probed."""
+    if not (packed_serves_all() and shares_packed(B, t, 1, 1, 0, 1, 1)):
         return False
-    lib = _lib.load()
-    geo = (t, 1, 1, 0, 1, 1)
-    return bool(shares_packed(B, t, 1, 1, 0, 1, 1)
-                # layer 1 (c_out -> c_mid): forward, input gradient, weight gradient
-                and lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, c_out, t, c_mid, *geo) > 0
-                and lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, c_out, t, c_mid, *geo) > 0
-                and lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, c_out, t, c_mid, *geo) > 0
-                and dgrad_mfma_supported(B, c_out, t, c_mid, t, 1, 1, 1, 1)
-                # layer 2 (c_mid -> c_out): its weight gradient reads the packed dropout(silu(a)) -- the fp32 tensor handed to
-                # conv1d_bwd is the pre-activation a, a stand-in (ADVICE r04: probe these too)
-                and lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, c_mid, t, c_out, *geo) > 0
-                and lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, c_mid, t, c_out, *geo) > 0
-                and lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, c_mid, t, c_out, *geo) > 0
-                and dgrad_mfma_supported(B, c_mid, t, c_out, t, 1, 1, 1, 1))
+    return all(pointwise_ws_elems("fwd", B, c_in, t, c_out) > 0
+               and (not dgrad or pointwise_ws_elems("dgrad", B, c_in, t, c_out) > 0)
+               and pointwise_ws_elems("wgrad", B, c_in, t, c_out) > 0
+               and (not dgrad or dgrad_mfma_supported(B, c_in, t, c_out, t, 1, 1, 1, 1)) for c_in, c_out in layers)
+
+
+def ffn_fused_supported(B, t, c_mid, c_out) -> bool:
+    """True where both halves of dense2(dropout(silu(a))) run on the packed bf16 kernels with shared packed operands: the FastSpeech2
+    feed-forward blocks at precision="bf16".  Layer 1 (c_out -> c_mid), and layer 2 (c_mid -> c_out), whose weight gradient reads the
+    packed dropout(silu(a)) -- the fp32 tensor handed to conv1d_bwd is the pre-activation a, a stand-in."""
+    return pointwise_shares_packed(B, t, (c_out, c_mid), (c_mid, c_out))
 
 
 def ln_dense_fused_supported(B, t, c_in, c_out) -> bool:
     """True where LayerNorm -> pointwise layer runs with the normalised tensor written straight into the layer's packed input."""
-    if not (_packed() and CONV_BACKEND["fwd"] == "mfma" and CONV_BACKEND["dgrad"] == "mfma" and CONV_BACKEND["wgrad"] != "gemm"):
-        return False
+    return c_in in (128, 256) and pointwise_shares_packed(B, t, (c_in, c_out), dgrad=False)
+
+
+def resdrop_fused_supported(B, t, c_in, c_out) -> bool:
+    """True where a + s * dropout(dense(h)) runs with the residual add and the dropout in the layer's epilogue, their backward in the
+    pack of dy (the FastSpeech2 sub-layers' last dense layers at precision="bf16")."""
+    return RESDROP_FUSION[0] and pointwise_shares_packed(B, t, (c_in, c_out))
+
+
+def ffn_packed_supported(B, t, c_in, c_mid, c_out) -> bool:
+    """True where LayerNorm -> dense(c_in -> c_mid) -> SiLU -> dropout -> dense(c_mid -> c_out) -> (+ residual, dropout) runs as the packed
+    chain of ffn_packed_fwd / ffn_packed_bwd (every fusion it is built from is available)."""
+    return bool(FFN_PACKED[0] and c_mid % 8 == 0 and ffn_fused_supported(B, t, c_mid, c_out) and ln_dense_fused_supported(B, t, c_in, c_mid)
+                and resdrop_fused_supported(B, t, c_mid, c_out))
+
+
+def _prepacked_wgrad(B, c_in, t, c_out, x, xp, dy, dyp, dw, db):
+    """-> the launch (for ``side_wgrad.run``) of a pointwise layer's weight gradient from its packed operands -- xp (or None) and dyp, beside
+    the fp32 tensors x and dy they were packed from -- accumulated into dw, then db (if given) += the row sums of the packed dy
+    ([c_out / 8 octet rows][pk_pitch units])."""
     lib = _lib.load()
-    return bool(c_in in (128, 256) and shares_packed(B, t, 1, 1, 0, 1, 1)
-                and lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, c_in, t, c_out, t, 1, 1, 0, 1, 1) > 0
-                and lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, c_in, t, c_out, t, 1, 1, 0, 1, 1) > 0)
+
+    def launch():
+        n_w = pointwise_ws_elems("wgrad", B, c_in, t, c_out)
+        wsw = WS.get("pkw", n_w, dw.device)
+        _count_conv(B, t, c_out, c_in, 1)
+        _chk(lib.evmi_conv1d_wgrad_cbt_bf16pk_prepacked(x.data_ptr(), _lib.ptr(xp), dy.data_ptr(), dyp.data_ptr(), dw.data_ptr(), wsw.data_ptr(), n_w, B, c_in, t,
+                                                        c_out, t, 1, 1, 0, 1, 1, 1, _s(dw)), "evmi_conv1d_wgrad_cbt_bf16pk_prepacked")
+        if db is not None:
+            job = (_lib.PkFlatRows * 1)()
+            job[0].dy, job[0].plane, job[0].units, job[0].C, job[0].db = dyp.data_ptr(), pk_pitch(B, t), pk_pitch(B, t), c_out, db.data_ptr()
+            n_r = lib.evmi_pkflat_rowsum_ws_elems(1, job)
+            wsr = WS.get("pkrow", n_r, dw.device)
+            _chk(lib.evmi_pkflat_rowsum(1, job, wsr.data_ptr(), n_r, _s(dw)), "evmi_pkflat_rowsum")
+
+    return launch
+
+
+def _staged_bwd(entry, lead, x, w, dy, dw_out, db_out, packed, alive, need_x_packed=None):
+    """Backward of a pointwise layer whose output gradient is formed from dy while dy is packed (``entry``: the staged input-gradient entry
+    point that does so, ``lead``: its arguments in front of w): stage 1 packs, the weight gradient forks behind the pack, stage 2 is the
+    input gradient, then the weight and bias gradient read the packed operands (``packed["x_packed"]``, the packed dy).  ``alive``: the
+    tensors the side launch reads (with the two packed buffers: what stays referenced until the join).  Returns dx."""
+    cin, B, t = x.shape
+    cout = w.shape[0]
+    fn = getattr(_lib.load(), entry)
+    pk_elems = pointwise_ws_elems("dgrad", B, cin, t, cout)
+    ws = torch.empty(pk_elems, device=dy.device, dtype=torch.float32)
+    dx = torch.empty(cin, B, t, device=dy.device, dtype=torch.float32)
+    args = (*lead, w.data_ptr(), dx.data_ptr(), ws.data_ptr(), pk_elems, B, cin, t, cout, t, 1, 1, 0, 1, 1)
+    _chk(fn(1, *args, _s(dy)), entry)
+    xp = packed.get("x_packed") if packed else None
+    if xp is None and need_x_packed:
+        raise RuntimeError(need_x_packed)
+    side = side_wgrad(*alive, ws, xp).mark()  # fork behind the pack, in front of the input gradient
+    _count_conv(B, t, cout, cin, 1)
+    _chk(fn(2, *args, _s(dy)), entry)
+    side.run(_prepacked_wgrad(B, cin, t, cout, x, xp, dy, ws, dw_out, db_out))
+    return dx
 
 
 def layernorm_dense_fwd(x, gamma, beta, w, bias, keep, act=ACT_NONE, eps=1e-5):
@@ -724,7 +822,7 @@ def layernorm_dense_fwd(x, gamma, beta, w, bias, keep, act=ACT_NONE, eps=1e-5):
     cin, B, t = x.shape
     cout = w.shape[0]
     lib = _lib.load()
-    pk_elems = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cin, t, cout, t, 1, 1, 0, 1, 1)
+    pk_elems = pointwise_ws_elems("fwd", B, cin, t, cout)
     ws = keep["x_packed"] = torch.empty(pk_elems, device=x.device, dtype=torch.float32)
     out = torch.empty(cout, B, t, device=x.device, dtype=torch.float32)
     # (the layer's weight fragments are prepared by LayerNorm's launch: the convolution starts without a preparation launch of its own)
@@ -736,18 +834,18 @@ def layernorm_dense_fwd(x, gamma, beta, w, bias, keep, act=ACT_NONE, eps=1e-5):
     return out
 
 
+# ---- dense2(dropout(silu(a))) and its backward with the activation / mask applied while the operands are packed ---------------------
 def conv1d_fwd_silu_dropout(a, w, bias, p, seed, keep):
     """y = dense(dropout(silu(a), p)) (pointwise w [cout, cin, 1]); the activated, masked tensor exists only packed, in ``keep["x_packed"]``
     (the layer's weight gradient reads it there).  Caller: ffn_fused_supported."""
     cin, B, t = a.shape
     cout = w.shape[0]
-    lib = _lib.load()
-    pk_elems = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cin, t, cout, t, 1, 1, 0, 1, 1)
+    pk_elems = pointwise_ws_elems("fwd", B, cin, t, cout)
     ws = keep["x_packed"] = torch.empty(pk_elems, device=a.device, dtype=torch.float32)
     out = torch.empty(cout, B, t, device=a.device, dtype=torch.float32)
     _count_conv(B, t, cout, cin, 1)
-    _chk(lib.evmi_conv1d_cbt_bf16pk_silu_dropout(a.data_ptr(), w.data_ptr(), _lib.ptr(bias), out.data_ptr(), ws.data_ptr(), pk_elems, B, cin, t, cout, 1, 0,
-                                                 float(p), int(seed), _lib.ptr(SEED_BASE[0]), _s(a)), "evmi_conv1d_cbt_bf16pk_silu_dropout")
+    _chk(_lib.load().evmi_conv1d_cbt_bf16pk_silu_dropout(a.data_ptr(), w.data_ptr(), _lib.ptr(bias), out.data_ptr(), ws.data_ptr(), pk_elems, B, cin, t, cout, 1, 0,
+                                                         float(p), int(seed), _lib.ptr(SEED_BASE[0]), _s(a)), "evmi_conv1d_cbt_bf16pk_silu_dropout")
     return out
 
 
@@ -756,97 +854,50 @@ def conv1d_bwd_silu_dropout_dy(x, w, ds, pre, p, seed, dw_out, db_out, packed):
     behind it): dy is formed while ds is packed -- it exists only as the packed bf16 operand that the input gradient, the weight gradient
     and the bias gradient (row sums of the packed rows) all read.  Returns dx; dw_out / db_out are accumulated into.  ``packed``: the
     forward's ``keep`` dict (x_packed).  Caller: ffn_fused_supported."""
-    cin, B, t = x.shape
-    cout = w.shape[0]
-    lib = _lib.load()
-    pk_elems = lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, cin, t, cout, t, 1, 1, 0, 1, 1)
-    ws = torch.empty(pk_elems, device=ds.device, dtype=torch.float32)
-    dx = torch.empty(cin, B, t, device=ds.device, dtype=torch.float32)
-    args = (ds.data_ptr(), pre.data_ptr(), float(p), int(seed), _lib.ptr(SEED_BASE[0]), w.data_ptr(), dx.data_ptr(), ws.data_ptr(), pk_elems, B, cin, t, cout, t,
-            1, 1, 0, 1, 1)
-    _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk_staged_silu_dropout(1, *args, _s(ds)), "evmi_conv1d_dgrad_cbt_bf16pk_staged_silu_dropout")
-    xp = packed.get("x_packed") if packed else None
-    side = side_wgrad(x, ds, pre, dw_out, db_out, ws, xp).mark()  # fork behind the pack, in front of the input gradient
-    _count_conv(B, t, cout, cin, 1)
-    _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk_staged_silu_dropout(2, *args, _s(ds)), "evmi_conv1d_dgrad_cbt_bf16pk_staged_silu_dropout")
-
-    def launch():
-        n_w = lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, cin, t, cout, t, 1, 1, 0, 1, 1)
-        wsw = WS.get("pkw", n_w, x.device)
-        _count_conv(B, t, cout, cin, 1)
-        _chk(lib.evmi_conv1d_wgrad_cbt_bf16pk_prepacked(x.data_ptr(), _lib.ptr(xp), ds.data_ptr(), ws.data_ptr(), dw_out.data_ptr(), wsw.data_ptr(), n_w, B, cin, t,
-                                                        cout, t, 1, 1, 0, 1, 1, 1, _s(x)), "evmi_conv1d_wgrad_cbt_bf16pk_prepacked")
-        if db_out is not None:  # row sums of the packed dy: [cout / 8 octet rows][B * t units]
-            job = (_lib.PkFlatRows * 1)()
-            job[0].dy, job[0].plane, job[0].units, job[0].C, job[0].db = ws.data_ptr(), pk_pitch(B, t), pk_pitch(B, t), cout, db_out.data_ptr()
-            n_r = lib.evmi_pkflat_rowsum_ws_elems(1, job)
-            wsr = WS.get("pkrow", n_r, x.device)
-            _chk(lib.evmi_pkflat_rowsum(1, job, wsr.data_ptr(), n_r, _s(x)), "evmi_pkflat_rowsum")
-
-    side.run(launch)
-    return dx
+    return _staged_bwd("evmi_conv1d_dgrad_cbt_bf16pk_staged_silu_dropout", (ds.data_ptr(), pre.data_ptr(), float(p), int(seed), _lib.ptr(SEED_BASE[0])),
+                       x, w, ds, dw_out, db_out, packed, alive=(x, ds, pre, dw_out, db_out))
 
 
 # ---- a feed-forward block whose wide middle tensor exists packed only ----------------------------------------------------------
-FFN_PACKED = [_os.environ.get("EVMI_FS2_FFN_PACKED", "1") != "0"]  # A/B switch (tools/fs2_train_bench.py)
-
-
-def ffn_packed_supported(B, t, c_in, c_mid, c_out) -> bool:
-    """True where LayerNorm -> dense(c_in -> c_mid) -> SiLU -> dropout -> dense(c_mid -> c_out) -> (+ residual, dropout) runs as the packed
-    chain of ffn_packed_fwd / ffn_packed_bwd (every fusion it is built from is available)."""
-    return bool(FFN_PACKED[0] and c_mid % 8 == 0 and ffn_fused_supported(B, t, c_mid, c_out) and ln_dense_fused_supported(B, t, c_in, c_mid)
-                and resdrop_fused_supported(B, t, c_mid, c_out))
+def _ffn_packed_chain(x, gamma, beta, w1, b1, w2, b2, res, eps, keep=None, p=0.0, seed=0, seed_out=0, scale=1.0):
+    """The three launches of ffn_packed_fwd (``keep`` given: bf16(a) is stored for the backward, masks are drawn from the seed base) and
+    ffn_packed_infer (no dropout, nothing stored): LayerNorm (+ the weight fragments of both layers), dense1, dense2."""
+    cin, B, t = x.shape
+    cmid, cout = w1.shape[0], w2.shape[0]
+    lib = _lib.load()
+    n1 = pointwise_ws_elems("fwd", B, cin, t, cmid)
+    n2 = pointwise_ws_elems("fwd", B, cmid, t, cout)
+    ws1 = torch.empty(n1, device=x.device, dtype=torch.float32)
+    ws2 = torch.empty(n2, device=x.device, dtype=torch.float32)
+    a_pk = base = None  # (inference: NULL for both)
+    if keep is not None:
+        a_pk = torch.empty(cmid // 8 * pk_pitch(B, t) * 4, device=x.device, dtype=torch.float32)  # 16-byte units of 8 bf16 channels
+        keep["x_packed"], keep["s_packed"], keep["a_pk"] = ws1, ws2, a_pk
+        base = _lib.ptr(SEED_BASE[0])
+    out = torch.empty(cout, B, t, device=x.device, dtype=torch.float32)
+    st = _s(x)
+    _chk(lib.evmi_layernorm_pack_bf16pk_w(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws1.data_ptr(), n1, B, cin, t, cmid, eps, w1.data_ptr(), w2.data_ptr(),
+                                          ws2.data_ptr(), n2, cout, st), "evmi_layernorm_pack_bf16pk_w")
+    _count_conv(B, t, cmid, cin, 1)
+    _chk(lib.evmi_conv1d_cbt_bf16pk_ffn_up(w1.data_ptr(), _lib.ptr(b1), ws1.data_ptr(), n1, _lib.ptr(a_pk), ws2.data_ptr(), n2, B, cin, t, cmid, cout, float(p),
+                                           int(seed), base, 1, st), "evmi_conv1d_cbt_bf16pk_ffn_up")
+    _count_conv(B, t, cout, cmid, 1)
+    _chk(lib.evmi_conv1d_cbt_bf16pk_resdrop(3, None, w2.data_ptr(), _lib.ptr(b2), res.data_ptr(), out.data_ptr(), ws2.data_ptr(), n2, B, cmid, t, cout, 0.0, 0,
+                                            float(p), int(seed_out), float(scale), base, st), "evmi_conv1d_cbt_bf16pk_resdrop")
+    return out
 
 
 def ffn_packed_fwd(x, gamma, beta, w1, b1, w2, b2, res, p, seed, seed_out, scale, keep, eps=1e-5):
     """res + scale * dropout(dense2(dropout(silu(dense1(LayerNorm(x))), p)), p) with NO fp32 copy of the c_mid-channel tensors: LayerNorm
     writes dense1's packed input, dense1's epilogue writes bf16(a) (``keep["a_pk"]``, for the backward) and dense2's packed input
     dropout(silu(a)) (``keep["s_packed"]``), dense2's epilogue adds the residual.  ``keep["x_packed"]``: LayerNorm(x), packed."""
-    cin, B, t = x.shape
-    cmid, cout = w1.shape[0], w2.shape[0]
-    lib = _lib.load()
-    geo = (t, 1, 1, 0, 1, 1)
-    n1 = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cin, t, cmid, *geo)
-    n2 = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cmid, t, cout, *geo)
-    ws1 = keep["x_packed"] = torch.empty(n1, device=x.device, dtype=torch.float32)
-    ws2 = keep["s_packed"] = torch.empty(n2, device=x.device, dtype=torch.float32)
-    a_pk = keep["a_pk"] = torch.empty(cmid // 8 * pk_pitch(B, t) * 4, device=x.device, dtype=torch.float32)  # 16-byte units of 8 bf16 channels
-    out = torch.empty(cout, B, t, device=x.device, dtype=torch.float32)
-    st = _s(x)
-    # three launches: LayerNorm (+ the weight fragments of both layers), dense1, dense2
-    _chk(lib.evmi_layernorm_pack_bf16pk_w(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws1.data_ptr(), n1, B, cin, t, cmid, eps, w1.data_ptr(), w2.data_ptr(),
-                                          ws2.data_ptr(), n2, cout, st), "evmi_layernorm_pack_bf16pk_w")
-    _count_conv(B, t, cmid, cin, 1)
-    _chk(lib.evmi_conv1d_cbt_bf16pk_ffn_up(w1.data_ptr(), _lib.ptr(b1), ws1.data_ptr(), n1, a_pk.data_ptr(), ws2.data_ptr(), n2, B, cin, t, cmid, cout, float(p),
-                                           int(seed), _lib.ptr(SEED_BASE[0]), 1, st), "evmi_conv1d_cbt_bf16pk_ffn_up")
-    _count_conv(B, t, cout, cmid, 1)
-    _chk(lib.evmi_conv1d_cbt_bf16pk_resdrop(3, None, w2.data_ptr(), _lib.ptr(b2), res.data_ptr(), out.data_ptr(), ws2.data_ptr(), n2, B, cmid, t, cout, 0.0, 0,
-                                            float(p), int(seed_out), float(scale), _lib.ptr(SEED_BASE[0]), st), "evmi_conv1d_cbt_bf16pk_resdrop")
-    return out
+    return _ffn_packed_chain(x, gamma, beta, w1, b1, w2, b2, res, eps, keep, p, seed, seed_out, scale)
 
 
 def ffn_packed_infer(x, gamma, beta, w1, b1, w2, b2, res, eps=1e-5):
-    """res + dense2(silu(dense1(LayerNorm(x)))) without dropout (inference): three launches -- LayerNorm (+ the weight fragments of both
-    layers), dense1 (its epilogue writes silu(a) as dense2's packed input; the pre-activation is not stored), dense2 (+ residual)."""
-    cin, B, t = x.shape
-    cmid, cout = w1.shape[0], w2.shape[0]
-    lib = _lib.load()
-    geo = (t, 1, 1, 0, 1, 1)
-    n1 = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cin, t, cmid, *geo)
-    n2 = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cmid, t, cout, *geo)
-    ws1 = torch.empty(n1, device=x.device, dtype=torch.float32)
-    ws2 = torch.empty(n2, device=x.device, dtype=torch.float32)
-    out = torch.empty(cout, B, t, device=x.device, dtype=torch.float32)
-    st = _s(x)
-    _chk(lib.evmi_layernorm_pack_bf16pk_w(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws1.data_ptr(), n1, B, cin, t, cmid, eps, w1.data_ptr(), w2.data_ptr(),
-                                          ws2.data_ptr(), n2, cout, st), "evmi_layernorm_pack_bf16pk_w")
-    _count_conv(B, t, cmid, cin, 1)
-    _chk(lib.evmi_conv1d_cbt_bf16pk_ffn_up(w1.data_ptr(), _lib.ptr(b1), ws1.data_ptr(), n1, None, ws2.data_ptr(), n2, B, cin, t, cmid, cout, 0.0, 0, None, 1, st),
-         "evmi_conv1d_cbt_bf16pk_ffn_up")
-    _count_conv(B, t, cout, cmid, 1)
-    _chk(lib.evmi_conv1d_cbt_bf16pk_resdrop(3, None, w2.data_ptr(), _lib.ptr(b2), res.data_ptr(), out.data_ptr(), ws2.data_ptr(), n2, B, cmid, t, cout, 0.0, 0,
-                                            0.0, 0, 1.0, None, st), "evmi_conv1d_cbt_bf16pk_resdrop")
-    return out
+    """res + dense2(silu(dense1(LayerNorm(x)))) without dropout (inference): dense1's epilogue writes silu(a) as dense2's packed input;
+    the pre-activation is not stored."""
+    return _ffn_packed_chain(x, gamma, beta, w1, b1, w2, b2, res, eps)
 
 
 def ffn_packed_bwd(x, w1, w2, dy, p, seed, seed_out, scale, dw1, db1, dw2, db2, keep):
@@ -856,9 +907,8 @@ def ffn_packed_bwd(x, w1, w2, dy, p, seed, seed_out, scale, dw1, db1, dw2, db2, 
     cin, B, t = x.shape
     cmid, cout = w1.shape[0], w2.shape[0]
     lib = _lib.load()
-    geo = (t, 1, 1, 0, 1, 1)
-    n_d2 = lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, cmid, t, cout, *geo)
-    n_d1 = lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, cin, t, cmid, *geo)
+    n_d2 = pointwise_ws_elems("dgrad", B, cmid, t, cout)
+    n_d1 = pointwise_ws_elems("dgrad", B, cin, t, cmid)
     wsd2 = torch.empty(n_d2, device=dy.device, dtype=torch.float32)
     wsd1 = torch.empty(n_d1, device=dy.device, dtype=torch.float32)
     dh = torch.empty(cin, B, t, device=dy.device, dtype=torch.float32)
@@ -872,64 +922,30 @@ def ffn_packed_bwd(x, w1, w2, dy, p, seed, seed_out, scale, dw1, db1, dw2, db2, 
     _count_conv(B, t, cout, cmid, 1)
     _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk_ffn_down(w2.data_ptr(), wsd2.data_ptr(), n_d2, a_pk.data_ptr(), wsd1.data_ptr(), n_d1, B, cin, t, cmid, cout, float(p),
                                                    int(seed), _lib.ptr(SEED_BASE[0]), st), "evmi_conv1d_dgrad_cbt_bf16pk_ffn_down")
-
-    def wgrad(c_i, c_o, xp, dyp, dw, db):
-        def launch():
-            n_w = lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, c_i, t, c_o, *geo)
-            wsw = WS.get("pkw", n_w, x.device)
-            _count_conv(B, t, c_o, c_i, 1)
-            # (the fp32 operands are stand-ins: both packed copies are given)
-            _chk(lib.evmi_conv1d_wgrad_cbt_bf16pk_prepacked(xp.data_ptr(), xp.data_ptr(), dyp.data_ptr(), dyp.data_ptr(), dw.data_ptr(), wsw.data_ptr(), n_w, B, c_i, t,
-                                                            c_o, t, 1, 1, 0, 1, 1, 1, _s(x)), "evmi_conv1d_wgrad_cbt_bf16pk_prepacked")
-            if db is not None:  # row sums of the packed output gradient: [c_o / 8 octet rows][B * t units]
-                job = (_lib.PkFlatRows * 1)()
-                job[0].dy, job[0].plane, job[0].units, job[0].C, job[0].db = dyp.data_ptr(), pk_pitch(B, t), pk_pitch(B, t), c_o, db.data_ptr()
-                n_r = lib.evmi_pkflat_rowsum_ws_elems(1, job)
-                wsr = WS.get("pkrow", n_r, x.device)
-                _chk(lib.evmi_pkflat_rowsum(1, job, wsr.data_ptr(), n_r, _s(x)), "evmi_pkflat_rowsum")
-        return launch
-
-    side2.run(wgrad(cmid, cout, ws2, wsd2, dw2, db2))
+    # (the packed buffers stand in for the fp32 operands, which were never stored: both packed copies are given)
+    side2.run(_prepacked_wgrad(B, cmid, t, cout, ws2, ws2, wsd2, wsd2, dw2, db2))
     side1 = side_wgrad(x, dw1, db1, wsd1, ws1, a_pk).mark()  # fork behind the epilogue that wrote the packed dy, in front of the input gradient
     _count_conv(B, t, cmid, cin, 1)
     _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk_staged(3, wsd1.data_ptr(), w1.data_ptr(), dh.data_ptr(), wsd1.data_ptr(), n_d1, B, cin, t, cmid, t, 1, 1, 0, 1, 1, st),
          "evmi_conv1d_dgrad_cbt_bf16pk_staged")
-    side1.run(wgrad(cin, cmid, ws1, wsd1, dw1, db1))
+    side1.run(_prepacked_wgrad(B, cin, t, cmid, ws1, ws1, wsd1, wsd1, dw1, db1))
     return dh
 
 
 # ---- a + s * dropout(dense(h)): the residual add and the dropout in the layer's epilogue, their backward in the pack of dy ---------------
-RESDROP_FUSION = [_os.environ.get("EVMI_FS2_RESDROP", "1") != "0"]  # A/B switch of the fusion below (tools/fs2_train_bench.py)
-
-
-def resdrop_fused_supported(B, t, c_in, c_out) -> bool:
-    """True where a pointwise layer c_in -> c_out runs on the packed bf16 kernels with shared packed operands in all three products
-    (the FastSpeech2 sub-layers' last dense layers at precision="bf16")."""
-    if not RESDROP_FUSION[0] or not (_packed() and CONV_BACKEND["fwd"] == "mfma" and CONV_BACKEND["dgrad"] == "mfma" and CONV_BACKEND["wgrad"] != "gemm"):
-        return False
-    lib = _lib.load()
-    geo = (t, 1, 1, 0, 1, 1)
-    return bool(shares_packed(B, t, 1, 1, 0, 1, 1)
-                and lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, c_in, t, c_out, *geo) > 0
-                and lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, c_in, t, c_out, *geo) > 0
-                and lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, c_in, t, c_out, *geo) > 0
-                and dgrad_mfma_supported(B, c_in, t, c_out, t, 1, 1, 1, 1))
-
-
 def conv1d_fwd_resdrop(x, w, bias, res, p, seed, scale, keep, in_p=None, in_seed=0):
     """res + scale * dropout(dense(in) + bias, p) in ONE launch pair (pack + convolution): in = x, or dropout(silu(x), in_p) when
     ``in_p`` is given (the second layer of a feed-forward block: conv1d_fwd_silu_dropout's input fusion).  The packed input stays in
     ``keep["x_packed"]`` for the weight gradient.  Caller: resdrop_fused_supported (and ffn_fused_supported for the input fusion)."""
     cin, B, t = x.shape
     cout = w.shape[0]
-    lib = _lib.load()
-    pk_elems = lib.evmi_conv1d_cbt_bf16pk_ws_elems(B, cin, t, cout, t, 1, 1, 0, 1, 1)
+    pk_elems = pointwise_ws_elems("fwd", B, cin, t, cout)
     ws = keep["x_packed"] = torch.empty(pk_elems, device=x.device, dtype=torch.float32)
     out = torch.empty(cout, B, t, device=x.device, dtype=torch.float32)
     _count_conv(B, t, cout, cin, 1)
-    _chk(lib.evmi_conv1d_cbt_bf16pk_resdrop(0 if in_p is None else 1, x.data_ptr(), w.data_ptr(), _lib.ptr(bias), res.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                            pk_elems, B, cin, t, cout, float(in_p or 0.0), int(in_seed), float(p), int(seed), float(scale),
-                                            _lib.ptr(SEED_BASE[0]), _s(x)), "evmi_conv1d_cbt_bf16pk_resdrop")
+    _chk(_lib.load().evmi_conv1d_cbt_bf16pk_resdrop(0 if in_p is None else 1, x.data_ptr(), w.data_ptr(), _lib.ptr(bias), res.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                                    pk_elems, B, cin, t, cout, float(in_p or 0.0), int(in_seed), float(p), int(seed), float(scale),
+                                                    _lib.ptr(SEED_BASE[0]), _s(x)), "evmi_conv1d_cbt_bf16pk_resdrop")
     return out
 
 
@@ -938,41 +954,13 @@ def conv1d_bwd_dropout_dy(x, w, dy, p, seed, scale, dw_out, db_out, packed, x_st
     dz = scale * dropout(dy, p) is formed while dy is packed -- it exists only as the packed bf16 operand that the input gradient, the
     weight gradient and the bias gradient (row sums of the packed rows) read.  Returns dx; dw_out / db_out are accumulated into.
     ``packed``: the forward's ``keep`` dict (x_packed)."""
-    cin, B, t = x.shape
-    cout = w.shape[0]
-    lib = _lib.load()
-    pk_elems = lib.evmi_conv1d_dgrad_cbt_bf16pk_ws_elems(B, cin, t, cout, t, 1, 1, 0, 1, 1)
-    ws = torch.empty(pk_elems, device=dy.device, dtype=torch.float32)
-    dx = torch.empty(cin, B, t, device=dy.device, dtype=torch.float32)
-    args = (dy.data_ptr(), float(p), int(seed), _lib.ptr(SEED_BASE[0]), float(scale), w.data_ptr(), dx.data_ptr(), ws.data_ptr(), pk_elems, B, cin, t, cout, t,
-            1, 1, 0, 1, 1)
-    _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk_staged_dropout(1, *args, _s(dy)), "evmi_conv1d_dgrad_cbt_bf16pk_staged_dropout")
-    xp = packed.get("x_packed") if packed else None
-    if xp is None:
-        raise RuntimeError("conv1d_bwd_dropout_dy: the forward's packed input is required")
-    side = side_wgrad(x, dy, dw_out, db_out, ws, xp).mark()  # fork behind the pack, in front of the input gradient
-    _count_conv(B, t, cout, cin, 1)
-    _chk(lib.evmi_conv1d_dgrad_cbt_bf16pk_staged_dropout(2, *args, _s(dy)), "evmi_conv1d_dgrad_cbt_bf16pk_staged_dropout")
-
-    def launch():
-        n_w = lib.evmi_conv1d_wgrad_cbt_bf16pk_ws_elems(B, cin, t, cout, t, 1, 1, 0, 1, 1)
-        wsw = WS.get("pkw", n_w, x.device)
-        _count_conv(B, t, cout, cin, 1)
-        _chk(lib.evmi_conv1d_wgrad_cbt_bf16pk_prepacked(x.data_ptr(), _lib.ptr(xp), dy.data_ptr(), ws.data_ptr(), dw_out.data_ptr(), wsw.data_ptr(), n_w, B, cin, t,
-                                                        cout, t, 1, 1, 0, 1, 1, 1, _s(x)), "evmi_conv1d_wgrad_cbt_bf16pk_prepacked")
-        if db_out is not None:  # row sums of the packed dz: [cout / 8 octet rows][B * t units]
-            job = (_lib.PkFlatRows * 1)()
-            job[0].dy, job[0].plane, job[0].units, job[0].C, job[0].db = ws.data_ptr(), pk_pitch(B, t), pk_pitch(B, t), cout, db_out.data_ptr()
-            n_r = lib.evmi_pkflat_rowsum_ws_elems(1, job)
-            wsr = WS.get("pkrow", n_r, x.device)
-            _chk(lib.evmi_pkflat_rowsum(1, job, wsr.data_ptr(), n_r, _s(x)), "evmi_pkflat_rowsum")
-
-    side.run(launch)
-    return dx
+    return _staged_bwd("evmi_conv1d_dgrad_cbt_bf16pk_staged_dropout", (dy.data_ptr(), float(p), int(seed), _lib.ptr(SEED_BASE[0]), float(scale)),
+                       x, w, dy, dw_out, db_out, packed, alive=(x, dy, dw_out, db_out),
+                       need_x_packed="conv1d_bwd_dropout_dy: the forward's packed input is required")
 
 
+# ---- transposed convolution ------------------------------------------------------------------------------------------------------
 def _convt_via_dgrad():
-    import os
     if CONV_BACKEND["dgrad"] != "mfma":
         return False
     if CONV_BACKEND["operands"] == "bf16":
@@ -989,12 +977,10 @@ def conv_transpose1d_fwd(x, w, bias, stride, pad):
         # a transposed convolution IS the input gradient of the strided convolution with the same weight tensor
         # (w [c_in, c_out, k] read as [conv c_out][conv c_in][k]): the polyphase matrix-core kernels (packed bf16 or fp32), one launch
         y = conv1d_bwd_data_mfma(x, w, t_out, stride, pad, 1, 1)
-        if bias is not None:
-            _chk(_lib.load().evmi_bias_add_rows_f32(y.data_ptr(), bias.data_ptr(), cout, B * t_out, _s(y)), "evmi_bias_add_rows_f32")
-        return y
-    col = WS.get("dcol", cout * k * B * t_in, x.device).view(cout * k, B * t_in)
-    gemm(w.reshape(cin, cout * k), x.view(cin, B * t_in), col, ta=True)
-    y = fold(col, cout, B, t_out, t_in, k, stride, pad, 1)
+    else:
+        col = WS.get("dcol", cout * k * B * t_in, x.device).view(cout * k, B * t_in)
+        gemm(w.reshape(cin, cout * k), x.view(cin, B * t_in), col, ta=True)
+        y = fold(col, cout, B, t_out, t_in, k, stride, pad, 1)
     if bias is not None:
         _chk(_lib.load().evmi_bias_add_rows_f32(y.data_ptr(), bias.data_ptr(), cout, B * t_out, _s(y)), "evmi_bias_add_rows_f32")
     return y
@@ -1004,25 +990,26 @@ def conv_transpose1d_bwd(x, w, dy, stride, pad, need_dx=True, dw_out=None, db_ou
     cin, B, t_in = x.shape
     _, cout, k = w.shape
     t_out = dy.shape[2]
+
+    def bias_grad():
+        return row_reduce(0, dy, None, db_out, cout, B * t_out, accumulate=accumulate) if db_out is not None else None
+
+    dx = dw = None
     if _convt_via_dgrad() and dgrad_mfma_supported(B, cout, t_out, cin, t_in, k, stride, 1, 1):
         # the adjoint pair of the above: dx = conv1d(dy, w), dw = weight gradient of that convolution with (input, output
         # gradient) = (dy, x) -- both in the transposed convolution's own weight layout [c_in, c_out, k]
-        db = row_reduce(0, dy, None, db_out, cout, B * t_out, accumulate=accumulate) if db_out is not None else None
-        dw = None
+        db = bias_grad()
         if need_dw:
             _, dw, _ = conv1d_bwd(dy, w, x, stride, pad, 1, 1, need_dx=False, dw_out=dw_out, accumulate=accumulate)
-        dx = conv1d_fwd(dy, w, None, stride, pad, 1, 1) if need_dx else None
+        if need_dx:
+            dx = conv1d_fwd(dy, w, None, stride, pad, 1, 1)
         return dx, dw, db
     col, t_chk = unfold(dy, k, stride, pad, 1)  # [Cout*k, B*T_in]
     assert t_chk == t_in
-    dw = None
     if need_dw:
         dw = dw_out if dw_out is not None else torch.empty_like(w)
         gemm(x.view(cin, B * t_in), col, dw.view(cin, cout * k), tb=True, beta=1.0 if accumulate else 0.0)
-    db = None
-    if db_out is not None:
-        db = row_reduce(0, dy, None, db_out, cout, B * t_out, accumulate=accumulate)
-    dx = None
+    db = bias_grad()
     if need_dx:
         dx = torch.empty(cin, B, t_in, device=x.device, dtype=torch.float32)
         gemm(w.reshape(cin, cout * k), col, dx.view(cin, B * t_in))
@@ -1157,9 +1144,6 @@ def stft_frames_bwd(dfr, B, T, n_fft, hop):
 
 
 # ---- FastSpeech2 training operators (csrc/fs2_train_ops.hip) -----------------------------------------------------------
-EW_SILU, EW_RELU, EW_GLU, EW_SILU_BWD, EW_RELU_BWD, EW_CLIP_SCALE = 13, 14, 15, 18, 19, 20
-
-
 def layernorm(x, gamma, beta, eps=1e-5):
     y = torch.empty_like(x)
     _chk(_lib.load().evmi_layernorm_cbt_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1] * x.shape[2],
@@ -1170,7 +1154,6 @@ def layernorm(x, gamma, beta, eps=1e-5):
 # LayerNorm parameter gradients reduced once per backward chain: with LN_DEFER["on"] (the FastSpeech2 trainer, around its step) a
 # LayerNorm backward leaves its per-workgroup partial sums in a buffer of its own and ``wgrad_join`` -- where every chain ends --
 # reduces all the lists collected since in one launch (55 small launches on the step's critical chain otherwise).
-LN_DEFER = {"on": False}
 _LN_PENDING = {}  # stream -> [(partials, dgamma, dbeta, C, N)]: a chain's partials are reduced on the stream that produced them
 
 
@@ -1273,18 +1256,10 @@ def dwconv_bwd(x, w, dy, dw, db, k, need_dx=True):
     return dx
 
 
-# A device-resident base added to every dropout seed ([1] int64 tensor, or None): the FastSpeech2 trainer stores
-# (seed, step, rank) << 16 there before each step and passes the draw's index as `seed`, so a step captured into a HIP graph
-# draws fresh masks on every replay (include/evmi.h: evmi_dropout_f32).
-SEED_BASE = [None]
-
-
 def store_f32(dst: torch.Tensor, values) -> None:
     """dst[: len(values)] = values (<= 8 floats), carried in a kernel's argument block (no host buffer to keep alive)."""
-    import ctypes as C
-
     vals = [float(v) for v in values]
-    arr = (C.c_float * len(vals))(*vals)
+    arr = (ctypes.c_float * len(vals))(*vals)
     _chk(_lib.load().evmi_store_f32(dst.data_ptr(), len(vals), arr, _s(dst)), "evmi_store_f32")
 
 
@@ -1392,37 +1367,6 @@ def align_attention_bwd(q, k, soft, logprob, prior, hard, dlogprob, text_lens32,
 
 
 # ---- Global Style Token module (csrc/gst.hip): fp32 in both precision modes -------------------------------------------------------
-UNSET = object()  # "not given" where None is a value (SEED_BASE[0] is None outside a step)
-
-
-class mode:
-    """``with mode(operands="bf16", side_wgrad=True, seed_base=t, ln_defer=True):`` the operator switches that are given are set
-    (CONV_BACKEND["operands"], SIDE_WGRAD["on"], SEED_BASE[0], LN_DEFER["on"]) and exactly their previous values put back on the way
-    out, also when the body raises; the others are not touched.  Nests.  (A class, not a generator: a few per host-bound step.)"""
-
-    def __init__(self, operands=None, side_wgrad=None, seed_base=UNSET, ln_defer=None):
-        given = [(CONV_BACKEND, "operands", operands), (SIDE_WGRAD, "on", side_wgrad), (LN_DEFER, "on", ln_defer)]
-        self.new = [g for g in given if g[2] is not None] + ([(SEED_BASE, 0, seed_base)] if seed_base is not UNSET else [])
-
-    def __enter__(self):
-        self.old = [(box, key, box[key]) for box, key, _ in self.new]
-        for box, key, v in self.new:
-            box[key] = v
-        return self
-
-    def __exit__(self, *exc):
-        for box, key, v in self.old:
-            box[key] = v
-        return False
-
-
-def exact_f32():
-    """``with exact_f32():`` the dense operators inside run on exact fp32 operands whatever the model's precision mode (the style
-    module is tiny and recurrent: the wrong place to save bits) and issue their weight gradients in place: a launch collected for the
-    sibling stream (``side_wgrad``) would run later, under whatever mode holds then."""
-    return mode(operands="f32", side_wgrad=False)
-
-
 def gst_conv_out(n: int) -> int:
     """Output length of the reference encoder's convolution (k = 3, stride 2, padding 1) on an axis of n."""
     return (n - 1) // 2 + 1

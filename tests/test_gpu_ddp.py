@@ -231,11 +231,8 @@ def test_fastspeech2_two_ranks_hold_the_mean_of_their_local_gradients(cuda_devic
     for rank in range(2):
         one = T._trainer(ref_cfg, cuda_device, learn_alignment=learn_alignment)
         full = T._shaped_batch(ref_cfg, 5, learn_alignment, cuda_device, B=8) if learn_alignment else {k: v.to(cuda_device) for k, v in T._train_batch(ref_cfg, 8, 23, seed=5).items()}
-        ops.CONV_BACKEND["operands"] = one.precision
-        try:
+        with ops.mode(operands=one.precision):
             one.forward_backward(_fs2_shard(full, rank, 4))
-        finally:
-            ops.CONV_BACKEND["operands"] = "f32"
         local.append(one.params.grad.double().cpu())
         clip = one.training.gradient_clip_val
     mean = (local[0] + local[1]) / 2

@@ -29,24 +29,23 @@ def _run_d_step(tr, d, audio, dl_seed, chain):
     from everyvoice_amd.train import ops
 
     H._DISC_CHAIN = chain
-    ops.CONV_BACKEND["operands"] = "bf16"
     try:
-        tr.d_params.zero_grad()
-        for layer in d.layers():
-            layer.frozen = False
-        tr._materialize(d.layers())
-        tape = ag.Tape()
-        tr._bucket_hook(tape, tr.d_params, d.layers(), None)
-        out, fm = d.forward(tape, ag.Var(audio, needs_grad=False))
-        g = torch.Generator(device="cpu").manual_seed(dl_seed)
-        out.grad = (torch.randn(out.data.shape, generator=g) / out.data.numel()).to(audio.device)
-        tape.backward()
-        torch.cuda.synchronize()
-        names = [n for layer in d.layers() for n in layer.param_names()]
-        grads = {n: tr.d_params.gradients()[n].clone() for n in names}
-        return out.data.clone(), grads
+        with ops.mode(operands="bf16"):
+            tr.d_params.zero_grad()
+            for layer in d.layers():
+                layer.frozen = False
+            tr._materialize(d.layers())
+            tape = ag.Tape()
+            tr._bucket_hook(tape, tr.d_params, d.layers(), None)
+            out, fm = d.forward(tape, ag.Var(audio, needs_grad=False))
+            g = torch.Generator(device="cpu").manual_seed(dl_seed)
+            out.grad = (torch.randn(out.data.shape, generator=g) / out.data.numel()).to(audio.device)
+            tape.backward()
+            torch.cuda.synchronize()
+            names = [n for layer in d.layers() for n in layer.param_names()]
+            grads = {n: tr.d_params.gradients()[n].clone() for n in names}
+            return out.data.clone(), grads
     finally:
-        ops.CONV_BACKEND["operands"] = "f32"
         H._DISC_CHAIN = True
 
 
@@ -105,22 +104,21 @@ def _run_g_step(tr, i, d, y, y_hat, chain):
     from everyvoice_amd.train import ops
 
     H._DISC_CHAIN = chain
-    ops.CONV_BACKEND["operands"] = "bf16"
     try:
-        for layer in d.layers():
-            layer.frozen = True
-        tr._materialize(d.layers())
-        ops.fill_(tr._slots, 0.0)
-        tape = ag.Tape()
-        xf = ag.Var(y_hat)
-        real = d.forward(tape, ag.Var(y, needs_grad=False), role="g_real")
-        fake = d.forward(tape, xf, role="g_fake")
-        tr._g_losses(i, real, fake)
-        tape.backward()
-        torch.cuda.synchronize()
-        return tr._slots[:, i].clone(), xf.grad.clone()
+        with ops.mode(operands="bf16"):
+            for layer in d.layers():
+                layer.frozen = True
+            tr._materialize(d.layers())
+            ops.fill_(tr._slots, 0.0)
+            tape = ag.Tape()
+            xf = ag.Var(y_hat)
+            real = d.forward(tape, ag.Var(y, needs_grad=False), role="g_real")
+            fake = d.forward(tape, xf, role="g_fake")
+            tr._g_losses(i, real, fake)
+            tape.backward()
+            torch.cuda.synchronize()
+            return tr._slots[:, i].clone(), xf.grad.clone()
     finally:
-        ops.CONV_BACKEND["operands"] = "f32"
         H._DISC_CHAIN = True
         for layer in d.layers():
             layer.frozen = False
@@ -144,21 +142,20 @@ def test_generator_step_on_one_real_and_generated_batch_equals_two_passes(which)
     for _ in range(int(which[3]) if which.startswith("msd") else 0):
         y, y_hat = ops.avgpool4s2(y), ops.avgpool4s2(y_hat)
     want_slots, want_dx = _run_g_step(tr, i, d, y, y_hat, chain=True)
-    ops.CONV_BACKEND["operands"] = "bf16"
     try:
-        for layer in d.layers():
-            layer.frozen = True
-        tr._materialize(d.layers())
-        ops.fill_(tr._slots, 0.0)
-        tape = ag.Tape()
-        both = ag.Var(torch.cat([y, y_hat], 1).contiguous())
-        res = d.forward(tape, both, role="g_both", grad_from=B)
-        tr._g_losses(i, None, res)
-        tape.backward()
-        torch.cuda.synchronize()
-        got_slots, got_dx = tr._slots[:, i].clone(), both.grad.clone()
+        with ops.mode(operands="bf16"):
+            for layer in d.layers():
+                layer.frozen = True
+            tr._materialize(d.layers())
+            ops.fill_(tr._slots, 0.0)
+            tape = ag.Tape()
+            both = ag.Var(torch.cat([y, y_hat], 1).contiguous())
+            res = d.forward(tape, both, role="g_both", grad_from=B)
+            tr._g_losses(i, None, res)
+            tape.backward()
+            torch.cuda.synchronize()
+            got_slots, got_dx = tr._slots[:, i].clone(), both.grad.clone()
     finally:
-        ops.CONV_BACKEND["operands"] = "f32"
         for layer in d.layers():
             layer.frozen = False
     assert float(got_dx[:, :B].abs().max()) == 0.0  # nothing flows into the real half
@@ -349,37 +346,36 @@ def test_chain_against_torch_autograd_with_its_roundings(which, n, T, generator_
     y = 0.5 * torch.tanh(torch.randn(n, T, generator=g))
     y_real = 0.5 * torch.tanh(torch.randn(n, T, generator=g))
     layers = d.layers()
-    ops.CONV_BACKEND["operands"] = "bf16"
     try:
-        tr.d_params.zero_grad()
-        for layer in layers:
-            layer.frozen = generator_step
-            ops.fill_(layer._dw, 0.0)
-        tr._materialize(layers)
-        ops.fill_(tr._slots, 0.0)
-        tape = ag.Tape()
-        xf = ag.Var(y.view(1, n, T).cuda(), needs_grad=generator_step)
-        if generator_step:
-            real = d.forward(tape, ag.Var(y_real.view(1, n, T).cuda(), needs_grad=False), role="g_real")
-            fake = d.forward(tape, xf, role="g_fake")
-            tr._g_losses(i_d, real, fake)
-            out = fake[0]
-        else:
-            out, _ = d.forward(tape, xf, role="pair")
-            out.grad = (torch.randn(out.data.shape, generator=g) / out.data.numel()).cuda()
-        assert d._chain.ok and d._chain._cfgs, "the chain did not run"
-        dl = out.grad.clone()
-        tape.backward()
-        torch.cuda.synchronize()
-        ws = [layer._w.detach().cpu().clone().requires_grad_(True) for layer in layers]
-        bs = [layer.bias_data().detach().cpu().clone().requires_grad_(True) for layer in layers]
-        got_logits = out.data.cpu()[0]
-        got_dw = [layer._dw.cpu().clone() for layer in layers]
-        got_db = [tr.d_params.gradients()[layer.name + ".bias"].cpu().clone() for layer in layers]
-        got_dx = xf.grad.cpu()[0] if generator_step else None
-        slots = tr._slots[:, i_d].cpu()
+        with ops.mode(operands="bf16"):
+            tr.d_params.zero_grad()
+            for layer in layers:
+                layer.frozen = generator_step
+                ops.fill_(layer._dw, 0.0)
+            tr._materialize(layers)
+            ops.fill_(tr._slots, 0.0)
+            tape = ag.Tape()
+            xf = ag.Var(y.view(1, n, T).cuda(), needs_grad=generator_step)
+            if generator_step:
+                real = d.forward(tape, ag.Var(y_real.view(1, n, T).cuda(), needs_grad=False), role="g_real")
+                fake = d.forward(tape, xf, role="g_fake")
+                tr._g_losses(i_d, real, fake)
+                out = fake[0]
+            else:
+                out, _ = d.forward(tape, xf, role="pair")
+                out.grad = (torch.randn(out.data.shape, generator=g) / out.data.numel()).cuda()
+            assert d._chain.ok and d._chain._cfgs, "the chain did not run"
+            dl = out.grad.clone()
+            tape.backward()
+            torch.cuda.synchronize()
+            ws = [layer._w.detach().cpu().clone().requires_grad_(True) for layer in layers]
+            bs = [layer.bias_data().detach().cpu().clone().requires_grad_(True) for layer in layers]
+            got_logits = out.data.cpu()[0]
+            got_dw = [layer._dw.cpu().clone() for layer in layers]
+            got_db = [tr.d_params.gradients()[layer.name + ".bias"].cpu().clone() for layer in layers]
+            got_dx = xf.grad.cpu()[0] if generator_step else None
+            slots = tr._slots[:, i_d].cpu()
     finally:
-        ops.CONV_BACKEND["operands"] = "f32"
         for layer in layers:
             layer.frozen = False
     # torch side

@@ -174,13 +174,10 @@ def test_attention_training_bf16_operands(cuda_device, D, H, B, T, p):
     do = torch.randn(B, D, T, generator=g)
     o.backward(do)
     x, lens32 = _cbt(qkv.detach()).to(dev), lens.to(dev, torch.int32)
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         out, saved = ops.attention_train_fwd(x, lens32, H, p, seed=7)
         dqkv = ops.attention_train_bwd(x, saved, _cbt(do).to(dev), H, p, seed=7)
         again = ops.attention_train_bwd(x, saved, _cbt(do).to(dev), H, p, seed=7)
-    finally:
-        ops.CONV_BACKEND["operands"] = "f32"
     assert torch.equal(dqkv, again)
     _close(out.cpu().permute(1, 0, 2), o.detach(), 1e-2)
     got = dqkv.cpu().permute(1, 0, 2)
@@ -333,11 +330,8 @@ def test_training_step_bf16_operands_follow_the_exact_step(cuda_device):
         from everyvoice_amd.train import ops
 
         tr = _trainer(ref_cfg, cuda_device, precision=prec)
-        ops.CONV_BACKEND["operands"] = prec  # what training_step does around forward_backward
-        try:
+        with ops.mode(operands=prec):  # what training_step does around forward_backward
             losses = tr.forward_backward(batch)
-        finally:
-            ops.CONV_BACKEND["operands"] = "f32"
         out[prec] = ({k: float(v) for k, v in losses.items()}, tr.params.grad.clone())
     for k, v in out["f32"][0].items():
         assert out["bf16"][0][k] == pytest.approx(v, rel=2e-2, abs=1e-4), k
@@ -447,11 +441,8 @@ def test_training_step_default_model_size_bf16_follows_oracle(cuda_device):
     ref = _oracle_from(tr, ref_cfg)
     want = training_losses_ref(ref, batch)
     want["total"].backward()
-    ops.CONV_BACKEND["operands"] = "bf16"  # what training_step does around forward_backward
-    try:
+    with ops.mode(operands="bf16"):  # what training_step does around forward_backward
         got = tr.forward_backward(batch)
-    finally:
-        ops.CONV_BACKEND["operands"] = "f32"
     for k, v in want.items():
         assert float(got[k]) == pytest.approx(float(v), rel=2e-2, abs=1e-4), k
     grads = tr.params.gradients()
@@ -513,11 +504,8 @@ def test_training_step_at_the_bench_shape_bf16_follows_fp32(cuda_device):
     out = {}
     for prec in ("f32", "bf16"):
         tr = _trainer(ref_cfg, cuda_device, precision=prec)
-        ops.CONV_BACKEND["operands"] = prec  # what training_step does around forward_backward
-        try:
+        with ops.mode(operands=prec):  # what training_step does around forward_backward
             losses = tr.forward_backward(batch)
-        finally:
-            ops.CONV_BACKEND["operands"] = "f32"
         out[prec] = ({k: float(v) for k, v in losses.items()}, {k: v.clone() for k, v in tr.params.gradients().items()}, tr.params.grad.clone())
         del tr
     for k, v in out["f32"][0].items():
@@ -546,11 +534,8 @@ def test_training_step_bench_slice_bf16_follows_oracle(cuda_device):
     ref = _oracle_from(tr, ref_cfg)
     want = training_losses_ref(ref, batch)
     want["total"].backward()
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         got = tr.forward_backward(batch)
-    finally:
-        ops.CONV_BACKEND["operands"] = "f32"
     for k, v in want.items():
         assert float(got[k]) == pytest.approx(float(v), rel=2e-2, abs=1e-4), k
     grads = tr.params.gradients()
@@ -577,11 +562,8 @@ def test_training_step_at_the_bench_batch_follows_oracle(cuda_device, prec):
     ref = _oracle_from(tr, ref_cfg)
     want = training_losses_ref(ref, batch)
     want["total"].backward()
-    ops.CONV_BACKEND["operands"] = prec
-    try:
+    with ops.mode(operands=prec):
         got = tr.forward_backward(batch)
-    finally:
-        ops.CONV_BACKEND["operands"] = "f32"
     for k, v in want.items():
         assert float(got[k]) == pytest.approx(float(v), rel=2e-4 if prec == "f32" else 2e-2, abs=1e-5 if prec == "f32" else 1e-4), k
     grads = tr.params.gradients()
@@ -614,9 +596,7 @@ def test_feed_forward_middle_fused_into_the_packs_equals_the_separate_passes(cud
     w2 = (torch.randn(D, F_, 1, generator=g) * F_ ** -0.5).to(cuda_device)
     b1, b2 = torch.randn(F_, generator=g).to(cuda_device) * 0.1, torch.randn(D, generator=g).to(cuda_device) * 0.1
     dy = torch.randn(D, B, T, generator=g).to(cuda_device)
-    prev = ops.CONV_BACKEND["operands"]
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         assert ops.ffn_fused_supported(B, T, F_, D)
         k1, k2 = {}, {}
         a = ops.conv1d_fwd(h, w1, b1, 1, 0, 1, 1, keep=k1)
@@ -635,8 +615,6 @@ def test_feed_forward_middle_fused_into_the_packs_equals_the_separate_passes(cud
         dh_f = ops.conv1d_bwd_silu_dropout_dy(h, w1, ds_f, a_f, p, seed, ew1, eb1, f1)
         ops.wgrad_join(cuda_device)
         torch.cuda.synchronize()
-    finally:
-        ops.CONV_BACKEND["operands"] = prev
     rel = lambda got, want: float((got - want).abs().max() / want.abs().max())  # noqa: E731
     assert float((s == 0).float().mean()) == pytest.approx(p, abs=0.01)  # (the mask is there)
     for name, got, want, tol in (("y", y_f, y, 2e-6), ("ds", ds_f, ds, 2e-6), ("dh", dh_f, dh, 2e-6), ("dw2", ew2, dw2, 2e-6), ("dw1", ew1, dw1, 2e-5),
@@ -660,9 +638,7 @@ def test_residual_add_and_dropout_in_the_dense_layers_epilogue_equal_the_separat
     w = (torch.randn(cout, cin, 1, generator=g) * cin ** -0.5).to(cuda_device)
     b = (torch.randn(cout, generator=g) * 0.1).to(cuda_device)
     dy = torch.randn(cout, B, T, generator=g).to(cuda_device)
-    prev = ops.CONV_BACKEND["operands"]
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         assert ops.resdrop_fused_supported(B, T, cin, cout)
         k1, k2 = {}, {}
         z = ops.conv1d_fwd(h, w, b, 1, 0, 1, 1, keep=k1)
@@ -675,8 +651,6 @@ def test_residual_add_and_dropout_in_the_dense_layers_epilogue_equal_the_separat
         keep = (ops.dropout(torch.ones(cout * B * T, device=cuda_device), p, seed) > 0).float().view(cout, B * T).cpu()
         ops.wgrad_join(cuda_device)
         torch.cuda.synchronize()
-    finally:
-        ops.CONV_BACKEND["operands"] = prev
     rel = lambda got, want: float((got - want).abs().max() / want.abs().max())  # noqa: E731
     for name, got, want, tol in (("y", y_f, y, 2e-6), ("dh", dh_f, dh, 2e-6), ("dw", ew, dw, 2e-6), ("db", eb, db, 2e-3)):
         assert rel(got, want) <= tol, (name, rel(got, want))
@@ -711,9 +685,7 @@ def test_fused_feed_forward_block_against_torch_with_the_kernels_own_mask(cuda_d
     dy = torch.randn(D, B, T, generator=g)
     dev = cuda_device
     bf = lambda t: t.to(torch.bfloat16).to(torch.float32)  # noqa: E731
-    prev = ops.CONV_BACKEND["operands"]
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         assert ops.ffn_fused_supported(B, T, F_, D) and ops.ln_dense_fused_supported(B, T, D, F_)
         xd, w1d, w2d = x.to(dev), w1.to(dev), w2.to(dev)
         gd, bd = gamma.to(dev), beta.to(dev)
@@ -728,8 +700,6 @@ def test_fused_feed_forward_block_against_torch_with_the_kernels_own_mask(cuda_d
         dx = ops.layernorm_bwd(xd, gd, dh, dgam, dbet)
         ops.wgrad_join(dev)
         torch.cuda.synchronize()
-    finally:
-        ops.CONV_BACKEND["operands"] = prev
     assert float(keep.mean()) == pytest.approx(1 - p, abs=0.005)
     # ---- torch, with the rounding points of the packed path
     N = B * T
@@ -780,9 +750,7 @@ def test_feed_forward_block_as_a_packed_chain_against_torch_with_the_kernels_own
     dy = torch.randn(D, B, T, generator=g)
     dev = cuda_device
     bf = lambda t: t.to(torch.bfloat16).to(torch.float32)  # noqa: E731
-    prev = ops.CONV_BACKEND["operands"]
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         assert ops.ffn_packed_supported(B, T, D, F_, D)
         xd, w1d, w2d = x.to(dev), w1.to(dev), w2.to(dev)
         gd, bd = gamma.to(dev), beta.to(dev)
@@ -797,8 +765,6 @@ def test_feed_forward_block_as_a_packed_chain_against_torch_with_the_kernels_own
         ops.wgrad_join(dev)
         torch.cuda.synchronize()
         a_pk = kp["a_pk"].view(torch.bfloat16).view(F_ // 8, ops.pk_pitch(B, T), 8)[:, : B * T].permute(0, 2, 1).reshape(F_, B * T).float().cpu()
-    finally:
-        ops.CONV_BACKEND["operands"] = prev
     N = B * T
     xm = x.view(D, N)
     mu, var = xm.mean(0, keepdim=True), xm.var(0, unbiased=False, keepdim=True)
@@ -828,6 +794,84 @@ def test_feed_forward_block_as_a_packed_chain_against_torch_with_the_kernels_own
         assert l2 <= 1e-3 and mx <= 1e-2, (name, l2, mx)
 
 
+@pytest.mark.parametrize("B,T", [(2, 32), (1, 77)])  # (one 64-column item on split-K launches; a row pitch rounded up to 128 with a zero tail)
+def test_ffn_core_tiers_issue_the_operator_sequences_they_stand_for(cuda_device, B, T):
+    """train/fs2.py: ffn_core on a Tape, in each of its tiers -- (a) the packed chain (default switches, res = x), (b) FFN_PACKED off: the
+    fused middle with the residual and the dropout in the second layer's epilogue, (c) RESDROP_FUSION off as well: the residual as an
+    operator of its own, (d) res = None -- against the explicit ops.* call sequence the tier stands for, written out here on the same
+    seeds: the same kernels on the same arguments in the same order per buffer, so the output, x.grad and the six parameter gradients
+    are compared with torch.equal (what test_weight_gradient_schedules_give_the_same_step relies on)."""
+    from everyvoice_amd.train import fs2 as tfs2, ops
+    from everyvoice_amd.train.autograd import Tape, Var
+    from everyvoice_amd.train.layers import ParamGroup
+
+    D, F_, p, seed, seed_out, sb = 256, 1024, 0.2, 4321, 977, 0.5
+    N = B * T
+    dev = cuda_device
+    g = torch.Generator().manual_seed(23 + B)
+    x0 = (torch.randn(D, B, T, generator=g) * 1.3 + 0.2).to(dev)
+    dy0 = torch.randn(D, B, T, generator=g).to(dev)
+    values = {"ln.weight": torch.rand(D, generator=g) + 0.5, "ln.bias": torch.randn(D, generator=g) * 0.1,
+              "l1.weight": torch.randn(F_, D, 1, generator=g) * D ** -0.5, "l1.bias": torch.randn(F_, generator=g) * 0.1,
+              "l2.weight": torch.randn(D, F_, 1, generator=g) * F_ ** -0.5, "l2.bias": torch.randn(D, generator=g) * 0.1}
+    names = list(values)
+    gam, bet, w1, b1, w2, b2 = (values[n].to(dev) for n in names)
+
+    def on_tape(with_res):
+        grp = ParamGroup(dev)
+        ln = tfs2.Affine(grp, "ln", D)
+        l1, l2 = tfs2.Dense(grp, "l1.weight", "l1.bias", D, F_), tfs2.Dense(grp, "l2.weight", "l2.bias", F_, D)
+        grp.finalize()
+        for n, v in values.items():
+            grp.load(n, v)
+        tape, x = Tape(), Var(x0.clone())
+        y = tfs2.ffn_core(tape, x, ln, l1, l2, p, seed, res=x if with_res else None, seed_out=seed_out, sb=sb)
+        y.grad = dy0.clone()
+        tape.backward()
+        return [y.data, x.grad] + [grp.gradients()[n] for n in names]
+
+    def by_hand(tier):
+        x, dy = x0.clone(), dy0.clone()
+        xr, dyr = x.view(D, 1, N), dy.view(D, 1, N)  # (position-wise layers see all columns as one item: train/fs2.py _row)
+        dgam, dbet, dw1, db1, dw2, db2 = (torch.zeros_like(t) for t in (gam, bet, w1, b1, w2, b2))
+        k1, k2 = {}, {}
+        if tier == "a":
+            y = ops.ffn_packed_fwd(xr, gam, bet, w1, b1, w2, b2, xr, p, seed, seed_out, sb, k1)
+            dh = ops.ffn_packed_bwd(xr, w1, w2, dyr, p, seed, seed_out, sb, dw1, db1, dw2, db2, k1)
+        else:
+            a = ops.layernorm_dense_fwd(xr, gam, bet, w1, b1, k1)
+            if tier == "b":
+                y = ops.conv1d_fwd_resdrop(a, w2, b2, xr, p, seed_out, sb, k2, in_p=p, in_seed=seed)
+                ds = ops.conv1d_bwd_dropout_dy(a, w2, dyr, p, seed_out, sb, dw2, db2, k2, x_standin=True)
+            else:
+                y = ops.conv1d_fwd_silu_dropout(a, w2, b2, p, seed, k2)
+                dz = dyr
+                if tier == "c":
+                    y = ops.dropout_fused(1, y, x, p, seed_out, sb)
+                    dz = ops.dropout_fused(4, dy, None, p, seed_out, sb).view(D, 1, N)
+                ds, _, _ = ops.conv1d_bwd(a, w2, dz, 1, 0, 1, 1, need_dx=True, dw_out=dw2, db_out=db2, accumulate=True, packed=k2, x_standin=True)
+            dh = ops.conv1d_bwd_silu_dropout_dy(xr, w1, ds, a, p, seed, dw1, db1, k1)
+        # LayerNorm's backward adds into the gradient the residual path left in x (dy itself); without a residual it is x's gradient
+        dx = ops.layernorm_bwd(x, gam, dh.view(D, B, T), dgam, dbet, acc_into=None if tier == "d" else dy)
+        ops.wgrad_join(dev)
+        return [y, dx, dgam, dbet, dw1, db1, dw2, db2]
+
+    switches = ops.FFN_PACKED[0], ops.RESDROP_FUSION[0]
+    try:
+        with ops.mode(operands="bf16"):
+            assert ops.ffn_packed_supported(B, T, D, F_, D) and ops.ffn_packed_supported(1, N, D, F_, D)
+            for tier, ffn_packed, resdrop in (("a", True, True), ("b", False, True), ("c", False, False), ("d", True, True)):
+                ops.FFN_PACKED[0], ops.RESDROP_FUSION[0] = ffn_packed, resdrop
+                got, want = on_tape(tier != "d"), by_hand(tier)
+                torch.cuda.synchronize()
+                for name, a_, b_ in zip(["y", "x.grad"] + names, got, want):
+                    assert a_.numel() == b_.numel() and torch.equal(a_.reshape(-1), b_.reshape(-1)), (tier, name, float((a_.reshape(-1) - b_.reshape(-1)).abs().max()))
+    finally:
+        ops.FFN_PACKED[0], ops.RESDROP_FUSION[0] = switches
+        ops.wgrad_join(dev)
+        torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("B,T,C,F_", [(4, 112, 256, 1024), (32, 814, 256, 768), (8, 64, 128, 256), (1, 4513, 256, 1024)])
 def test_layernorm_written_as_the_packed_input_of_the_dense_layer_behind_it(cuda_device, B, T, C, F_):
     """ops.layernorm_dense_fwd (train/fs2.py: ln_dense, ffn_core): LayerNorm -> pointwise layer with the normalised tensor written
@@ -841,9 +885,7 @@ def test_layernorm_written_as_the_packed_input_of_the_dense_layer_behind_it(cuda
     w = (torch.randn(F_, C, 1, generator=g) * C ** -0.5).to(cuda_device)
     b = (torch.randn(F_, generator=g) * 0.1).to(cuda_device)
     dy = torch.randn(F_, B, T, generator=g).to(cuda_device)
-    prev = ops.CONV_BACKEND["operands"]
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         assert ops.ln_dense_fused_supported(B, T, C, F_)
         k1, k2 = {}, {}
         h = ops.layernorm(x, gamma, beta)
@@ -854,8 +896,6 @@ def test_layernorm_written_as_the_packed_input_of_the_dense_layer_behind_it(cuda
         dh_f, _, _ = ops.conv1d_bwd(x, w, dy, 1, 0, 1, 1, need_dx=True, dw_out=ew, db_out=eb, accumulate=True, packed=k2)
         ops.wgrad_join(cuda_device)
         torch.cuda.synchronize()
-    finally:
-        ops.CONV_BACKEND["operands"] = prev
     rel = lambda got, want: float((got - want).abs().max() / want.abs().max())  # noqa: E731
     for name, got, want in (("y", y_f, y), ("dh", dh_f, dh), ("dw", ew, dw), ("db", eb, db)):
         assert rel(got, want) <= 2e-6, (name, rel(got, want))
@@ -1141,12 +1181,8 @@ def test_weight_gradient_schedules_give_the_same_step(cuda_device, use_graph):
     ref_cfg = _ref_cfg(0.1, 0)
     # (T = 64: B * T a multiple of 64, so the decoder's feed-forward blocks take the fused form of ffn_core under every schedule too)
     batches = [_shaped_batch(ref_cfg, seed, True, cuda_device, T=64) for seed in (5, 6)]
-    prev_ops = ops.CONV_BACKEND["operands"]
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         assert ops.ffn_fused_supported(4, 64, ref_cfg.decoder.feedforward_dim, ref_cfg.decoder.input_dim)
-    finally:
-        ops.CONV_BACKEND["operands"] = prev_ops
     prev = ops.SIDE_GROUP[0]
     finals = []
     try:

@@ -326,11 +326,8 @@ def test_bf16_precision_mode_with_the_module_follows_the_exact_step(cuda_device)
     out = {}
     for prec in ("f32", "bf16"):
         tr = _gst_trainer(ref_cfg, cuda_device, precision=prec)
-        ops.CONV_BACKEND["operands"] = prec  # what training_step does around forward_backward
-        try:
+        with ops.mode(operands=prec):  # what training_step does around forward_backward
             losses = tr.forward_backward(batch)
-        finally:
-            ops.CONV_BACKEND["operands"] = "f32"
         out[prec] = ({k: float(v) for k, v in losses.items()}, tr.params.grad.clone())
     for k, v in out["f32"][0].items():
         assert out["bf16"][0][k] == pytest.approx(v, rel=2e-2, abs=1e-4), k

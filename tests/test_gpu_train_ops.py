@@ -297,9 +297,8 @@ def _bf(t):
 def bf16_operands():
     from everyvoice_amd.train import ops
 
-    ops.CONV_BACKEND["operands"] = "bf16"
-    yield
-    ops.CONV_BACKEND["operands"] = "f32"
+    with ops.mode(operands="bf16"):
+        yield
 
 
 @pytest.mark.parametrize("c", MFMA_CONVS)

@@ -147,15 +147,12 @@ def test_mrf_stage_forward_backward_against_torch_autograd(cuda_device, C, T):
     tape = ag.Tape()
     xv = ag.Var(x.to(cuda_device))
     grp.zero_grad()
-    ops.CONV_BACKEND["operands"] = "bf16"
-    try:
+    with ops.mode(operands="bf16"):
         out = st.apply(tape, xv)
         out.grad = dout.to(cuda_device)
         tape.backward()
         for layer in layers:
             layer.finish_grads()
-    finally:
-        ops.CONV_BACKEND["operands"] = "f32"
     # torch: the same network on the effective weights (rounded to bf16, as the kernels read them), fp32 activations
     xt = x.permute(1, 0, 2).clone().requires_grad_()
     ws = {}
