@@ -166,6 +166,42 @@ def _fold_bn(w, b, sd, prefix):
     return w * s.view(-1, *([1] * (w.dim() - 1))), (b - sd[prefix + ".running_mean"].float()) * s + sd[prefix + ".bias"].float()
 
 
+def variance_settings(c: "FastSpeech2ModelConfig") -> dict:
+    """The three settings of the schema that choose an axis or a loss, validated and as plain strings:
+    ``{"level": {"duration", "pitch", "energy"}, "loss": {"duration", "pitch", "energy", "mel"}}``.  ``level``: "phone" (the predictor and its
+    bucket embedding on the symbol axis, in front of the length regulator) or "frame" (on the frame axis, behind it; durations exist on the
+    symbol axis only, so ``duration.level`` is checked against the schema and has no effect); ``loss``: "mse" or "mae" (``mel`` = ``mel_loss``, for
+    the mel and the postnet terms).  Enum objects are taken by their ``.value``; anything else raises ``ValueError``.  The configuration
+    itself is not touched: ``apply_variance_settings`` is what a constructor calls."""
+    vp = c.variance_predictors
+    out = {"level": {}, "loss": {}}
+    for name in ("duration", "pitch", "energy"):
+        cfg = getattr(vp, name)
+        level, loss = getattr(cfg.level, "value", cfg.level), getattr(cfg.loss, "value", cfg.loss)
+        if level not in ("phone", "frame"):
+            raise ValueError(f"model.variance_predictors.{name}.level: 'phone' or 'frame', got {level!r}")
+        if loss not in ("mse", "mae"):
+            raise ValueError(f"model.variance_predictors.{name}.loss: 'mse' or 'mae', got {loss!r}")
+        out["level"][name], out["loss"][name] = level, loss
+    mel_loss = getattr(c.mel_loss, "value", c.mel_loss)
+    if mel_loss not in ("mse", "mae"):
+        raise ValueError(f"model.mel_loss: 'mse' or 'mae', got {mel_loss!r}")
+    out["loss"]["mel"] = mel_loss
+    return out
+
+
+def apply_variance_settings(c: "FastSpeech2ModelConfig") -> dict:
+    """``variance_settings(c)``, refusing a value outside the schema where the configuration is read (not inside the first step), with
+    the plain strings written back into ``c``: the hyper-parameters of a checkpoint are JSON only, and a configuration may arrive
+    holding enum objects.  What the model, the trainer and ``lightning.FastSpeech2Config`` call when they take a configuration over."""
+    out = variance_settings(c)
+    for name in ("duration", "pitch", "energy"):
+        cfg = getattr(c.variance_predictors, name)
+        cfg.level, cfg.loss = out["level"][name], out["loss"][name]
+    c.mel_loss = out["loss"]["mel"]
+    return out
+
+
 def gst_state_dict_shapes(c: "FastSpeech2ModelConfig") -> dict:
     """THE key-name table of the Global Style Token module: every tensor of its state dict except ``num_batches_tracked`` (which the
     trainer adds for each ``bns.{i}``), in declaration order.  The module lives in the absent FastSpeech2_lightning submodule, so the
@@ -324,7 +360,11 @@ class _VariancePredictor:
 
 
 class FastSpeech2:
-    """``model = FastSpeech2(config, stats); model.load_state_dict(sd); mel, post, durations, pitch, energy, mel_lens = model(ids, lens)``"""
+    """``model = FastSpeech2(config, stats); model.load_state_dict(sd); mel, post, durations, pitch, energy, mel_lens = model(ids, lens)``
+
+    ``variance_predictors.{pitch,energy}.level`` places each predictor and its bucket embedding: "phone" = on the symbol axis in front
+    of the length regulator, "frame" = on the frame axis behind it (pitch, then energy, on either axis; the positional term of the
+    decoder comes after both).  A frame-level predictor returns its values as [B, T]."""
 
     def __init__(self, config: FastSpeech2ModelConfig | None = None, stats: Stats | None = None, device="cuda:0",
                  lang2id: dict | None = None, speaker2id: dict | None = None, precision: str = "f32"):
@@ -336,6 +376,7 @@ class FastSpeech2:
         self.device = torch.device(device)
         self.lang2id, self.speaker2id = lang2id or {}, speaker2id or {}
         self.audio_config = None  # the model's preprocessing.audio, where the caller knows it: the synthesis helpers make a style reference's mel with it
+        self.levels = apply_variance_settings(self.config)["level"]
         if self.config.use_global_style_token_module:
             gst_state_dict_shapes(self.config)  # (refuses a size the kernels are not built for here, not inside the first forward)
         if self.device.type != "cuda":
@@ -477,8 +518,9 @@ class FastSpeech2:
     def __call__(self, ids: torch.Tensor, lens: torch.Tensor, duration_control=1.0, pitch_control=1.0, energy_control=1.0,
                  durations: torch.Tensor | None = None, speakers: torch.Tensor | None = None, languages: torch.Tensor | None = None,
                  style_mel: torch.Tensor | None = None):
-        """ids [B, L] (0 = padding), lens [B] -> (mel [B, T, n_mels], postnet mel, durations [B, L], pitch [B, L],
-        energy [B, L], mel_lens [B]) on the device.  ``style_mel`` (a model with the Global Style Token module needs it, any other
+        """ids [B, L] (0 = padding), lens [B] -> (mel [B, T, n_mels], postnet mel, durations [B, L], pitch, energy, mel_lens [B]) on the
+        device.  ``pitch`` / ``energy`` (the predictions times their control, zero at padded positions) are [B, L] for a phone-level
+        predictor and [B, T] for a frame-level one (``variance_predictors.<name>.level``).  ``style_mel`` (a model with the Global Style Token module needs it, any other
         refuses it): the style reference's mel [B, Ts, n_mels], or [1, Ts, n_mels] for one reference serving the whole batch."""
         if not self._ready:
             raise RuntimeError("load_state_dict() or init_random() first")
@@ -527,13 +569,21 @@ class FastSpeech2:
             _chk(lib.evmi_fs2_add_item_embedding_f32(x.data_ptr(), rows.data_ptr(), lens32.data_ptr(), style.data_ptr(), B, L, D, _s(x)),
                  "evmi_fs2_add_item_embedding_f32")
         log_d = self.duration_predictor.forward(x, lens32)
-        pitch = self.pitch_predictor.forward(x, lens32)
         vp = c.variance_predictors
-        _chk(lib.evmi_fs2_bucket_embed_add_f32(x.data_ptr(), pitch.data_ptr(), self.pitch_bins.data_ptr(), self.pitch_table.data_ptr(),
-                                               vp.pitch.n_bins, B, L, D, float(pitch_control), _s(x)), "evmi_fs2_bucket_embed_add_f32")
-        energy = self.energy_predictor.forward(x, lens32)
-        _chk(lib.evmi_fs2_bucket_embed_add_f32(x.data_ptr(), energy.data_ptr(), self.energy_bins.data_ptr(), self.energy_table.data_ptr(),
-                                               vp.energy.n_bins, B, L, D, float(energy_control), _s(x)), "evmi_fs2_bucket_embed_add_f32")
+        variances = (("pitch", self.pitch_predictor, self.pitch_bins, self.pitch_table, vp.pitch.n_bins, pitch_control),
+                     ("energy", self.energy_predictor, self.energy_bins, self.energy_table, vp.energy.n_bins, energy_control))
+        out = {}
+
+        def adapt(level, h, h_lens, n):
+            """pitch, then energy, for the predictors of this level: predict on h [D, B, n], add the bucket embedding of prediction * control
+            in place (at padded positions too: the value there is 0, and the next predictor's k = 3 convolutions see those columns)"""
+            for name, pred, bins, table, n_bins, control in variances:
+                if self.levels[name] == level:
+                    out[name] = pred.forward(h, h_lens)
+                    _chk(lib.evmi_fs2_bucket_embed_add_f32(h.data_ptr(), out[name].data_ptr(), bins.data_ptr(), table.data_ptr(), n_bins, B, n, D,
+                                                           float(control), _s(h)), "evmi_fs2_bucket_embed_add_f32")
+
+        adapt("phone", x, lens32, L)
         if durations is None:
             dur = torch.empty(B, L, device=dev, dtype=torch.int32)
             _chk(lib.evmi_fs2_durations_i32(log_d.data_ptr(), lens32.data_ptr(), dur.data_ptr(), B, L, float(duration_control), _s(x)),
@@ -543,11 +593,13 @@ class FastSpeech2:
             dur = durations.to(dev, torch.int32).clamp_min(0).masked_fill(pad, 0).contiguous()
         cum = torch.cumsum(dur, 1, dtype=torch.int32).contiguous()
         mel_lens = cum[:, -1].contiguous()
-        T = int(mel_lens.max())  # the one host sync of the forward: the output length
+        T = int(mel_lens.max())  # the one host sync of the forward: the output length (in front of every frame-level predictor)
         if T <= 0:
             raise ValueError("all predicted durations are zero")
         frames = torch.empty(D, B, T, device=dev, dtype=torch.float32)
         _chk(lib.evmi_length_regulate_cbt_f32(x.data_ptr(), cum.data_ptr(), frames.data_ptr(), D, B, L, T, _s(x)), "evmi_length_regulate_cbt_f32")
+        adapt("frame", frames, mel_lens, T)
+        pitch, energy = out["pitch"], out["energy"]
         _chk(lib.evmi_fs2_add_posemb_f32(frames.data_ptr(), mel_lens.data_ptr(), self.inv_freq.data_ptr(), B, T, D, _s(x)), "evmi_fs2_add_posemb_f32")
         y = self.decoder.forward(frames, mel_lens)
         mel = _conv(y, self.w_mel, self.b_mel)

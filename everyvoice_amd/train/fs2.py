@@ -7,12 +7,19 @@ contract without Lightning: ``training_step(batch) -> losses`` (forward in train
 all-reduce, clipping, Noam-scheduled AdamW), ``state_dict()`` with the state-dict names ``everyvoice_amd.fs2.FastSpeech2``
 loads, ``checkpoint()`` with ``model_info`` and JSON-only hyper-parameters (``everyvoice/tests/test_model.py:85-151``).
 
-Teacher forcing as FastSpeech2 trains: ground-truth durations drive the length regulator, ground-truth (phone-level) pitch
-and energy are bucketised into the embeddings, the predictors are regressed on them; loss weights are the reference's
+Teacher forcing as FastSpeech2 trains: ground-truth durations drive the length regulator, ground-truth pitch and energy are
+bucketised into the embeddings, the predictors are regressed on them; loss weights are the reference's
 ``FastSpeech2TrainingConfig`` defaults (``everyvoice/.schema/everyvoice-text-to-spec-0.5.json``: mel 1.0, postnet 1.0, pitch /
 energy / duration 0.1; optimiser ``noam``: lr 1e-3, betas (0.9, 0.999), eps 1e-8, weight decay 1e-6, warm-up 1000).
+``variance_predictors.{pitch,energy}.level`` places each predictor and its embedding: "phone" = on the symbol axis in front of
+the length regulator (targets [B, L]: given, or the per-frame values averaged over each symbol's frames), "frame" = on the frame
+axis behind it (targets ``pitch_frames`` / ``energy_frames`` [B, T] as they are); pitch comes before energy on either axis and
+the decoder's positional term after both.  ``variance_predictors.<name>.loss`` and ``mel_loss`` (mel and postnet terms) choose
+"mse" or "mae" per term (``mse_loss`` / ``mae_loss``).  Phone-level predictors and the duration predictor run on the side stream;
+frame-level predictors run on the main chain, in order; both axes share one bucket-table gradient kernel.
 Durations come from the dataset (``learn_alignment: false``) or from the alignment module's monotonic search
-(``everyvoice_amd.heavy.maximum_path``); the gradient of the alignment losses themselves is not part of this step yet.
+(``everyvoice_amd.heavy.maximum_path``); the alignment losses (CTC forward-sum, binarisation) are part of the step, and their
+gradient reaches the aligner's projections and the text embedding on a tape of its own beside the encoder's backward.
 
 Everything is channel-major fp32 ``x[c][b][t]``; no torch autograd and no torch math in the step.
 """
@@ -26,7 +33,7 @@ from dataclasses import asdict, dataclass, field
 import torch
 
 from .. import _lib
-from ..fs2 import N_PHONOLOGICAL_FEATURES, FastSpeech2ModelConfig, Stats
+from ..fs2 import N_PHONOLOGICAL_FEATURES, FastSpeech2ModelConfig, Stats, apply_variance_settings
 from . import ops
 from .autograd import _ACTIVATION_ELEMS, Tape, Var
 from .layers import ParamGroup, WNBatch, WNConv
@@ -521,6 +528,23 @@ def mse_loss(tape: Tape, pred: Var, target: torch.Tensor, count_dev: torch.Tenso
     return out
 
 
+def mae_loss(tape: Tape, pred: Var, target: torch.Tensor, count_dev: torch.Tensor, weight: float) -> torch.Tensor:
+    """weight * sum(|pred - target|) / count -> device scalar, beside ``mse_loss`` (same operands, same device count); the gradient is
+    weight * sign(pred - target) / count with sign(0) = 0 -- nothing where both operands are zero (the padded region)."""
+    out = torch.empty(1, device=pred.data.device, dtype=torch.float32)
+    ops.scalar_reduce(0, pred.data, target, out, scale=weight)
+    ops.elementwise(ops.EW_SCALE_DIV_SCALAR, out, c=count_dev, out=out, p0=1.0)
+
+    def bwd():
+        sign = ops.elementwise(ops.EW_SIGN_DIFF, pred.data, target, p0=weight)
+        pred.accumulate(ops.elementwise(ops.EW_SCALE_DIV_SCALAR, sign, c=count_dev, out=sign, p0=1.0))
+
+    tape.record(bwd)
+    return out
+
+
+_LOSS = {"mse": mse_loss, "mae": mae_loss}
+
 # ---- the model ---------------------------------------------------------------------------------------------------------
 class _ConformerT:
     def __init__(self, g: ParamGroup, cfg, prefix: str):
@@ -820,6 +844,8 @@ class FastSpeech2Trainer(CapturedStep):
         self._graph_init()
         self.last_step_was_graph = False
         self.config = c = config or FastSpeech2ModelConfig()
+        settings = apply_variance_settings(c)  # (refuses a level / loss outside the schema's values here, not inside the first step)
+        self.levels, self.loss_kinds = settings["level"], settings["loss"]
         self.stats = stats or Stats()
         self.training = training or FastSpeech2TrainingConfig()
         self.device = torch.device(device)
@@ -1025,7 +1051,11 @@ class FastSpeech2Trainer(CapturedStep):
         if learn and batch.get("attn_prior") is not None:
             d["attn_prior"] = fit(up(batch["attn_prior"], torch.float64), {1: Tp, 2: Lp}).contiguous()
         for key in ("pitch", "energy"):
-            if key in batch:
+            if self.levels[key] == "frame":
+                if batch.get(key + "_frames") is None:
+                    raise ValueError(f"variance_predictors.{key}.level is 'frame': the batch needs `{key}_frames` [B, T]")
+                d[key + "_frames"] = fit(up(batch[key + "_frames"], torch.float32), {1: Tp}).contiguous()
+            elif key in batch:
                 d[key] = fit(up(batch[key], torch.float32), {1: Lp}).contiguous()
             else:
                 d[key + "_frames"] = fit(up(batch[key + "_frames"], torch.float32), {1: Tp}).contiguous()
@@ -1214,8 +1244,13 @@ class FastSpeech2Trainer(CapturedStep):
             losses.update(align_losses)
         cum = torch.cumsum(dur, 1, dtype=torch.int32).contiguous()
         log_d_t = torch.log(dur.float() + 1.0).contiguous()
-        pitch_t = self._phone_level(batch, "pitch", cum, dur, pad, T)
-        energy_t = self._phone_level(batch, "energy", cum, dur, pad, T)
+        # variance targets: [B, L] for a phone-level predictor, the per-frame values [B, T] (zero past the item's frames) for a frame-level one
+        levels, kinds = self.levels, self.loss_kinds
+        target = {key: self._phone_level(batch, key, cum, dur, pad, T) if levels[key] == "phone"
+                  else ops.mask_cols_(batch[key + "_frames"].view(1, B, T).clone(), mel_lens).view(B, T) for key in ("pitch", "energy")}
+        variances = {"pitch": (self.pitch_predictor, self.pitch_bins, self.pitch_table, tr.pitch_loss_weight),
+                     "energy": (self.energy_predictor, self.energy_bins, self.energy_table, tr.energy_loss_weight)}
+        phone = [key for key in ("pitch", "energy") if levels[key] == "phone"]
 
         for table, key in ((self.speaker_table, "speakers"), (self.language_table, "languages")):
             if table is not None:
@@ -1237,59 +1272,86 @@ class FastSpeech2Trainer(CapturedStep):
             if data_parallel and on_stream:
                 dp_cut()  # backward: ... join_branch(xe, xa) | exchange of the tail bucket | aligner beside the encoder ...
             tape.record(lambda: join_branch(xe, xa))
-            x1 = self._add_bucket_embedding(tape, x, pitch_t, self.pitch_bins, self.pitch_table)
-            x1a = Var(x1.data)
-            _ACTIVATION_ELEMS[0] -= x1.data.numel()
-            tape.record(lambda: join_branch(x1, x1a))
             tp = pjoin["tape"]
+            # (duration, then the phone-level predictors in order; each on an alias of the tensor it reads: the encoder output, or that
+            # plus the embeddings of the phone-level predictors in front of it)
+            jobs = [("duration", self.duration_predictor, xa, log_d_t, w)]
 
             def predictors():
-                losses["duration"] = mse_loss(tp, self.duration_predictor.forward(tp, xa, lens, seeds), log_d_t.view(1, B, L), n_tok, w)
-                losses["pitch"] = mse_loss(tp, self.pitch_predictor.forward(tp, xa, lens, seeds), pitch_t.view(1, B, L), n_tok, tr.pitch_loss_weight)
-                losses["energy"] = mse_loss(tp, self.energy_predictor.forward(tp, x1a, lens, seeds), energy_t.view(1, B, L), n_tok, tr.energy_loss_weight)
+                for name, pred, alias, want, weight in jobs:
+                    losses[name] = _LOSS[kinds[name]](tp, pred.forward(tp, alias, lens, seeds), want.view(1, B, L), n_tok, weight)
 
-            if on_stream:
-                main = torch.cuda.current_stream(dev)
-                self._pred_fork.record(main)
-                self._pred_stream.wait_event(self._pred_fork)
-                with torch.cuda.stream(self._pred_stream):
+            def launch_predictors():
+                if on_stream:
+                    main = torch.cuda.current_stream(dev)
+                    self._pred_fork.record(main)
+                    self._pred_stream.wait_event(self._pred_fork)
+                    with torch.cuda.stream(self._pred_stream):
+                        predictors()
+                else:
                     predictors()
-            else:
-                predictors()
-            x = self._add_bucket_embedding(tape, x1, energy_t, self.energy_bins, self.energy_table)
+
+            if not phone:
+                launch_predictors()
+            alias = xa
+            for i, key in enumerate(phone):  # (the branch starts when its last input exists: in front of the last phone-level embedding)
+                pred, bins, table, weight = variances[key]
+                if alias is None:
+                    alias = Var(x.data)
+                    _ACTIVATION_ELEMS[0] -= x.data.numel()
+                    tape.record(lambda v=x, a=alias: join_branch(v, a))
+                jobs.append((key, pred, alias, target[key], weight))
+                if i == len(phone) - 1:
+                    launch_predictors()
+                x, alias = self._add_bucket_embedding(tape, x, target[key], bins, table), None
         else:
-            losses["duration"] = mse_loss(tape, self.duration_predictor.forward(tape, x, lens, seeds), log_d_t.view(1, B, L), n_tok, w)
-            losses["pitch"] = mse_loss(tape, self.pitch_predictor.forward(tape, x, lens, seeds), pitch_t.view(1, B, L), n_tok, tr.pitch_loss_weight)
-            x = self._add_bucket_embedding(tape, x, pitch_t, self.pitch_bins, self.pitch_table)
-            losses["energy"] = mse_loss(tape, self.energy_predictor.forward(tape, x, lens, seeds), energy_t.view(1, B, L), n_tok, tr.energy_loss_weight)
-            x = self._add_bucket_embedding(tape, x, energy_t, self.energy_bins, self.energy_table)
+            losses["duration"] = _LOSS[kinds["duration"]](tape, self.duration_predictor.forward(tape, x, lens, seeds), log_d_t.view(1, B, L), n_tok, w)
+            for key in phone:
+                pred, bins, table, weight = variances[key]
+                losses[key] = _LOSS[kinds[key]](tape, pred.forward(tape, x, lens, seeds), target[key].view(1, B, L), n_tok, weight)
+                x = self._add_bucket_embedding(tape, x, target[key], bins, table)
 
         frames = torch.empty(D, B, T, device=dev, dtype=torch.float32)
         _chk(lib.evmi_length_regulate_cbt_f32(x.data.data_ptr(), cum.data_ptr(), frames.data_ptr(), D, B, L, T, _s(frames)), "evmi_length_regulate_cbt_f32")
-        _chk(lib.evmi_fs2_add_posemb_f32(frames.data_ptr(), mel_lens.data_ptr(), self.inv_freq.data_ptr(), B, T, D, _s(frames)), "evmi_fs2_add_posemb_f32")
-        f = Var(frames)
+        frame = [key for key in ("pitch", "energy") if levels[key] == "frame"]
+        if not frame:
+            _chk(lib.evmi_fs2_add_posemb_f32(frames.data_ptr(), mel_lens.data_ptr(), self.inv_freq.data_ptr(), B, T, D, _s(frames)), "evmi_fs2_add_posemb_f32")
+        f = regulated = Var(frames)
         x_enc = x
 
         def lr_bwd():
-            if f.grad is None:
+            if regulated.grad is None:
                 return
-            dfr = ops.mask_cols_(f.grad, mel_lens)  # the positional sinusoid is constant; padded frames were zeroed
+            dfr = ops.mask_cols_(regulated.grad, mel_lens)  # the positional sinusoid is constant; padded frames were zeroed
             dx = torch.empty(D, B, L, device=dev, dtype=torch.float32)
             _chk(lib.evmi_length_regulate_bwd_cbt_f32(dfr.data_ptr(), cum.data_ptr(), dx.data_ptr(), D, B, L, T, _s(dx)), "evmi_length_regulate_bwd_cbt_f32")
             x_enc.accumulate(dx)
 
         tape.record(lr_bwd)
+        if frame:
+            # Frame-level predictors: on the main chain, in order, on the regulated frames (zero at the padded ones) WITHOUT the positional
+            # term; each adds its targets' embedding at every frame, padded ones included (the next predictor's k = 3 convolutions see
+            # those columns).  Then the positional term, which also zeroes the padding: its backward is the mask.
+            h = f
+            for key in frame:
+                pred, bins, table, weight = variances[key]
+                losses[key] = _LOSS[kinds[key]](tape, pred.forward(tape, h, mel_lens, seeds), target[key].view(1, B, T), n_frames, weight)
+                h = self._add_bucket_embedding(tape, h, target[key], bins, table)
+            _chk(lib.evmi_fs2_add_posemb_f32(h.data.data_ptr(), mel_lens.data_ptr(), self.inv_freq.data_ptr(), B, T, D, _s(frames)), "evmi_fs2_add_posemb_f32")
+            f = Var(h.data)  # (in place on the last embedding's output, which nothing else reads)
+            _ACTIVATION_ELEMS[0] -= h.data.numel()
+            tape.record(lambda v=h, o=f: o.grad is not None and v.accumulate(ops.mask_cols_(o.grad, mel_lens)))
         if data_parallel and not on_stream:
             dp_cut()
         y = self.decoder.forward(tape, f, mel_lens, seeds)
         mel = masked(tape, dense(tape, y, self.mel_linear), mel_lens)
-        losses["mel"] = mse_loss(tape, mel, mel_t, n_el, tr.mel_loss_weight)
+        losses["mel"] = _LOSS[kinds["mel"]](tape, mel, mel_t, n_el, tr.mel_loss_weight)
         if self.postnet:
             h = mel
             for i, (conv, bn) in enumerate(self.postnet):
                 h = batchnorm(tape, dense(tape, h, conv), bn, ops.ACT_TANH if i < len(self.postnet) - 1 else ops.ACT_NONE)
             post = masked(tape, residual(tape, mel, h), mel_lens)
-            losses["postnet"] = mse_loss(tape, post, mel_t, n_el, tr.postnet_loss_weight)
+            losses["postnet"] = _LOSS[kinds["mel"]](tape, post, mel_t, n_el, tr.postnet_loss_weight)
         if _EVAL[0]:
             ops.wgrad_join(dev)
             return self._finish_backward(losses, grads=False)
