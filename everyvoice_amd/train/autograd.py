@@ -43,6 +43,12 @@ class Var:
             ops.axpby(1.0, self.grad, 1.0, g, out=self.grad)
 
 
+def alias(x: Var) -> Var:
+    """Another Var over x's data with a gradient of its own -- a second reader's view, not another activation (it is not counted)."""
+    _ACTIVATION_ELEMS[0] -= x.data.numel()
+    return Var(x.data)
+
+
 class _Cut:
     """A point of the tape where backward may be interrupted (``Tape.backward_segments``); ``join`` runs before the interruption."""
 

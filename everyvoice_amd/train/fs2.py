@@ -35,9 +35,9 @@ import torch
 from .. import _lib
 from ..fs2 import N_PHONOLOGICAL_FEATURES, FastSpeech2ModelConfig, Stats, apply_variance_settings
 from . import ops
-from .autograd import _ACTIVATION_ELEMS, Tape, Var
+from .autograd import _ACTIVATION_ELEMS, Tape, Var, alias
 from .layers import ParamGroup, WNBatch, WNConv
-from .step import EAGER, BucketReducer, CapturedStep, on_own_stream, step_scope
+from .step import EAGER, BucketReducer, CapturedStep, SideBranch, _held_tensors, on_own_stream, step_scope  # noqa: F401 (_held_tensors: its old home)
 
 
 @dataclass
@@ -201,40 +201,6 @@ def _row(t):
     kernels share one packed copy of every operand between forward, input gradient and weight gradient for any B * T
     (csrc/conv_pk_common.h: pk_shared_items) -- with B items that needs B * T to be a multiple of 64."""
     return t if (t.shape[1] == 1 or not ops.packed_bf16()) else t.reshape(t.shape[0], 1, -1)
-
-
-def _held_tensors(fns, depth: int = 4) -> list:
-    """Every tensor the closures `fns` (tape operators) can reach through their cells: Vars, dicts, lists, nested closures.  A branch
-    that runs on another stream keeps this list until the main chain has joined it: an operator that drops a tensor when it has
-    LAUNCHED its kernels (`packed.clear()`, a Var going out of scope) hands the block back to the pool of the stream that allocated it,
-    and that stream's next allocation may write it while the branch's kernels still read it."""
-    out, seen = [], set()
-
-    def visit(o, d):
-        if id(o) in seen or d < 0:
-            return
-        seen.add(id(o))
-        if torch.is_tensor(o):
-            out.append(o)
-        elif isinstance(o, Var):
-            visit(o.data, d)
-            visit(o.grad, d)
-        elif isinstance(o, dict):
-            for v in o.values():
-                visit(v, d - 1)
-        elif isinstance(o, (list, tuple)):
-            for v in o:
-                visit(v, d - 1)
-        elif callable(o) and getattr(o, "__closure__", None):
-            for c in o.__closure__:
-                try:
-                    visit(c.cell_contents, d - 1)
-                except ValueError:  # (an empty cell)
-                    pass
-
-    for f in fns:
-        visit(f, depth)
-    return out
 
 
 def _items(B, T):
@@ -517,6 +483,111 @@ def masked(tape: Tape, x: Var, lens32) -> Var:
     return y
 
 
+def _add_posemb_(x, lens32, inv_freq):
+    """x [D, B, L] += the positional sinusoid at the columns t < len[b]; the others are zeroed.  In place."""
+    D, B, L = x.shape
+    _chk(_lib.load().evmi_fs2_add_posemb_f32(x.data_ptr(), lens32.data_ptr(), inv_freq.data_ptr(), B, L, D, _s(x)), "evmi_fs2_add_posemb_f32")
+    return x
+
+
+def add_position_(tape: Tape, x: Var, lens32, inv_freq) -> Var:
+    """The positional term IN PLACE on x's data, which nothing else reads: the result is an alias.  The term is constant and the
+    padded columns are zeroed, so the backward is the column mask."""
+    _add_posemb_(x.data, lens32, inv_freq)
+    return _record(tape, alias(x), lambda dy: x.accumulate(ops.mask_cols_(dy, lens32)))
+
+
+def embed_text(tape: Tape, text, lens32, layer, inv_freq=None) -> Var:
+    """The text input layer -> [D, B, L], zero at the padded columns; with `inv_freq`: plus the positional sinusoid.  `layer` a Table:
+    `text` = symbol ids [B, L] int32; a Dense (the bias-free Linear): `text` = phonological feature vectors [43, B, L]."""
+    lib = _lib.load()
+    if not isinstance(layer, Table):
+        v = dense(tape, Var(text, needs_grad=False), layer)
+        if inv_freq is None:
+            return masked(tape, v, lens32)
+        return _record(tape, Var(_add_posemb_(v.data.clone(), lens32, inv_freq)), lambda dy: v.accumulate(ops.mask_cols_(dy.clone(), lens32)))
+    (B, L), D = text.shape, layer.D
+    e = torch.empty(D, B, L, device=text.device, dtype=torch.float32)
+    _chk(lib.evmi_fs2_embed_f32(text.data_ptr(), lens32.data_ptr(), layer.data().data_ptr(), 0 if inv_freq is None else inv_freq.data_ptr(), e.data_ptr(),
+                                B, L, D, _s(e)), "evmi_fs2_embed_f32")
+    return _record(tape, Var(e), lambda dy: _chk(lib.evmi_fs2_embed_bwd_f32(
+        dy.data_ptr(), text.data_ptr(), lens32.data_ptr(), layer.grad().data_ptr(), layer.rows, B, L, D, 0, _s(dy)), "evmi_fs2_embed_bwd_f32"))
+
+
+def add_item_embedding(tape: Tape, x: Var, item_ids, lens32, table, sink) -> Var:
+    """x[:, b, l] + table[item_ids[b]] at the non-padded positions.  `table` [rows, D]: a speaker / language table, or the style matrix
+    of the Global Style Token module (item b = row b).  Its gradient goes to `sink`: a tensor [rows, D] the kernel adds into (the
+    table's parameter gradient), or a Var, which accumulates a matrix of its own."""
+    lib = _lib.load()
+    D, B, L = x.data.shape
+    rows = table.shape[0]
+    out = x.data.clone()
+    _chk(lib.evmi_fs2_add_item_embedding_f32(out.data_ptr(), item_ids.data_ptr(), lens32.data_ptr(), table.data_ptr(), B, L, D, _s(out)),
+         "evmi_fs2_add_item_embedding_f32")
+
+    def bwd(dy):
+        to_var = isinstance(sink, Var)
+        d_table = torch.zeros(rows, D, device=dy.device, dtype=torch.float32) if to_var else sink
+        _chk(lib.evmi_fs2_item_embedding_bwd_f32(dy.data_ptr(), item_ids.data_ptr(), lens32.data_ptr(), d_table.data_ptr(), rows, B, L, D, _s(dy)),
+             "evmi_fs2_item_embedding_bwd_f32")
+        if to_var:
+            sink.accumulate(d_table)
+        x.accumulate(dy)
+
+    return _record(tape, Var(out), bwd)
+
+
+def add_bucket_embedding(tape: Tape, x: Var, values, bins, table: Table) -> Var:
+    """x[:, b, l] + table[bucket(values[b, l])] at every position (`bins`: the bucket boundaries); one kernel serves both axes."""
+    lib = _lib.load()
+    D, B, L = x.data.shape
+    out = x.data.clone()
+    _chk(lib.evmi_fs2_bucket_embed_add_f32(out.data_ptr(), values.data_ptr(), bins.data_ptr(), table.data().data_ptr(), table.rows, B, L, D, 1.0, _s(out)),
+         "evmi_fs2_bucket_embed_add_f32")
+
+    def bwd(dy):
+        idx = torch.empty(B, L, device=dy.device, dtype=torch.int32)
+        _chk(lib.evmi_fs2_bucket_embed_bwd_f32(dy.data_ptr(), values.data_ptr(), bins.data_ptr(), table.grad().data_ptr(), idx.data_ptr(), table.rows,
+                                               B, L, D, 1.0, _s(dy)), "evmi_fs2_bucket_embed_bwd_f32")
+        x.accumulate(dy)
+
+    return _record(tape, Var(out), bwd)
+
+
+def length_regulate(tape: Tape, x: Var, cum, mel_lens32, T: int, inv_freq=None) -> Var:
+    """x [D, B, L] -> frames [D, B, T]: symbol l of item b fills the frames cum[b, l - 1] <= t < cum[b, l]; with `inv_freq` the positional
+    term is added to the new tensor at once.  The backward masks the frames' gradient with `mel_lens32` first (the positional term is
+    constant, padded frames were zeroed)."""
+    lib = _lib.load()
+    D, B, L = x.data.shape
+    frames = torch.empty(D, B, T, device=x.data.device, dtype=torch.float32)
+    _chk(lib.evmi_length_regulate_cbt_f32(x.data.data_ptr(), cum.data_ptr(), frames.data_ptr(), D, B, L, T, _s(frames)), "evmi_length_regulate_cbt_f32")
+    if inv_freq is not None:
+        _add_posemb_(frames, mel_lens32, inv_freq)
+
+    def bwd(dy):
+        dfr = ops.mask_cols_(dy, mel_lens32)
+        dx = torch.empty(D, B, L, device=dy.device, dtype=torch.float32)
+        _chk(lib.evmi_length_regulate_bwd_cbt_f32(dfr.data_ptr(), cum.data_ptr(), dx.data_ptr(), D, B, L, T, _s(dx)), "evmi_length_regulate_bwd_cbt_f32")
+        x.accumulate(dx)
+
+    return _record(tape, Var(frames), bwd)
+
+
+def joined_alias(tape: Tape, branch: SideBranch, x: Var) -> Var:
+    """`branch`'s view of x: an alias whose gradient the branch's backward leaves; where x's own backward is due the main chain joins
+    the branch and adds that gradient to x's -- the same additions in the same order whatever stream ran the branch."""
+    a = alias(x)
+
+    def bwd():
+        branch.join()
+        if a.grad is not None:
+            x.accumulate(a.grad)
+
+    tape.record(bwd)
+    return a
+
+
 def mse_loss(tape: Tape, pred: Var, target: torch.Tensor, count_dev: torch.Tensor, weight: float) -> torch.Tensor:
     """weight * sum((pred - target)^2) / count -> device scalar; both operands are zero outside the valid region.  ``count_dev``:
     the number of valid elements as a DEVICE scalar (it changes from batch to batch; a captured step must not bake it in)."""
@@ -636,59 +707,41 @@ class _AlignerT:
                       Dense(g, *name("query", 4), n_mels, self.n_att, 1)]
 
     def join_side(self):
-        """The main stream waits for the CTC side stream (what the aligner's backward does anyway; a captured stretch that ends
-        before that backward must not leave the forked stream unjoined)."""
-        if getattr(self, "_pending_done", None) is not None:
-            torch.cuda.current_stream(self._pending_done_device).wait_event(self._pending_done)
-            self._pending_done = None  # joined: the aligner's backward (possibly in the NEXT captured stretch) must not wait on an
-                                       # event that belongs to this one
+        """The current stream waits for the CTC branch (what the aligner's backward does anyway): the ``join`` of a ``Tape.cut`` that
+        ends a captured stretch before that backward."""
+        self.ctc.join()
+
+    @staticmethod
+    def _search(soft, mel_lens32, text_lens32):
+        from ..heavy import maximum_path
+        hard, dur = maximum_path(ops.elementwise(16, soft), mel_lens32, text_lens32)
+        return hard, dur.to(torch.int32)
 
     def forward(self, tape: Tape, text_emb: Var, mel: Var, prior, text_lens32, mel_lens32, n_frames_dev, ctc_weight: float, bin_on: bool,
                 bin_w_dev=None, bin_div_dev=None):
         """-> ``join``; ``join() -> (losses dict, hard durations [B, L] int32, hard alignment)`` once the main stream needs them.
-        Records the backward of both losses into the projections / embedding."""
-        from ..heavy import maximum_path
+        Records the backward of both losses into the projections / embedding.  ``self.ctc`` / ``self.mas``: the trainer's SideBranches."""
         k = dense(tape, dense(tape, text_emb, self.key[0], ops.ACT_RELU), self.key[1])
         q = dense(tape, dense(tape, dense(tape, mel, self.query[0], ops.ACT_RELU), self.query[1], ops.ACT_RELU), self.query[2])
         soft, logprob = ops.align_attention_fwd(q.data, k.data, prior, text_lens32, self.temperature)
         # The CTC forward-sum loss and its gradient (one workgroup per utterance walking the frames: ~2 ms of latency, a fraction of
-        # the chip) are only needed when backward reaches the aligner: they run on a side stream beside the variance adaptor and
-        # the decoder, and the aligner's backward waits for them.
-        main = torch.cuda.current_stream(logprob.device)
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(logprob.device)
-        fork, done = torch.cuda.Event(), torch.cuda.Event()
-        fork.record(main)
-        self._side.wait_event(fork)
-        with torch.cuda.stream(self._side):
-            ctc, dlogprob = ops.forward_sum_loss_and_grad(logprob, text_lens32, mel_lens32, ctc_weight)
-            done.record(self._side)
+        # the chip) are only needed when backward reaches the aligner: beside the variance adaptor and the decoder.
+        ctc, dlogprob = self.ctc.fork(ops.forward_sum_loss_and_grad, logprob, text_lens32, mel_lens32, ctc_weight)
         # The monotonic search over log(soft) (no gradient; one wave per utterance, ~0.7 ms) gives the durations the length regulator
-        # and the variance targets need -- but the encoder does not: it runs on a second side stream beside the encoder's forward,
-        # and `join()` (called by the trainer in front of the first use of the durations) makes the main stream wait for it.
-        if getattr(self, "_side_mas", None) is None:
-            self._side_mas = torch.cuda.Stream(logprob.device)
-        mas_done = torch.cuda.Event()
-        self._side_mas.wait_event(fork)
-        with torch.cuda.stream(self._side_mas):
-            hard, dur = maximum_path(ops.elementwise(16, soft), mel_lens32, text_lens32)
-            dur = dur.to(torch.int32)
-            mas_done.record(self._side_mas)
-        if not torch.cuda.is_current_stream_capturing():
-            for t in (hard, dur):  # allocated on the side stream's pool, used (and released) under the main stream
-                t.record_stream(main)
+        # and the variance targets need -- but the encoder does not: beside the encoder's forward, until `join()`.
+        hard, dur = self.mas.fork(self._search, soft, mel_lens32, text_lens32)
+        self.mas.hand_over(hard, dur)
         losses = {"attn_ctc": ctc}
-        self._pending_done, self._pending_done_device = done, logprob.device
 
         def join():
             from ..heavy import binarization_loss
-            torch.cuda.current_stream(logprob.device).wait_event(mas_done)
+            self.mas.join()
             if bin_on:  # the weight ramps with the epoch: it is a device scalar, so the launch sequence (and a captured graph) stays
                 losses["attn_bin"] = ops.elementwise(ops.EW_MUL, binarization_loss(hard, soft).reshape(1), bin_w_dev)
             return losses, dur, hard
 
         def bwd():
-            self.join_side()  # (the CTC side stream: its gradient is needed now)
+            self.ctc.join()  # (its gradient is needed now)
             # (binarisation weight / frame count: one device scalar, frames / weight, divides a unit scale)
             dq, dk = ops.align_attention_bwd(q.data, k.data, soft, logprob, prior, hard if bin_on else None, dlogprob, text_lens32,
                                              self.temperature, 1.0 if bin_on else 0.0, bin_count=bin_div_dev if bin_on else n_frames_dev)
@@ -816,6 +869,29 @@ class _StyleTokensT:
         return style
 
 
+@dataclass
+class _Step:
+    """The state of one step, handed from stage to stage of ``FastSpeech2Trainer._forward_backward``."""
+    batch: dict
+    meta: dict
+    pad: torch.Tensor       # [B, L] bool: the padded symbols
+    pred: SideBranch        # the variance predictors
+    align: SideBranch       # the aligner's backward
+    segmented: bool         # the backward is handed out as a generator (data-parallel capture)
+    data_parallel: bool
+    tape: Tape = field(default_factory=Tape)
+    losses: dict = field(default_factory=dict)
+    draws: int = 0
+
+    def seeds(self, n: int = 1) -> int:
+        """Counter-based dropout seeds: the draw's index inside the step; the kernels add the device-resident base
+        (seed, step, rank) << 16 -- distinct per (seed, step, rank, draw): every data-parallel rank masks its shard
+        independently, as per-process RNG streams do under DDP."""
+        self.draws += n
+        assert self.draws < 65536, "more dropout draws in one step than the seed layout reserves"
+        return self.draws - n
+
+
 class FastSpeech2Trainer(CapturedStep):
     """``tr = FastSpeech2Trainer(config, stats); losses = tr.training_step(batch)``.
 
@@ -834,9 +910,8 @@ class FastSpeech2Trainer(CapturedStep):
         # weight / bias gradients on a sibling stream beside the input-gradient chain (ops.side_wgrad): the step is one eager stream
         # of mostly small launches, so the two fill each other's gaps
         self.side_wgrad = (os.environ.get("EVMI_FS2_SIDE_WGRAD", "1") == "1") if side_wgrad is None else bool(side_wgrad)
-        self._stream = None  # set at the end of __init__ (with its sibling streams)
-        self._pred_branch = os.environ.get("EVMI_FS2_PRED_STREAM", "1") == "1"  # the variance predictors beside the decoder (_step)
-        self._align_branch = os.environ.get("EVMI_FS2_ALIGN_STREAM", "1") == "1"  # the aligner's backward beside the encoder's (_step)
+        self._pred_branch = os.environ.get("EVMI_FS2_PRED_STREAM", "1") == "1"  # the variance predictors beside the decoder (_begin_step)
+        self._align_branch = os.environ.get("EVMI_FS2_ALIGN_STREAM", "1") == "1"  # the aligner's backward beside the encoder's (_begin_step)
         self._dp_branch = os.environ.get("EVMI_FS2_DP_BRANCH", "1") == "1"  # both branches under data parallelism too (stretches cut behind their joins)
         self.last_step_branch_on_stream = False
         self.use_graph = bool(use_graph)
@@ -901,13 +976,12 @@ class FastSpeech2Trainer(CapturedStep):
         self._stream = torch.cuda.Stream(self.device)
         with torch.cuda.stream(self._stream):
             ops._side_state(self.device)  # the weight-gradient sibling of self._stream
-        if self.aligner is not None:
-            self.aligner._side = torch.cuda.Stream(self.device)
-            self.aligner._side_mas = torch.cuda.Stream(self.device)
-        if self.device.type == "cuda":
-            self._pred_stream = torch.cuda.Stream(self.device)
-            self._pred_fork, self._pred_done = torch.cuda.Event(), torch.cuda.Event()
-            self._align_fork, self._align_done = torch.cuda.Event(), torch.cuda.Event()
+        if self.aligner is not None:  # the CTC loss and the alignment search, each on a stream of its own
+            self.aligner.ctc = SideBranch(self.device)
+            self.aligner.mas = SideBranch(self.device)
+        # the variance predictors, forward and backward, and -- on the same stream, behind events of its own -- the aligner's backward
+        self._pred = SideBranch(self.device)
+        self._align = SideBranch(self.device, stream=self._pred.stream)
 
     def _tail_offset(self) -> int:
         """First element of the flat buffers that belongs to the decoder / mel_linear / postnet (declared last, in this order)."""
@@ -1116,292 +1190,186 @@ class FastSpeech2Trainer(CapturedStep):
             return self._forward_backward(d, meta)
 
     def _forward_backward(self, batch: dict, meta: dict, segmented: bool = False):
-        """The launch sequence of one step on a prepared (device) batch: no host read, no host-dependent argument.
+        """The launch sequence of one step on a prepared (device) batch: no host read, no host-dependent argument.  Under
+        ``evaluate`` the same stages with both branches on the chain, no gradient zeroing and no backward.
         ``segmented``: -> (backward generator, losses) instead of running the backward: every ``next()`` runs it up to the next
         gradient-bucket boundary (data-parallel graph capture: the all-reduces sit between the captured stretches), and
         ``_finish_backward(losses)`` completes the step's gradient side."""
-        lib, dev, c, tr = _lib.load(), self.device, self.config, self.training
-        lens, mel_lens, mel_t = batch["lens"], batch["mel_lens"], batch["mel_t"]
-        feats, ids = batch.get("pfs"), batch.get("ids")
-        B, L, T = meta["B"], meta["L"], meta["T"]
-        D = c.encoder.input_dim
-        n_tok, n_frames, n_el = self._scal[1:2], self._scal[2:3], self._scal[3:4]  # device scalars (see _store_step_scalars)
-        pad = torch.arange(L, device=dev)[None, :] >= lens[:, None]
-        learn = self.aligner is not None
+        st = self._begin_step(batch, meta, segmented)
+        x, align_join = self._embed_and_encode(st)
+        cum, log_d, target = self._durations_and_targets(st, align_join)
+        x = self._add_utterance_embeddings(st, x)
+        x = self._phone_adaptor(st, x, log_d, target)
+        frame = [key for key in ("pitch", "energy") if self.levels[key] == "frame"]
+        # (the decoder's positional term comes behind the last variance embedding: here, or at the end of the frame-level adaptor)
+        f = length_regulate(st.tape, x, cum, batch["mel_lens"], meta["T"], None if frame else self.inv_freq)
+        if frame:
+            f = self._frame_adaptor(st, f, frame, target)
+        if st.data_parallel and not st.pred.enabled:
+            self._dp_cut(st)
+        self._decode(st, f)
+        return self._backward(st)
 
-        if not _EVAL[0]:
+    def _begin_step(self, batch: dict, meta: dict, segmented: bool) -> _Step:
+        """Which schedule the step takes (the one place that says so), its state, and the parameters' side: gradients zeroed, the
+        weight-normed layers' effective weights computed."""
+        train = not _EVAL[0]
+        pad = torch.arange(meta["L"], device=self.device)[None, :] >= batch["lens"][:, None]
+        # Data parallel: the captured step is cut into stretches around the gradient exchanges and a forked stream has to come back
+        # inside one stretch -- so the stretch boundary sits BEHIND the predictors' join (`_phone_adaptor`), not across the branch, and the
+        # step a data-parallel run times is the step one GPU times.  EVMI_FS2_DP_BRANCH=0: the predictors on the chain there.
+        data_parallel = segmented or self._reducer is not None
+        on_stream = train and self._pred_branch and (self._dp_branch or not data_parallel)
+        self.last_step_branch_on_stream = on_stream
+        st = _Step(batch, meta, pad, self._pred.begin(on_stream), self._align.begin(on_stream and self._align_branch), segmented, data_parallel)
+        if train:
             self.params.zero_grad()
         self._wn_batch.materialize()
-        tape = Tape()
-        counter = [0]
+        return st
 
-        def seeds(n=1):
-            """Counter-based dropout seeds: the draw's index inside the step; the kernels add the device-resident base
-            (seed, step, rank) << 16 -- distinct per (seed, step, rank, draw): every data-parallel rank masks its shard
-            independently, as per-process RNG streams do under DDP."""
-            counter[0] += n
-            assert counter[0] < 65536, "more dropout draws in one step than the seed layout reserves"
-            return counter[0] - n
+    def _embed_and_encode(self, st: _Step):
+        """Text embedding and encoder, the aligner beside them -> (encoder output, the aligner's ``join`` or None)."""
+        b, tape, tr = st.batch, st.tape, self.training
+        lens = b["lens"]
+        text, layer = (b["pfs"], self.text_linear) if self.pfs else (b["ids"], self.text_table)
+        align_join = None
+        if self.aligner is not None:
+            # The aligner's backward depends on its own losses only (attention, five k = 3 convolutions over the mel frames, fp32
+            # products: ~1 ms).  It has a tape of its own (st.align) and an alias of the text embedding whose gradient joins the chain in
+            # front of the embedding's backward; `_phone_adaptor` says where it starts.
+            ta = joined_alias(tape, st.align, embed_text(tape, text, lens, layer))
+            align_join = self.aligner.forward(st.align.tape, ta, Var(b["mel_t"], needs_grad=False), b.get("attn_prior"), lens, b["mel_lens"], self._scal[2:3],
+                                              tr.attn_ctc_loss_weight, self._bin_weight() > 0.0, self._scal[4:5], self._scal[5:6])
+        x0 = embed_text(tape, text, lens, layer, self.inv_freq)
+        return self.encoder.forward(tape, x0, lens, st.seeds), align_join
 
-        def embed(with_position: bool) -> Var:
-            if self.pfs:  # Linear(43 -> D) over the feature vectors, padded columns zeroed (+ the positional sinusoid)
-                v = dense(tape, Var(feats, needs_grad=False), self.text_linear)
-                if not with_position:
-                    return masked(tape, v, lens)
-                e = v.data.clone()
-                _chk(lib.evmi_fs2_add_posemb_f32(e.data_ptr(), lens.data_ptr(), self.inv_freq.data_ptr(), B, L, D, _s(e)), "evmi_fs2_add_posemb_f32")
-                out = Var(e)
-                tape.record(lambda: out.grad is not None and v.accumulate(ops.mask_cols_(out.grad.clone(), lens)))
-                return out
-            e = torch.empty(D, B, L, device=dev, dtype=torch.float32)
-            _chk(lib.evmi_fs2_embed_f32(ids.data_ptr(), lens.data_ptr(), self.text_table.data().data_ptr(), self.inv_freq.data_ptr() if with_position else 0,
-                                        e.data_ptr(), B, L, D, _s(e)), "evmi_fs2_embed_f32")
-            v = Var(e)
-            tape.record(lambda: v.grad is not None and _chk(lib.evmi_fs2_embed_bwd_f32(
-                v.grad.data_ptr(), ids.data_ptr(), lens.data_ptr(), self.text_table.grad().data_ptr(), self.text_table.rows, B, L, D, 0, _s(e)), "evmi_fs2_embed_bwd_f32"))
-            return v
-
-        losses = {}
-        # The variance predictors are side branches under teacher forcing (see below): they get a tape of their own and ALIASES of their
-        # inputs, in every training schedule (one order of additions into the encoder output's gradient whatever stream runs them).
-        struct = not _EVAL[0]
-        # (data parallel: the captured step is cut into stretches around the gradient exchanges and a forked stream has to come back
-        # inside one stretch -- so the stretch boundary sits BEHIND the branch's join (below: `dp_cut`), not across the branch, and the
-        # step a data-parallel run times is the step one GPU times.  EVMI_FS2_DP_BRANCH=0: the predictors on the chain there, as in round 5.)
-        data_parallel = segmented or self._reducer is not None
-        on_stream = struct and self._pred_branch and dev.type == "cuda" and (self._dp_branch or not data_parallel)
-        self.last_step_branch_on_stream = bool(on_stream)
-        pjoin = {"done": None, "tape": Tape()} if struct else None
-
-        def join_branch(var, alias):
-            """(a tape operator) the main chain waits for the branch and takes the gradient it left on its alias of `var`"""
-            if pjoin["done"] is not None:
-                torch.cuda.current_stream(dev).wait_event(pjoin["done"])
-                pjoin["done"] = None
-            if alias.grad is not None:
-                var.accumulate(alias.grad)
-
-        # The aligner's backward depends on its own losses only (attention, five k = 3 convolutions over the mel frames, fp32 products:
-        # ~1 ms at the END of the chain).  On the predictors' stream from the start of backward it gave their 1.2 ms back (17.7 vs 16.5 ms:
-        # its kernels are large enough to take CUs from the decoder's backward); started where the ENCODER's backward starts -- 4.5 k
-        # columns, latency-bound launches that leave most of the chip idle -- it runs beside that.  Its own tape, an alias of the text
-        # embedding whose gradient joins the chain in front of the embedding's backward: the same additions in every schedule.
-        astruct = struct and learn
-
-        def start_aligner_backward():
-            if not astruct or pjoin.get("astarted"):
-                return
-            pjoin["astarted"] = True
-            if on_stream and self._align_branch:
-                main = torch.cuda.current_stream(dev)
-                self._align_fork.record(main)
-                self._pred_stream.wait_event(self._align_fork)
-                with torch.cuda.stream(self._pred_stream), ops.mode(side_wgrad=False):
-                    pjoin["akeep"] = _held_tensors(pjoin["atape"]._ops)  # (outlive the KERNELS: the aligner's forward ran on the main stream)
-                    pjoin["atape"].backward()
-                    self._align_done.record(self._pred_stream)
-                pjoin["adone"] = self._align_done
-            else:
-                pjoin["atape"].backward()
-
-        def join_aligner(var, alias):
-            start_aligner_backward()  # (if the encoder output had no gradient to trigger it)
-            if pjoin.get("adone") is not None:
-                torch.cuda.current_stream(dev).wait_event(pjoin["adone"])
-                pjoin["adone"] = None
-            if alias.grad is not None:
-                var.accumulate(alias.grad)
-
-        def dp_cut():
-            """Data parallel: where the tail bucket (decoder / mel_linear / postnet: ~half of the parameters, final once backward has left
-            the decoder) goes to its all-reduce, which runs on a side stream under the rest of the backward.  Recorded in front of the
-            decoder's forward = reached after its backward.  With the predictors on their stream the point sits behind their join
-            (the bucket leaves a length-regulator backward and two embedding backwards later; every fork is closed inside a stretch)."""
-            if segmented:
-                # (captured step: the stretch ends here; every stream forked so far must be back on the main one)
-                tape.cut(self.aligner.join_side if learn else None)
-            else:
-                lo_tail, red = self._tail_offset(), self._reducer
-                tape.record(lambda: (ops.wgrad_join(dev), red.launch(lo_tail, self.params.grad.numel())))
-
-        if learn:
-            te = embed(False)
-            if astruct:
-                pjoin["atape"] = Tape()
-                ta = Var(te.data)
-                _ACTIVATION_ELEMS[0] -= te.data.numel()  # (an alias, not another activation)
-                tape.record(lambda: join_aligner(te, ta))
-            align_join = self.aligner.forward(pjoin["atape"] if astruct else tape, ta if astruct else te, Var(mel_t, needs_grad=False), batch.get("attn_prior"),
-                                              lens, mel_lens, n_frames, tr.attn_ctc_loss_weight, self._bin_weight() > 0.0, self._scal[4:5], self._scal[5:6])
-        else:
-            dur = batch["durations"]
-
-        x0 = embed(True)
-        x = self.encoder.forward(tape, x0, lens, seeds)
-
-        if learn:  # the alignment search ran beside the encoder
+    def _durations_and_targets(self, st: _Step, align_join):
+        """-> (cumulated durations [B, L] int32, log(1 + durations), variance targets: [B, L] for a phone-level predictor, the per-frame
+        values [B, T], zero past the item's frames, for a frame-level one)."""
+        b, B, T = st.batch, st.meta["B"], st.meta["T"]
+        if align_join is not None:  # the alignment search ran beside the encoder
             align_losses, dur, self.last_alignment = align_join()
-            losses.update(align_losses)
+            st.losses.update(align_losses)
+        else:
+            dur = b["durations"]
         cum = torch.cumsum(dur, 1, dtype=torch.int32).contiguous()
-        log_d_t = torch.log(dur.float() + 1.0).contiguous()
-        # variance targets: [B, L] for a phone-level predictor, the per-frame values [B, T] (zero past the item's frames) for a frame-level one
-        levels, kinds = self.levels, self.loss_kinds
-        target = {key: self._phone_level(batch, key, cum, dur, pad, T) if levels[key] == "phone"
-                  else ops.mask_cols_(batch[key + "_frames"].view(1, B, T).clone(), mel_lens).view(B, T) for key in ("pitch", "energy")}
-        variances = {"pitch": (self.pitch_predictor, self.pitch_bins, self.pitch_table, tr.pitch_loss_weight),
-                     "energy": (self.energy_predictor, self.energy_bins, self.energy_table, tr.energy_loss_weight)}
-        phone = [key for key in ("pitch", "energy") if levels[key] == "phone"]
+        log_d = torch.log(dur.float() + 1.0).contiguous()
+        target = {key: self._phone_level(b, key, cum, dur, st.pad, T) if self.levels[key] == "phone"
+                  else ops.mask_cols_(b[key + "_frames"].view(1, B, T).clone(), b["mel_lens"]).view(B, T) for key in ("pitch", "energy")}
+        return cum, log_d, target
 
+    def _add_utterance_embeddings(self, st: _Step, x: Var) -> Var:
+        """Speaker, language and style: one vector per utterance, added at its non-padded symbols."""
+        b, lens = st.batch, st.batch["lens"]
         for table, key in ((self.speaker_table, "speakers"), (self.language_table, "languages")):
             if table is not None:
-                x = self._add_item_embedding(tape, x, table, batch[key], lens)
+                x = add_item_embedding(st.tape, x, b[key], lens, table.data(), table.grad())
         if self.gst is not None:
-            x = self._add_style_embedding(tape, x, self.gst.forward(tape, batch["mel_btf"]), lens)
+            style = self.gst.forward(st.tape, b["mel_btf"])
+            x = add_item_embedding(st.tape, x, torch.arange(st.meta["B"], device=self.device, dtype=torch.int32), lens, style.data, style)
+        return x
 
-        w = tr.duration_loss_weight
-        # The three variance predictors are side branches under teacher forcing (the decoder takes the TARGETS' embeddings): ~170 launches
-        # of ~8 us at 4.5 k columns, forward and backward.  They run as ONE chain on a stream of their own beside the length regulator, the
-        # decoder and its backward, on aliases of the encoder output whose gradients join the main chain where that output's backward
-        # starts: 17.7 -> 16.5 ms per step.  (Three chains on three streams, each forked per predictor, were measured in round 3 and lost
-        # 2.6 ms: ~600 small launches then, every one a cross-stream edge of the captured graph.)
-        if struct:
-            xe, xa = x, Var(x.data)  # the predictors' view of the encoder output: same data, its own gradient
-            _ACTIVATION_ELEMS[0] -= x.data.numel()  # (an alias, not another activation)
-            # (runs in backward when everything behind x has contributed: in front of the encoder's backward -- where the aligner's starts)
-            tape.record(start_aligner_backward)
-            if data_parallel and on_stream:
-                dp_cut()  # backward: ... join_branch(xe, xa) | exchange of the tail bucket | aligner beside the encoder ...
-            tape.record(lambda: join_branch(xe, xa))
-            tp = pjoin["tape"]
-            # (duration, then the phone-level predictors in order; each on an alias of the tensor it reads: the encoder output, or that
-            # plus the embeddings of the phone-level predictors in front of it)
-            jobs = [("duration", self.duration_predictor, xa, log_d_t, w)]
+    def _variance(self, key: str):
+        tr = self.training
+        return {"pitch": (self.pitch_predictor, self.pitch_bins, self.pitch_table, tr.pitch_loss_weight),
+                "energy": (self.energy_predictor, self.energy_bins, self.energy_table, tr.energy_loss_weight)}[key]
 
-            def predictors():
-                for name, pred, alias, want, weight in jobs:
-                    losses[name] = _LOSS[kinds[name]](tp, pred.forward(tp, alias, lens, seeds), want.view(1, B, L), n_tok, weight)
+    def _predict(self, st: _Step, tape: Tape, name: str, predictor, x: Var, want, lens, count_dev, weight: float) -> None:
+        st.losses[name] = _LOSS[self.loss_kinds[name]](tape, predictor.forward(tape, x, lens, st.seeds), want.view(1, *want.shape), count_dev, weight)
 
-            def launch_predictors():
-                if on_stream:
-                    main = torch.cuda.current_stream(dev)
-                    self._pred_fork.record(main)
-                    self._pred_stream.wait_event(self._pred_fork)
-                    with torch.cuda.stream(self._pred_stream):
-                        predictors()
-                else:
-                    predictors()
+    def _run_predictors(self, st: _Step, jobs: list) -> None:
+        for name, predictor, x, want, weight in jobs:
+            self._predict(st, st.pred.tape, name, predictor, x, want, st.batch["lens"], self._scal[1:2], weight)
 
-            if not phone:
-                launch_predictors()
-            alias = xa
-            for i, key in enumerate(phone):  # (the branch starts when its last input exists: in front of the last phone-level embedding)
-                pred, bins, table, weight = variances[key]
-                if alias is None:
-                    alias = Var(x.data)
-                    _ACTIVATION_ELEMS[0] -= x.data.numel()
-                    tape.record(lambda v=x, a=alias: join_branch(v, a))
-                jobs.append((key, pred, alias, target[key], weight))
-                if i == len(phone) - 1:
-                    launch_predictors()
-                x, alias = self._add_bucket_embedding(tape, x, target[key], bins, table), None
+    def _phone_adaptor(self, st: _Step, x: Var, log_d, target: dict) -> Var:
+        """The duration predictor and the phone-level predictors with their embeddings -> the length regulator's input.
+        The predictors are side branches under teacher forcing (the decoder takes the TARGETS' embeddings): ~170 launches of ~8 us at
+        4.5 k columns, forward and backward.  They run as ONE chain (st.pred: beside the length regulator, the decoder and its backward
+        when on its stream: 17.7 -> 16.5 ms per step; three chains on three streams lost 2.6 ms to ~600 cross-stream edges), each on an
+        alias of the tensor it reads: the encoder output, or that plus the embeddings of the phone-level predictors in front of it."""
+        tape, pred = st.tape, st.pred
+        # Backward runs these three upwards: the chain joins the predictors; (data parallel, predictors on their stream) the tail bucket
+        # leaves, a length-regulator backward and two embedding backwards later than with `_forward_backward`'s cut, so that every fork
+        # is closed inside a stretch; then the aligner's backward starts where the ENCODER's does -- 4.5 k columns, latency-bound
+        # launches that leave most of the chip idle (from the start of backward it took CUs from the decoder's: 17.7 vs 16.5 ms).
+        tape.record(st.align.backward)
+        if st.data_parallel and pred.enabled:
+            self._dp_cut(st)
+        a = joined_alias(tape, pred, x)
+        jobs = [("duration", self.duration_predictor, a, log_d, self.training.duration_loss_weight)]
+        phone = [key for key in ("pitch", "energy") if self.levels[key] == "phone"]
+        if not phone:
+            pred.fork(self._run_predictors, st, jobs, done=False)
+        for i, key in enumerate(phone):
+            predictor, bins, table, weight = self._variance(key)
+            jobs.append((key, predictor, a if i == 0 else joined_alias(tape, pred, x), target[key], weight))
+            if i == len(phone) - 1:  # the branch starts when its last input exists: in front of the last phone-level embedding
+                pred.fork(self._run_predictors, st, jobs, done=False)
+            x = add_bucket_embedding(tape, x, target[key], bins, table)
+        return x
+
+    def _frame_adaptor(self, st: _Step, h: Var, frame: list, target: dict) -> Var:
+        """Frame-level predictors: on the main chain, in order, on the regulated frames (zero at the padded ones) WITHOUT the positional
+        term; each adds its targets' embedding at every frame, padded ones included (the next predictor's k = 3 convolutions see
+        those columns).  Then the positional term, which also zeroes the padding."""
+        mel_lens = st.batch["mel_lens"]
+        for key in frame:
+            predictor, bins, table, weight = self._variance(key)
+            self._predict(st, st.tape, key, predictor, h, target[key], mel_lens, self._scal[2:3], weight)
+            h = add_bucket_embedding(st.tape, h, target[key], bins, table)
+        return add_position_(st.tape, h, mel_lens, self.inv_freq)
+
+    def _dp_cut(self, st: _Step) -> None:
+        """Data parallel: where the tail bucket (decoder / mel_linear / postnet: ~half of the parameters, final once backward has left
+        the decoder) goes to its all-reduce, which runs on a side stream under the rest of the backward.  Recorded in front of the
+        decoder's forward = reached after its backward."""
+        if st.segmented:  # (captured step: the stretch ends here; every stream forked so far must be back on the main one)
+            st.tape.cut(self.aligner.join_side if self.aligner is not None else None)
         else:
-            losses["duration"] = _LOSS[kinds["duration"]](tape, self.duration_predictor.forward(tape, x, lens, seeds), log_d_t.view(1, B, L), n_tok, w)
-            for key in phone:
-                pred, bins, table, weight = variances[key]
-                losses[key] = _LOSS[kinds[key]](tape, pred.forward(tape, x, lens, seeds), target[key].view(1, B, L), n_tok, weight)
-                x = self._add_bucket_embedding(tape, x, target[key], bins, table)
+            dev, lo_tail, red, n_all = self.device, self._tail_offset(), self._reducer, self.params.grad.numel()
+            st.tape.record(lambda: (ops.wgrad_join(dev), red.launch(lo_tail, n_all)))
 
-        frames = torch.empty(D, B, T, device=dev, dtype=torch.float32)
-        _chk(lib.evmi_length_regulate_cbt_f32(x.data.data_ptr(), cum.data_ptr(), frames.data_ptr(), D, B, L, T, _s(frames)), "evmi_length_regulate_cbt_f32")
-        frame = [key for key in ("pitch", "energy") if levels[key] == "frame"]
-        if not frame:
-            _chk(lib.evmi_fs2_add_posemb_f32(frames.data_ptr(), mel_lens.data_ptr(), self.inv_freq.data_ptr(), B, T, D, _s(frames)), "evmi_fs2_add_posemb_f32")
-        f = regulated = Var(frames)
-        x_enc = x
-
-        def lr_bwd():
-            if regulated.grad is None:
-                return
-            dfr = ops.mask_cols_(regulated.grad, mel_lens)  # the positional sinusoid is constant; padded frames were zeroed
-            dx = torch.empty(D, B, L, device=dev, dtype=torch.float32)
-            _chk(lib.evmi_length_regulate_bwd_cbt_f32(dfr.data_ptr(), cum.data_ptr(), dx.data_ptr(), D, B, L, T, _s(dx)), "evmi_length_regulate_bwd_cbt_f32")
-            x_enc.accumulate(dx)
-
-        tape.record(lr_bwd)
-        if frame:
-            # Frame-level predictors: on the main chain, in order, on the regulated frames (zero at the padded ones) WITHOUT the positional
-            # term; each adds its targets' embedding at every frame, padded ones included (the next predictor's k = 3 convolutions see
-            # those columns).  Then the positional term, which also zeroes the padding: its backward is the mask.
-            h = f
-            for key in frame:
-                pred, bins, table, weight = variances[key]
-                losses[key] = _LOSS[kinds[key]](tape, pred.forward(tape, h, mel_lens, seeds), target[key].view(1, B, T), n_frames, weight)
-                h = self._add_bucket_embedding(tape, h, target[key], bins, table)
-            _chk(lib.evmi_fs2_add_posemb_f32(h.data.data_ptr(), mel_lens.data_ptr(), self.inv_freq.data_ptr(), B, T, D, _s(frames)), "evmi_fs2_add_posemb_f32")
-            f = Var(h.data)  # (in place on the last embedding's output, which nothing else reads)
-            _ACTIVATION_ELEMS[0] -= h.data.numel()
-            tape.record(lambda v=h, o=f: o.grad is not None and v.accumulate(ops.mask_cols_(o.grad, mel_lens)))
-        if data_parallel and not on_stream:
-            dp_cut()
-        y = self.decoder.forward(tape, f, mel_lens, seeds)
+    def _decode(self, st: _Step, f: Var) -> None:
+        """Decoder, mel projection and postnet, with their losses."""
+        tape, tr, mel_lens, mel_t = st.tape, self.training, st.batch["mel_lens"], st.batch["mel_t"]
+        loss, n_el = _LOSS[self.loss_kinds["mel"]], self._scal[3:4]
+        y = self.decoder.forward(tape, f, mel_lens, st.seeds)
         mel = masked(tape, dense(tape, y, self.mel_linear), mel_lens)
-        losses["mel"] = _LOSS[kinds["mel"]](tape, mel, mel_t, n_el, tr.mel_loss_weight)
+        st.losses["mel"] = loss(tape, mel, mel_t, n_el, tr.mel_loss_weight)
         if self.postnet:
             h = mel
             for i, (conv, bn) in enumerate(self.postnet):
                 h = batchnorm(tape, dense(tape, h, conv), bn, ops.ACT_TANH if i < len(self.postnet) - 1 else ops.ACT_NONE)
             post = masked(tape, residual(tape, mel, h), mel_lens)
-            losses["postnet"] = _LOSS[kinds["mel"]](tape, post, mel_t, n_el, tr.postnet_loss_weight)
+            st.losses["postnet"] = loss(tape, post, mel_t, n_el, tr.postnet_loss_weight)
+
+    def _backward(self, st: _Step):
+        """The step's backward, in one of three forms: none (``evaluate``), all of it here, or as the generator a data-parallel capture
+        advances stretch by stretch.  The predictors' backward starts with the step's: behind their forward, beside the decoder's
+        backward when on their stream, in front of the chain's otherwise."""
         if _EVAL[0]:
-            ops.wgrad_join(dev)
-            return self._finish_backward(losses, grads=False)
-        def branch_backward():
-            """The predictors' backward starts with the step's: on their stream, behind their forward, beside the decoder's backward.
-            -> what the branch's operators hold (it must outlive the branch's KERNELS, not just their launches: kept until the chain has joined)"""
-            main = torch.cuda.current_stream(dev)
-            self._pred_fork.record(main)
-            self._pred_stream.wait_event(self._pred_fork)
-            with torch.cuda.stream(self._pred_stream), ops.mode(side_wgrad=False):  # (their weight gradients stay here: it is a side chain already)
-                keep = _held_tensors(pjoin["tape"]._ops)
-                pjoin["tape"].backward()
-                self._pred_done.record(self._pred_stream)
-            pjoin["done"] = self._pred_done
-            if not torch.cuda.is_current_stream_capturing():
-                for t in [v for v in losses.values() if torch.is_tensor(v)]:
-                    t.record_stream(main)
-            return keep
+            ops.wgrad_join(self.device)
+            self._close_branches(st)
+            return self._finish_backward(st.losses, grads=False)
+        if st.segmented:
+            return self._backward_segments(st), st.losses
+        st.pred.backward()
+        st.pred.hand_over(*st.losses.values())
+        st.tape.backward()
+        self._close_branches(st)
+        return self._finish_backward(st.losses)
 
-        def branch_close(keep):
-            main = torch.cuda.current_stream(dev)
-            for which in ("done", "adone"):  # (a join that did not run: nothing needed that gradient)
-                if pjoin.get(which) is not None:
-                    main.wait_event(pjoin[which])
-                    pjoin[which] = None
-            del keep
-            pjoin.pop("akeep", None)
+    def _backward_segments(self, st: _Step):
+        st.pred.backward()
+        st.pred.hand_over(*st.losses.values())
+        # (a stretch ends at every yield: the cut sits behind the predictors' join, so their stream is back; the aligner's starts behind it)
+        yield from st.tape.backward_segments()
+        self._close_branches(st)
 
-        if segmented:
-            def segments():
-                if on_stream:
-                    keep = branch_backward()
-                    for tag in tape.backward_segments():
-                        # (a stretch ends here: the cut sits behind the predictors' join, so their stream is back; the aligner's starts behind it)
-                        yield tag
-                    branch_close(keep)
-                    return
-                pjoin["tape"].backward()  # (the predictors' backward: in front of the chain's first stretch, on its stream)
-                yield from tape.backward_segments()
-
-            return segments(), losses
-        if on_stream:
-            keep = branch_backward()
-            tape.backward()
-            branch_close(keep)
-            return self._finish_backward(losses)
-        if struct:
-            pjoin["tape"].backward()
-        tape.backward()
-        return self._finish_backward(losses)
+    def _close_branches(self, st: _Step) -> None:
+        """A join that did not run (nothing needed that gradient, or there was no backward) runs here; what the branches kept may go."""
+        for branch in (st.pred, st.align) + ((self.aligner.ctc, self.aligner.mas) if self.aligner is not None else ()):
+            branch.close()
 
     def _finish_backward(self, losses: dict, grads: bool = True) -> dict:
         if grads:
@@ -1435,64 +1403,6 @@ class FastSpeech2Trainer(CapturedStep):
         _chk(_lib.load().evmi_length_regulate_bwd_cbt_f32(fr.data_ptr(), cum.data_ptr(), sums.data_ptr(), 1, B, L, T, _s(fr)), "evmi_length_regulate_bwd_cbt_f32")
         return torch.where(dur > 0, sums / dur.clamp_min(1), torch.full_like(sums, 1e-7)).masked_fill(pad, 0.0).contiguous()
 
-    def _add_item_embedding(self, tape, x: Var, table: Table, item_ids, lens):
-        lib = _lib.load()
-        D, B, L = x.data.shape
-        out = x.data.clone()
-        _chk(lib.evmi_fs2_add_item_embedding_f32(out.data_ptr(), item_ids.data_ptr(), lens.data_ptr(), table.data().data_ptr(), B, L, D, _s(out)),
-             "evmi_fs2_add_item_embedding_f32")
-        y = Var(out)
-
-        def bwd():
-            if y.grad is None:
-                return
-            _chk(lib.evmi_fs2_item_embedding_bwd_f32(y.grad.data_ptr(), item_ids.data_ptr(), lens.data_ptr(), table.grad().data_ptr(), table.rows, B, L, D, _s(out)),
-                 "evmi_fs2_item_embedding_bwd_f32")
-            x.accumulate(y.grad)
-
-        tape.record(bwd)
-        return y
-
-    def _add_style_embedding(self, tape, x: Var, style: Var, lens):
-        """x[:, b, l] += style[b] at the non-padded positions: the item-embedding kernels with the style matrix [B, D] as the table."""
-        lib = _lib.load()
-        D, B, L = x.data.shape
-        rows = torch.arange(B, device=x.data.device, dtype=torch.int32)
-        out = x.data.clone()
-        _chk(lib.evmi_fs2_add_item_embedding_f32(out.data_ptr(), rows.data_ptr(), lens.data_ptr(), style.data.data_ptr(), B, L, D, _s(out)),
-             "evmi_fs2_add_item_embedding_f32")
-        y = Var(out)
-
-        def bwd():
-            if y.grad is None:
-                return
-            ds = torch.zeros(B, D, device=out.device, dtype=torch.float32)
-            _chk(lib.evmi_fs2_item_embedding_bwd_f32(y.grad.data_ptr(), rows.data_ptr(), lens.data_ptr(), ds.data_ptr(), B, B, L, D, _s(out)),
-                 "evmi_fs2_item_embedding_bwd_f32")
-            style.accumulate(ds)
-            x.accumulate(y.grad)
-
-        tape.record(bwd)
-        return y
-
-    def _add_bucket_embedding(self, tape, x: Var, values, bins, table: Table):
-        lib = _lib.load()
-        D, B, L = x.data.shape
-        out = x.data.clone()
-        _chk(lib.evmi_fs2_bucket_embed_add_f32(out.data_ptr(), values.data_ptr(), bins.data_ptr(), table.data().data_ptr(), table.rows, B, L, D, 1.0, _s(out)),
-             "evmi_fs2_bucket_embed_add_f32")
-        y = Var(out)
-        tape.record(lambda: y.grad is not None and self._bucket_embedding_backward(y, x, values, bins, table))
-        return y
-
-    def _bucket_embedding_backward(self, y: Var, x: Var, values, bins, table: Table):
-        lib = _lib.load()
-        D, B, L = y.data.shape
-        idx = torch.empty(B, L, device=y.data.device, dtype=torch.int32)
-        _chk(lib.evmi_fs2_bucket_embed_bwd_f32(y.grad.data_ptr(), values.data_ptr(), bins.data_ptr(), table.grad().data_ptr(), idx.data_ptr(), table.rows,
-                                               B, L, D, 1.0, _s(y.data)), "evmi_fs2_bucket_embed_bwd_f32")
-        x.accumulate(y.grad)
-
     def training_step(self, batch: dict) -> dict:
         """One optimiser step; returns the losses as device scalars (no host synchronisation inside the step).
 
@@ -1509,8 +1419,6 @@ class FastSpeech2Trainer(CapturedStep):
         (``_store_step_scalars``).  Shapes seen once or twice run eagerly; ``graph_buckets=(l, t)`` pads L and T up to multiples,
         so a real data stream lands on a small set of shapes (the extra padded columns enter the Conformer's BatchNorm statistics,
         as the reference's own padding does).  Eager and replayed steps are bit for bit the same arithmetic."""
-        if self._stream is None:
-            return self._training_step(batch)
         losses, caller = on_own_stream(self._stream, self.device, self._training_step, batch)
         for v in losses.values():
             v.record_stream(caller)

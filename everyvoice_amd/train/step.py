@@ -1,9 +1,11 @@
 """What both trainers do around and inside a step: its environment (``step_scope``), the trainer's own stream joined to the caller's
-(``on_own_stream``), the captured-step policy (``CapturedStep``) and the data-parallel gradient exchange (``BucketReducer``)."""
+(``on_own_stream``), a chain beside the main one (``SideBranch``), the captured-step policy (``CapturedStep``) and the data-parallel
+gradient exchange (``BucketReducer``)."""
 
 import torch
 
 from . import ops
+from .autograd import Tape, Var
 
 
 class step_scope(ops.mode):
@@ -39,6 +41,115 @@ def on_own_stream(stream, device, fn, *args):
         out = fn(*args)
     caller.wait_stream(stream)
     return out, caller
+
+
+def _held_tensors(fns, depth: int = 4) -> list:
+    """Every tensor the closures `fns` (tape operators) can reach through their cells: Vars, dicts, lists, nested closures."""
+    out, seen = [], set()
+
+    def visit(o, d):
+        if id(o) in seen or d < 0:
+            return
+        seen.add(id(o))
+        if torch.is_tensor(o):
+            out.append(o)
+        elif isinstance(o, Var):
+            visit(o.data, d)
+            visit(o.grad, d)
+        elif isinstance(o, dict):
+            for v in o.values():
+                visit(v, d - 1)
+        elif isinstance(o, (list, tuple)):
+            for v in o:
+                visit(v, d - 1)
+        elif callable(o) and getattr(o, "__closure__", None):
+            for c in o.__closure__:
+                try:
+                    visit(c.cell_contents, d - 1)
+                except ValueError:  # (an empty cell)
+                    pass
+
+    for f in fns:
+        visit(f, depth)
+    return out
+
+
+class SideBranch:
+    """A chain that runs beside the main chain and is joined later: a stream (given, or a new one of `device`), ONE fork and ONE done
+    event re-recorded on every use (a wait takes the record that precedes it in host order), a tape of its own and the tensors it keeps
+    alive until the join.  Not `enabled`: every operation runs inline on the current stream and the joins do nothing -- the same
+    operators in the same order, so both forms leave the same bits.  ``begin()`` opens a step's use, ``close()`` ends it.
+
+    What holds for every such chain, and is written down here only:
+    - What the branch's operators hold must outlive their KERNELS, not just their launches.  An operator that drops a tensor once it
+      has launched (``packed.clear()``, a Var going out of scope) hands the block back to the pool of the stream that allocated it, and
+      that stream's next allocation may write it while the branch still reads it: ``backward`` keeps ``_held_tensors`` of its tape
+      until ``close``.
+    - A tensor allocated under the branch and used (and released) under the main stream is handed over with ``record_stream``; that
+      applies outside graph capture only (a capture's pool is private to the graph): ``hand_over``.
+    - The branch IS a side chain: its backward runs under ``ops.mode(side_wgrad=False)``, its weight gradients stay on its stream.
+    - A captured stretch must not end with a fork open: every ``fork`` / ``backward`` that records done is followed by a ``join`` (an
+      operator of the main tape, the ``join`` of a ``Tape.cut``) or by ``close`` inside the same stretch.  A join waits ONCE and
+      forgets the event: a later stretch must not wait on an event that belongs to an earlier one."""
+
+    def __init__(self, device, stream=None, enabled: bool = True):
+        self.device, self.stream = device, stream
+        if enabled:
+            self.stream = stream if stream is not None else torch.cuda.Stream(device)
+            self._fork, self._done = torch.cuda.Event(), torch.cuda.Event()
+        self.begin(enabled)
+
+    def begin(self, enabled: bool = True):
+        """A new use (a step): an empty tape, nothing kept, nothing pending.  A branch constructed enabled may sit a step out."""
+        self.enabled = bool(enabled) and self.stream is not None
+        self.tape, self.kept, self._pending = Tape(), [], None
+        return self
+
+    def fork(self, fn, *args, done: bool = True):
+        """``fn(*args)`` on the branch, behind everything queued so far on the current stream -> its result.  ``done=False``: no done
+        event (the branch's next use follows on the same stream: the predictors' backward behind their forward)."""
+        if not self.enabled:
+            return fn(*args)
+        self._fork.record(torch.cuda.current_stream(self.device))
+        self.stream.wait_event(self._fork)
+        with torch.cuda.stream(self.stream):
+            out = fn(*args)
+            if done:
+                self._done.record(self.stream)
+        if done:
+            self._pending = self._done
+        return out
+
+    def _tape_backward(self):
+        with ops.mode(side_wgrad=False):
+            self.kept += _held_tensors(self.tape._ops)
+            self.tape.backward()
+
+    def backward(self):
+        """The backward of the branch's tape, forked here (an empty tape: nothing, so a second call is harmless)."""
+        if not self.tape._ops:
+            return
+        if not self.enabled:
+            return self.tape.backward()
+        self.fork(self._tape_backward)
+
+    def hand_over(self, *tensors):
+        """`tensors` were allocated under the branch; the current stream uses and releases them."""
+        if self.enabled and not torch.cuda.is_current_stream_capturing():
+            cur = torch.cuda.current_stream(self.device)
+            for t in tensors:
+                t.record_stream(cur)
+
+    def join(self):
+        """The current stream waits for what the branch has recorded as done -- once."""
+        if self._pending is not None:
+            torch.cuda.current_stream(self.device).wait_event(self._pending)
+            self._pending = None
+
+    def close(self):
+        """Join if nothing needed the branch's results so far, then let go of what was kept."""
+        self.join()
+        self.kept = []
 
 
 class HipCapture:
