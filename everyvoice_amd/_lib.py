@@ -14,6 +14,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_NAME = "libevmi_hip.so"
 
 EVMI_OK = 0
+EVMI_ERR_UNSUPPORTED = 4
 EVMI_PREC_BF16 = 0
 EVMI_PREC_F32 = 1
 EVMI_MAX_UPSAMPLES = 8
@@ -235,6 +236,10 @@ SYMBOLS = {
     "evmi_weight_norm_fwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     "evmi_weight_norm_bwd_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
     "evmi_normalize_vec_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "evmi_generator_bf16_check": (C.c_int, [C.POINTER(GeneratorConfig)]),
+    "evmi_conv_generic_weight_elems": (C.c_longlong, [C.c_int] * 3),
+    "evmi_conv_generic_relayout_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "evmi_conv_generic_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_longlong] * 3 + [C.c_float] * 3 + [C.c_int, C.c_void_p]),
     "evmi_conv_tc_supported": (C.c_int, [C.c_int] * 4),
     "evmi_conv_tc_relayout_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "evmi_conv_tc_tile_layout": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3),

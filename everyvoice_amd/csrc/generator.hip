@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "conv_tc_generic.h"
 #include "conv_tc_mfma.h"
 #include "resblock_branch_kernel.h"
 #include "resblock_pair_kernel.h"
@@ -38,7 +39,7 @@ int launch_conv1d_f32(const float*, const float*, const float*, const float*, fl
 int launch_conv_transpose1d_f32(const float*, const float*, const float*, float*, int, int, int, int, int,
                                 int, int, float, hipStream_t);
 int launch_tanh_f32(float*, long long, hipStream_t);
-int launch_nct_f32_to_tc_bf16(const float*, bf16_t*, int, int, int, hipStream_t);
+int launch_nct_f32_to_tc_bf16(const float*, bf16_t*, int, int, int, int, hipStream_t);
 int launch_conv_post_tanh(const bf16_t*, const float*, float, float*, int, int, int, int, float, hipStream_t);
 int launch_istft_head(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, hipStream_t);
 int launch_reflect_pad_left1_f32(const float*, float*, long long, int, float, hipStream_t);
@@ -70,7 +71,8 @@ struct DevBuf {
 // One convolution of the bf16 schedule, weights already on the device in kernel layout.
 struct TcConv {
   std::string layer;
-  const ConvTcLaunch* launch = nullptr;
+  const ConvTcLaunch* launch = nullptr;  // a specialised instantiation, or nullptr: the generic-shape kernel (conv_tc_generic.h)
+  std::string kernel;                    // the name a profile shows
   int c_in = 0, c_out = 0, ks = 0, dil = 1, pad = 0;
   size_t w_off = 0;     // element offset into the bf16 weight arena
   size_t bias_off = 0;  // element offset into the fp32 bias arena
@@ -191,60 +193,134 @@ static void relayout_conv(const float* w, int c_out, int c_in, int ks, const Con
       }
 }
 
+// ... and into the generic kernel's zero-padded image (conv_tc_generic.h); w rows hold w_cin <= c_in channels, the rest stay zero
+static void relayout_conv_generic(const float* w, int c_out, int w_cin, int c_in, int ks, std::vector<uint16_t>& arena, size_t off) {
+  for (int m = 0; m < c_out; ++m)
+    for (int j = 0; j < ks; ++j)
+      for (int c = 0; c < w_cin; ++c)
+        arena[off + (size_t)conv_generic_weight_index(c_in, ks, m, j, c)] = f32_to_bf16_bits(w[((size_t)m * w_cin + c) * ks + j]);
+}
+
+// EVMI_CONV_GENERIC=1 (A/B switch, read once): every single convolution of the bf16 schedule on the generic kernel, no fused
+// pair / branch launches -- the generic kernel at the shapes the specialised ones cover
+static bool force_generic() {
+  static const bool on = env_int("EVMI_CONV_GENERIC", 0) == 1;
+  return on;
+}
+
+static std::string generic_kernel_name(const TcConv& t) {
+  char buf[48];
+  snprintf(buf, sizeof buf, "conv_tc_generic<ci%d,co%d,k%d,d%d>", t.c_in, t.c_out, t.ks, t.dil);
+  return buf;
+}
+
+// The generator's kernel lookup: the specialised tables first (find_conv_tc, which the training path keeps to itself), then the
+// generic kernel.  Returns false with t untouched where neither takes the shape.
+static bool pick_generator_conv(TcConv& t) {
+  t.launch = force_generic() ? nullptr : find_conv_tc(t.c_in, t.c_out, t.ks, t.dil);
+  if (t.launch) {
+    t.kernel = t.launch->name;
+    return true;
+  }
+  if (conv_generic_refusal(t.c_in, t.c_out, t.ks, t.dil)) return false;
+  t.kernel = generic_kernel_name(t);
+  return true;
+}
+
+static int round_up8(int v) { return (v + 7) / 8 * 8; }
+
+// What the bf16 path cannot take, named by the configuration field ("" = it takes the configuration).  Host arithmetic only.
+static std::string bf16_refusal(const evmi_generator_config& c) {
+  for (int i = 0; i < c.num_upsamples; ++i) {
+    const int u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
+    if (k < u || (k - u) % 2)
+      return "upsample_kernel_sizes[" + std::to_string(i) + "] = " + std::to_string(k) + " with upsample_rates[" + std::to_string(i) + "] = " +
+             std::to_string(u) + ": the kernel must be at least the rate and differ from it by an even number";
+  }
+  for (int i = 0; i <= c.num_upsamples; ++i)
+    if ((c.upsample_initial_channel >> i) % 8)
+      return "upsample_initial_channel = " + std::to_string(c.upsample_initial_channel) + ": stage " + std::to_string(i) + " has " +
+             std::to_string(c.upsample_initial_channel >> i) + " channels, every stage needs a multiple of 8";
+  for (int j = 0; j < c.num_kernels; ++j) {
+    const int k = c.resblock_kernel_sizes[j];
+    if (k % 2 == 0) return "resblock_kernel_sizes[" + std::to_string(j) + "] = " + std::to_string(k) + ": must be odd";
+    for (int m = 0; m < c.num_dilations[j]; ++m)
+      if ((long long)(k - 1) * c.resblock_dilations[j][m] > kGenericMaxHalo)
+        return "resblock_dilation_sizes[" + std::to_string(j) + "][" + std::to_string(m) + "] = " + std::to_string(c.resblock_dilations[j][m]) +
+               " with kernel " + std::to_string(k) + ": (kernel - 1) * dilation exceeds the halo limit of " + std::to_string(kGenericMaxHalo) + " rows";
+  }
+  if (c.istft_layer) {
+    if (c.istft_n_fft != 16 || c.istft_hop != 4)
+      return "gen_istft_n_fft / gen_istft_hop_size: the iSTFT head takes only n_fft 16 / hop 4 (the reference's gen_istft_* values)";
+    const int cl = c.upsample_initial_channel >> c.num_upsamples;
+    if (!(cl == 32 || cl == 64 || cl == 128))
+      return "upsample_initial_channel: the iSTFT head takes 32, 64 or 128 input channels, not " + std::to_string(cl);
+  }
+  return "";
+}
+
 static int prepare_tc(evmi_generator* g) {
   const auto& c = g->cfg;
   g->tc_ok = false;
-  if (c.istft_layer && (c.istft_n_fft != 16 || c.istft_hop != 4)) {
-    g->tc_why = "iSTFT head: only n_fft 16 / hop 4 (the reference's gen_istft_* values)";
-    return EVMI_OK;
-  }
+  g->tc_why = bf16_refusal(c);
+  if (!g->tc_why.empty()) return EVMI_OK;
   std::vector<uint16_t> warena;
   std::vector<float> barena;
-  auto reserve = [&](TcConv& t) {
-    t.w_off = warena.size();
-    warena.resize(warena.size() + (size_t)t.c_out * t.c_in * t.ks);
-    t.bias_off = barena.size();
-    barena.resize(barena.size() + t.c_out);
-  };
   auto missing = [&](const std::string& what) {
-    g->tc_why = "no MFMA instantiation for " + what;
+    g->tc_why = "no MFMA kernel for " + what;
     return EVMI_OK;
   };
-  // conv_pre
+  // kernel, arena space and weight image of one convolution; w: [c_out][w_cin][ks] fp32 with w_cin <= t.c_in (the rest: zero channels)
+  auto place = [&](TcConv& t, const float* w, int w_cin) -> bool {
+    if (!pick_generator_conv(t)) return false;
+    if (t.launch && w_cin != t.c_in) {  // zero-padded input channels (n_mels 73 .. 79 -> 80): only the generic image holds them
+      if (conv_generic_refusal(t.c_in, t.c_out, t.ks, t.dil)) return false;
+      t.launch = nullptr;
+      t.kernel = generic_kernel_name(t);
+    }
+    t.w_off = warena.size();
+    t.bias_off = barena.size();
+    barena.resize(barena.size() + t.c_out);
+    if (t.launch) {
+      warena.resize(warena.size() + (size_t)t.c_out * t.c_in * t.ks);
+      relayout_conv(w, t.c_out, t.c_in, t.ks, t.launch, warena, t.w_off);
+    } else {
+      warena.resize(warena.size() + (size_t)conv_generic_weight_elems(t.c_in, t.c_out, t.ks), 0);
+      relayout_conv_generic(w, t.c_out, w_cin, t.c_in, t.ks, warena, t.w_off);
+    }
+    return true;
+  };
+  // conv_pre: the time-major mel rows carry zero channels up to a multiple of 8
   {
     TcConv& t = g->tc_pre;
+    t = TcConv();
     t.layer = "conv_pre";
-    t.c_in = c.n_mels; t.c_out = c.upsample_initial_channel; t.ks = 7; t.dil = 1; t.pad = 3;
-    t.launch = find_conv_tc(t.c_in, t.c_out, t.ks, 1);
-    if (!t.launch) return missing("conv_pre c_in=" + std::to_string(t.c_in));
-    reserve(t);
-    relayout_conv(g->host_w["conv_pre.weight"].data(), t.c_out, t.c_in, t.ks, t.launch, warena, t.w_off);
+    t.c_in = round_up8(c.n_mels); t.c_out = c.upsample_initial_channel; t.ks = 7; t.dil = 1; t.pad = 3;
+    if (!place(t, g->host_w["conv_pre.weight"].data(), c.n_mels)) return missing("conv_pre c_in=" + std::to_string(t.c_in));
     memcpy(&barena[t.bias_off], g->host_w["conv_pre.bias"].data(), sizeof(float) * t.c_out);
   }
   // upsamplers in polyphase form
   g->tc_ups.assign(c.num_upsamples, TcConv());
   for (int i = 0; i < c.num_upsamples; ++i) {
     const int u = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
-    if (k != 2 * u) return missing("upsampler with kernel != 2*rate");
+    const int nt = (k + u - 1) / u;  // taps of the polyphase form (2 where k = 2 u)
     const int cin = g->ch(i), cout = g->ch(i + 1);
     TcConv& t = g->tc_ups[i];
     t.layer = "ups." + std::to_string(i);
-    t.c_in = cin; t.c_out = u * cout; t.ks = 2; t.dil = 1; t.pad = 1;
-    t.launch = find_conv_tc(t.c_in, t.c_out, 2, 1);
-    if (!t.launch) return missing(t.layer + " c_in=" + std::to_string(cin));
-    reserve(t);
-    // wc[phi*cout + co][tap][ci]: tap 0 reads x[q-1] with w[ci][co][phi+u], tap 1 reads x[q] with w[ci][co][phi]
+    t.c_in = cin; t.c_out = u * cout; t.ks = nt; t.dil = 1; t.pad = nt - 1;
+    // output t = q u + phi - p: wc[phi*cout + co][tap][ci], tap (nt - 1 - j) reads x[q - j] with w[ci][co][phi + j u], zero where
+    // phi + j u >= k (k = 2 u: tap 0 reads x[q-1] with w[..][phi+u], tap 1 reads x[q] with w[..][phi])
     const std::vector<float>& w = g->host_w["ups." + std::to_string(i) + ".weight"];
     const std::vector<float>& bs = g->host_w["ups." + std::to_string(i) + ".bias"];
-    std::vector<float> wc((size_t)t.c_out * cin * 2);
+    std::vector<float> wc((size_t)t.c_out * cin * nt, 0.f);
     for (int phi = 0; phi < u; ++phi)
       for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci) {
           const size_t m = (size_t)phi * cout + co;
-          wc[(m * cin + ci) * 2 + 0] = w[((size_t)ci * cout + co) * k + phi + u];
-          wc[(m * cin + ci) * 2 + 1] = w[((size_t)ci * cout + co) * k + phi];
+          for (int j = 0; j < nt; ++j)
+            if (phi + j * u < k) wc[(m * cin + ci) * nt + (nt - 1 - j)] = w[((size_t)ci * cout + co) * k + phi + j * u];
         }
-    relayout_conv(wc.data(), t.c_out, cin, 2, t.launch, warena, t.w_off);
+    if (!place(t, wc.data(), cin)) return missing(t.layer + " c_in=" + std::to_string(cin));
     for (int phi = 0; phi < u; ++phi)
       for (int co = 0; co < cout; ++co) barena[t.bias_off + (size_t)phi * cout + co] = bs[co];
   }
@@ -265,10 +341,8 @@ static int prepare_tc(evmi_generator* g) {
           t.c_in = cc; t.c_out = cc; t.ks = k;
           t.dil = which == 1 ? c.resblock_dilations[j][m] : 1;
           t.pad = t.dil * (k - 1) / 2;
-          t.launch = find_conv_tc(cc, cc, k, t.dil);
-          if (!t.launch) return missing(t.layer + " c=" + std::to_string(cc) + " k=" + std::to_string(k));
-          reserve(t);
-          relayout_conv(g->host_w[rb_name(c, n, which, m, "weight")].data(), cc, cc, k, t.launch, warena, t.w_off);
+          if (!place(t, g->host_w[rb_name(c, n, which, m, "weight")].data(), cc))
+            return missing(t.layer + " c=" + std::to_string(cc) + " k=" + std::to_string(k));
           memcpy(&barena[t.bias_off], g->host_w[rb_name(c, n, which, m, "bias")].data(), sizeof(float) * cc);
           convs.push_back(t);
         }
@@ -278,7 +352,7 @@ static int prepare_tc(evmi_generator* g) {
       std::vector<size_t> pair_w;
       for (int m = 0; m < c.num_dilations[j]; ++m) {
         const PairLaunch* pl = nullptr;
-        if (c.resblock_type == 1 && g->use_pairs) pl = find_resblock_pair(cc, k, c.resblock_dilations[j][m]);
+        if (c.resblock_type == 1 && g->use_pairs && !force_generic()) pl = find_resblock_pair(cc, k, c.resblock_dilations[j][m]);
         pairs.push_back(pl);
         size_t off = 0;
         if (pl) {
@@ -321,7 +395,6 @@ static int prepare_tc(evmi_generator* g) {
   // conv_post: w[1][c][7] -> [7][c] fp32
   {
     const int cl = g->ch(c.num_upsamples);
-    if (!(cl == 16 || cl == 32 || cl == 64 || cl == 128)) return missing("conv_post c_in=" + std::to_string(cl));
     const std::vector<float>& w = g->host_w["conv_post.weight"];
     std::vector<float> wk((size_t)7 * cl);
     for (int cidx = 0; cidx < cl; ++cidx)
@@ -410,7 +483,7 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
   const auto& c = g->cfg;
   if (!g->tc_ok) return fail(EVMI_ERR_UNSUPPORTED, "bf16 MFMA path unavailable: " + g->tc_why);
   const size_t se = align_up(stage_elems_max(g, B, T), 64);
-  const size_t in_e = align_up((size_t)B * T * c.n_mels, 64);
+  const size_t in_e = align_up((size_t)B * T * round_up8(c.n_mels), 64);
   EVMI_TRY(g->ws.ensure((in_e + 5 * se) * 2));
   bf16_t* base = (bf16_t*)g->ws.p;
   bf16_t* X0 = base;
@@ -430,15 +503,15 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
     a.out_row_stride = row_stride; a.out_shift = shift; a.out_limit = limit;
     a.pre_slope = pre; a.post_slope = post; a.out_scale = scale; a.accumulate = accumulate;
     EVMI_TRY(rec.begin());
-    EVMI_TRY(launch_conv_tc(t.launch, a, B, s));
+    EVMI_TRY(t.launch ? launch_conv_tc(t.launch, a, B, s) : launch_conv_generic(a, t.c_in, t.ks, B, s));
     const double flops = 2.0 * B * (double)n_rows * t.c_out * t.ks * t.c_in;
     const double bytes = 2.0 * B * ((double)t_in * t.c_in + (double)limit * (1 + (res ? 1 : 0) + (accumulate ? 1 : 0))) +
                          2.0 * t.c_out * t.ks * t.c_in;
-    return rec.end(t.launch->name, t.layer, flops, bytes);
+    return rec.end(t.kernel.c_str(), t.layer, flops, bytes);
   };
 
   EVMI_TRY(rec.begin());
-  EVMI_TRY(launch_nct_f32_to_tc_bf16(mel, X0, B, c.n_mels, T, s));
+  EVMI_TRY(launch_nct_f32_to_tc_bf16(mel, X0, B, c.n_mels, g->tc_pre.c_in, T, s));
   EVMI_TRY(rec.end("nct_f32_to_tc_bf16", "mel", 0.0, 6.0 * B * T * c.n_mels));
 
   // conv_pre -> A (already leaky-relu'd for the first upsampler)
@@ -454,7 +527,8 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
     bf16_t* P[2] = {buf[1], buf[2]};
     bf16_t* T1 = buf[3];
     // A is read by the upsampler only; the stage output ACC reuses buf[4] after that
-    EVMI_TRY(run(g->tc_ups[i], A, len, len + 1, U, nullptr, (long long)u * cout, -(long long)p * cout,
+    // rows q = (t + p) / u of the polyphase form, t < len u (len + 1 of them where k = 2 u)
+    EVMI_TRY(run(g->tc_ups[i], A, len, (len_out - 1 + p) / u + 1, U, nullptr, (long long)u * cout, -(long long)p * cout,
                  (long long)len_out * cout, 1.f, 1.f, 1.f, 0));
     bf16_t* ACC = buf[4];
     const bool last_stage = i == c.num_upsamples - 1;
@@ -704,7 +778,22 @@ int evmi_generator_finalize(evmi_generator* g) {
   }
   EVMI_TRY(prepare_tc(g));
   g->finalized = true;
+  // what the bf16 path cannot take is reported here, not by the first forward; the object is finalized all the same and runs
+  // EVMI_PREC_F32
+  if (!g->tc_ok) return fail(EVMI_ERR_UNSUPPORTED, "finalize: bf16 path unavailable (EVMI_PREC_F32 takes this configuration): " + g->tc_why);
   return EVMI_OK;
+}
+
+int evmi_generator_bf16_check(const evmi_generator_config* cfg) {
+  if (!cfg) return fail(EVMI_ERR_INVALID_ARG, "generator_bf16_check: null argument");
+  const evmi_generator_config& c = *cfg;
+  bool counts_ok = c.num_upsamples > 0 && c.num_upsamples <= EVMI_MAX_UPSAMPLES && c.num_kernels > 0 && c.num_kernels <= EVMI_MAX_RESBLOCK_KERNELS;
+  for (int j = 0; counts_ok && j < c.num_kernels; ++j) counts_ok = c.num_dilations[j] > 0 && c.num_dilations[j] <= EVMI_MAX_DILATIONS;
+  if (counts_ok) {  // (bf16_refusal walks the arrays by these counts)
+    const std::string why = bf16_refusal(c);
+    if (!why.empty()) return fail(EVMI_ERR_UNSUPPORTED, why);
+  }
+  return validate_cfg(c);
 }
 
 int evmi_generator_hop(const evmi_generator* g) { return g ? g->hop() : 0; }
@@ -712,7 +801,7 @@ int evmi_generator_hop(const evmi_generator* g) { return g ? g->hop() : 0; }
 int64_t evmi_generator_workspace_bytes(const evmi_generator* g, int B, int T, int precision) {
   if (!g || B <= 0 || T <= 0) return 0;
   const size_t se = align_up(stage_elems_max(g, B, T), 64);
-  if (precision == EVMI_PREC_BF16) return (int64_t)((align_up((size_t)B * T * g->cfg.n_mels, 64) + 5 * se) * 2);
+  if (precision == EVMI_PREC_BF16) return (int64_t)((align_up((size_t)B * T * round_up8(g->cfg.n_mels), 64) + 5 * se) * 2);
   return (int64_t)(5 * se * 4);
 }
 

@@ -106,6 +106,13 @@ class Generator(nn.Module):
         post_out = config.gen_istft_n_fft + 2 if m.istft_layer else 1
         self.conv_post = _ConvParams(post_out, ch_last, 7, bias=post_out)
         self._c_cfg = _model_cfg_to_c(config)
+        if precision == "bf16":
+            # what the bf16 kernels cannot take is refused here, not by the first forward (host arithmetic: no GPU needed)
+            lib = _lib.load()
+            if lib.evmi_generator_bf16_check(C.byref(self._c_cfg)) != _lib.EVMI_OK:
+                why = lib.evmi_last_error()
+                raise ValueError(f"precision=\"bf16\" does not take this configuration: {why.decode() if why else '?'}; "
+                                 "precision=\"f32\" takes it")
         object.__setattr__(self, "_handle", None)
         self._uploaded_version = None
         self.reset_parameters()
@@ -170,7 +177,13 @@ class Generator(nn.Module):
                     f"evmi_generator_set_weight({name})",
                 )
             with torch.cuda.device(index):  # finalize uploads to the handle's device: the caller's current device is left alone
-                _lib.check(lib.evmi_generator_finalize(self._handle), "evmi_generator_finalize")
+                rc = lib.evmi_generator_finalize(self._handle)
+                # "unsupported" from a configuration that bf16 refuses: the object is finalized and runs EVMI_PREC_F32, which is all
+                # the other precisions ask of it (any other failure, and this one in bf16, is raised)
+                bf16_refused = (rc == _lib.EVMI_ERR_UNSUPPORTED and self.precision != "bf16"
+                                and lib.evmi_generator_bf16_check(C.byref(self._c_cfg)) != _lib.EVMI_OK)
+                if not bf16_refused:
+                    _lib.check(rc, "evmi_generator_finalize")
             self._uploaded_version = ver
         return lib
 

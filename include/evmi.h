@@ -175,8 +175,16 @@ int evmi_generator_num_weights(const evmi_generator* g);
 int evmi_generator_weight_info(const evmi_generator* g, int i, char* name, int name_len,
                                int64_t* numel);
 /* Re-lays out and uploads the weights for both precisions.  Must be called after all
- * evmi_generator_set_weight calls and before the first forward. */
+ * evmi_generator_set_weight calls and before the first forward.
+ * A configuration that EVMI_PREC_BF16 cannot take is reported HERE, not by the first forward: EVMI_ERR_UNSUPPORTED, the message
+ * names the configuration field; the object is finalized all the same and runs EVMI_PREC_F32. */
 int evmi_generator_finalize(evmi_generator* g);
+/* The same question before any weight exists (host arithmetic, no GPU): EVMI_OK when EVMI_PREC_BF16 takes `cfg`, else
+ * EVMI_ERR_UNSUPPORTED / EVMI_ERR_INVALID_ARG with evmi_last_error() naming the field.  bf16 takes any n_mels, any stage channel
+ * count that is a multiple of 8, any odd resblock kernel with (kernel - 1) * dilation <= 256, any upsampler with kernel >= rate
+ * and (kernel - rate) even; shapes outside the specialised kernel tables run on the generic-shape kernel (evmi_conv_generic_bf16).
+ * The iSTFT head: gen_istft_n_fft 16 / hop 4 and 32 / 64 / 128 input channels only. */
+int evmi_generator_bf16_check(const evmi_generator_config* cfg);
 
 /* Samples produced per mel frame (prod(upsample_rates) [* istft_hop]). */
 int evmi_generator_hop(const evmi_generator* g);
@@ -428,6 +436,23 @@ int evmi_conv_tc_relayout_batched_f32(const float* w_base_dev, void* dst_base_bf
 int evmi_conv_tc_tm_bf16(const void* x_tm, const void* w_laid, const float* bias_dev, const void* res_tm, const void* mask_tm, void* out_tm,
                          int B, int T, int Tp, int PL, int c_in, int c_out, int ks, int dil, float pre_slope, float post_slope,
                          float mask_slope, float out_scale, void* stream);
+/* ---- The generic-shape bf16 MFMA convolution (csrc/conv_tc_generic.hip): the kernel the generator falls back to where the
+ * specialised tables above hold no instantiation.  c_in, c_out (multiples of 8), ks >= 1 and dil >= 1 are run-time values,
+ * (ks - 1) * dil <= 256.  Plain tensors: x bf16 [B][t_in][c_in], out (and res, indexed like out) bf16, B items of out_limit elements.
+ *   out[flat] = post( [accumulate ? out[flat] : 0] + out_scale * ( res[flat] + bias[m] + sum_j sum_c W[m][c][j] * pre(x[r + j*dil - pad][c]) ) )
+ *   for rows r < n_rows, flat = r * out_row_stride + m + out_shift; elements with flat outside [0, out_limit) are dropped (a plain
+ *   convolution: out_row_stride = c_out, out_shift = 0, out_limit = n_rows * c_out; the polyphase transposed convolution of rate u,
+ *   padding p: c_out = u * channels, out_row_stride = c_out, out_shift = -p * channels).  Rows of x outside [0, t_in) read as zero.
+ *   pre / post: leaky-ReLU slopes (1 = none).  res may be NULL.  The three out_* values are multiples of 8 elements.
+ *   evmi_conv_generic_weight_elems   bf16 elements of the weight image (zero padding included; 0 for a non-positive size)
+ *   evmi_conv_generic_relayout_f32   w fp32 [c_out][c_in][ks] (device) -> that image
+ * Items of a batch are independent and the summation order of an output element does not depend on its position: an item alone
+ * gives the bits it gives inside a batch. */
+long long evmi_conv_generic_weight_elems(int c_in, int c_out, int ks);
+int evmi_conv_generic_relayout_f32(const float* w_dev, void* dst_bf16_dev, int c_in, int c_out, int ks, void* stream);
+int evmi_conv_generic_bf16(const void* x, const void* w_laid, const float* bias_dev, const void* res, void* out, int B, int t_in, int n_rows,
+                           int c_in, int c_out, int ks, int dil, int pad, long long out_row_stride, long long out_shift, long long out_limit,
+                           float pre_slope, float post_slope, float out_scale, int accumulate, void* stream);
 long long evmi_conv1d_wgrad_tm_bf16_ws_elems(long long rows, int c_in, int c_out, int k, int dil);
 int evmi_conv1d_wgrad_tm_bf16(const void* x_tm, const void* dy_tm, float* dw_dev, float* ws_dev, long long ws_elems, long long rows,
                               int c_in, int c_out, int k, int pad, int dil, int accumulate, void* stream);
