@@ -1,5 +1,6 @@
 // C-ABI entry points that map 1:1 onto a kernel family (see include/evmi.h).
 #include "common.h"
+#include "mel_frontend.h"
 
 namespace evmi {
 int length_regulate(const void*, const int64_t*, void*, int64_t*, int32_t*, int, int, int, int, int, hipStream_t);
@@ -8,8 +9,6 @@ int launch_conv1d_f32(const float*, const float*, const float*, const float*, fl
                       int, int, int, int, int, float, float, int, hipStream_t);
 int launch_conv_transpose1d_f32(const float*, const float*, const float*, float*, int, int, int, int, int,
                                 int, int, float, hipStream_t);
-int launch_mel_frontend(const float*, const float*, const float*, float*, float*, float*, int, int, int, int, int,
-                        int, int, int, int, hipStream_t, const int* lens);
 }  // namespace evmi
 
 using namespace evmi;
@@ -54,11 +53,8 @@ int evmi_mel_spectrogram_f32(const float* audio_dev, const float* dft_basis_dev,
                              int hop, int n_bins_padded, int n_mels, int apply_log, void* stream) {
   if (!audio_dev || !dft_basis_dev || !mel_basis_dev || !mel_dev)
     return fail(EVMI_ERR_INVALID_ARG, "mel_spectrogram: null pointer");
-  if (B <= 0 || n_samples <= 0 || n_mels <= 0 || n_bins_padded % 16 || n_bins_padded < n_fft / 2 + 1)
-    return fail(EVMI_ERR_INVALID_ARG, "mel_spectrogram: bad shape");
-  const int n_frames = 1 + n_samples / hop;
-  return launch_mel_frontend(audio_dev, dft_basis_dev, mel_basis_dev, mel_dev, energy_dev, mag_dev, B, n_samples,
-                             n_frames, n_fft, hop, n_bins_padded, n_fft / 2 + 1, n_mels, apply_log, (hipStream_t)stream, nullptr);
+  return launch_mel_frontend("mel_spectrogram", audio_dev, dft_basis_dev, mel_basis_dev, mel_dev, energy_dev, mag_dev, B, n_samples, n_fft,
+                             n_fft, hop, n_bins_padded, n_mels, apply_log, (hipStream_t)stream, nullptr);
 }
 
 int evmi_mel_spectrogram_ragged_f32(const float* audio_dev, const int* lens_dev, const float* dft_basis_dev, const float* mel_basis_dev,
@@ -66,11 +62,29 @@ int evmi_mel_spectrogram_ragged_f32(const float* audio_dev, const int* lens_dev,
                                     int n_bins_padded, int n_mels, int apply_log, void* stream) {
   if (!audio_dev || !lens_dev || !dft_basis_dev || !mel_basis_dev || !mel_dev)
     return fail(EVMI_ERR_INVALID_ARG, "mel_spectrogram_ragged: null pointer");
-  if (B <= 0 || n_samples_max <= 0 || n_mels <= 0 || n_bins_padded % 16 || n_bins_padded < n_fft / 2 + 1)
-    return fail(EVMI_ERR_INVALID_ARG, "mel_spectrogram_ragged: bad shape");
-  const int n_frames = 1 + n_samples_max / hop;
-  return launch_mel_frontend(audio_dev, dft_basis_dev, mel_basis_dev, mel_dev, energy_dev, mag_dev, B, n_samples_max,
-                             n_frames, n_fft, hop, n_bins_padded, n_fft / 2 + 1, n_mels, apply_log, (hipStream_t)stream, lens_dev);
+  return launch_mel_frontend("mel_spectrogram_ragged", audio_dev, dft_basis_dev, mel_basis_dev, mel_dev, energy_dev, mag_dev, B, n_samples_max,
+                             n_fft, n_fft, hop, n_bins_padded, n_mels, apply_log, (hipStream_t)stream, lens_dev);
+}
+
+int evmi_mel_spectrogram_win_f32(const float* audio_dev, const int* lens_dev, const float* dft_basis_dev, const float* mel_basis_dev,
+                                 float* mel_dev, float* energy_dev, float* mag_dev, int B, int n_samples_max, int n_fft, int win_length,
+                                 int hop, int n_bins_padded, int n_mels, int apply_log, void* stream) {
+  if (!audio_dev || !dft_basis_dev || !mel_basis_dev || !mel_dev)
+    return fail(EVMI_ERR_INVALID_ARG, "mel_spectrogram_win: null pointer");
+  return launch_mel_frontend("mel_spectrogram_win", audio_dev, dft_basis_dev, mel_basis_dev, mel_dev, energy_dev, mag_dev, B, n_samples_max,
+                             n_fft, win_length, hop, n_bins_padded, n_mels, apply_log, (hipStream_t)stream, lens_dev);
+}
+
+int evmi_mel_spectrogram_plan(int n_fft, int win_length, int hop, int n_mels, int* k0, int* k1, int* frame_stride_words, int* chunk_tiles,
+                              long long* lds_bytes) {
+  MelPlan p;
+  if (int rc = mel_plan("mel_spectrogram_plan", n_fft, win_length, hop, n_mels, (n_fft / 2 + 1 + 15) / 16 * 16, &p)) return rc;
+  if (k0) *k0 = p.k0;
+  if (k1) *k1 = p.k1;
+  if (frame_stride_words) *frame_stride_words = p.frame_stride;
+  if (chunk_tiles) *chunk_tiles = p.chunk_tiles;
+  if (lds_bytes) *lds_bytes = p.lds_bytes;
+  return EVMI_OK;
 }
 
 }  // extern "C"

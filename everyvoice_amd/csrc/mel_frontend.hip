@@ -10,9 +10,16 @@
 // The DFT is a GEMM [32 frames x n_fft] x [n_fft x 2*(n_fft/2+1)] on the fp32-input matrix cores
 // (v_mfma_f32_32x32x2_f32: exact fp32 fmaf chains, 157 TFLOP/s class) against a window-folded basis
 // held in HBM/L2 (n_fft=1024: 4.2 MB).  The frame matrix is never materialised: the padded audio
-// segment of a 32-frame block sits once in LDS with a skew of one word per hop (index s + s/hop),
-// which makes the 32 lanes of an A-fragment read (stride hop) hit 32 distinct banks.
+// segment of a 32-frame block sits once in LDS, skewed by one word per hop when the hop is even (index
+// s + s/hop) and not at all when it is odd, so the 32 lanes of an A-fragment read are always an odd
+// number of words apart (hop + 1 or hop) and hit 32 distinct banks.
+//
+// A window shorter than n_fft sits centred in it (torch.stft): basis rows outside [left, left + win) are
+// exactly zero, so the k-loop runs over [k0, k1) only (left rounded down / left + win rounded up to even:
+// the MFMA takes two k per step) and only the samples that loop reads are staged.  A dropped product is
+// a * 0 added to a finite accumulator: the result equals the full loop's bit for bit.
 #include "common.h"
+#include "mel_frontend.h"
 
 namespace evmi {
 
@@ -35,14 +42,18 @@ __device__ __forceinline__ int reflect_index(int i, int n) {
 // chunks and walk the bins in ascending order whatever the chunking, so the result does not depend on it.
 constexpr int MEL_ROWS_PER_THREAD = 8;  // n_mels <= 16 * 8
 
+// SKEW: 1 for an even hop (index s + s / hop), 0 for an odd one (index s); k0, k1: the even-aligned support of the window
+template <int SKEW>
 __global__ __launch_bounds__(MEL_THREADS) void mel_frontend_kernel(
     const float* __restrict__ audio, const float* __restrict__ basis_ri, const float* __restrict__ melb,
     float* __restrict__ out, float* __restrict__ energy, float* __restrict__ mag_out, int n_samples_max, int n_frames,
-    int n_fft, int hop, int nb_pad, int n_bins, int n_mels, int apply_log, int chunk_tiles, const int* __restrict__ lens) {
+    int n_fft, int hop, int nb_pad, int n_bins, int n_mels, int apply_log, int chunk_tiles, const int* __restrict__ lens,
+    int k0, int k1) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int seg = (MEL_FRAMES - 1) * hop + n_fft;           // audio samples a block needs
-  float* As = reinterpret_cast<float*>(smem);                // skewed: index s + s / hop
-  const int as_words = seg + seg / hop + 1;
+  const int kspan = k1 - k0;
+  const int seg = (MEL_FRAMES - 1) * hop + kspan;           // audio samples a block reads: sample s is k0 + s of frame 0
+  float* As = reinterpret_cast<float*>(smem);                // skewed: index s + SKEW * (s / hop)
+  const int as_words = seg + (SKEW ? seg / hop : 0) + 1;
   float* Ls = As + ((as_words + 3) & ~3);                    // log-mel rows [MEL_FRAMES][n_mels + 1] for the energy reduction
   float* Ms = Ls + ((MEL_FRAMES * (n_mels + 1) + 3) & ~3);   // magnitudes of one bin chunk [MEL_FRAMES][16 * chunk_tiles + 1]
   const int ms_stride = 16 * chunk_tiles + 1;
@@ -57,16 +68,16 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_frontend_kernel(
   const int pad = n_fft / 2;
 
   for (int s = tid; s < seg; s += MEL_THREADS) {
-    const int g = f0 * hop + s - pad;  // position in the un-padded signal
+    const int g = f0 * hop + k0 + s - pad;  // position in the un-padded signal
     // positions beyond the reflect-padded signal only feed frames >= n_frames (never stored)
     const float v = (g >= -pad && g <= n_samples - 1 + pad) ? ab[reflect_index(g, n_samples)] : 0.f;
-    As[s + s / hop] = v;
+    As[SKEW ? s + s / hop : s] = v;
   }
   __syncthreads();
 
   const int n_col_tiles = (2 * nb_pad) / 32;
   const int i = lane & 31, kh = lane >> 5;
-  const int a_base = i * hop + i;  // skewed start of frame i: (i*hop) + (i*hop)/hop
+  const int a_base = i * (hop + SKEW);  // (skewed) start of frame i: (i*hop) + (i*hop)/hop
   const int fr = tid & 31, mg = tid >> 5;  // mel projection: thread -> (frame, mel rows mg, mg + 16, ...)
   float macc[MEL_ROWS_PER_THREAD];
 #pragma unroll
@@ -80,13 +91,13 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_frontend_kernel(
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float* bcol = basis_ri + ct * 32 + i;  // column of this lane
       const int ld = 2 * nb_pad;
+      const float* bcol = basis_ri + (long long)k0 * ld + ct * 32 + i;  // column of this lane, from basis row k0
 #pragma unroll 8
-      for (int k = 0; k < n_fft; k += 2) {
+      for (int k = 0; k < kspan; k += 2) {
         const int kk = k + kh;
-        // frame i, sample kk: skewed index a_base + kk + kk / hop  (the window is folded into the basis)
-        const float av = As[a_base + kk + kk / hop];
+        // frame i, sample k0 + kk: (skewed) index a_base + kk + kk / hop  (the window is folded into the basis)
+        const float av = As[SKEW ? a_base + kk + kk / hop : a_base + kk];
         const float bv = bcol[(long long)kk * ld];
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
       }
@@ -144,27 +155,51 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_frontend_kernel(
   }
 }
 
-int launch_mel_frontend(const float* audio, const float* basis_ri, const float* melb, float* out, float* energy,
-                        float* mag_out, int B, int n_samples, int n_frames, int n_fft, int hop, int nb_pad,
-                        int n_bins, int n_mels, int apply_log, hipStream_t s, const int* lens) {
-  if (n_fft % hop || n_fft % 2 || hop <= 0) return fail(EVMI_ERR_UNSUPPORTED, "mel: n_fft must be a multiple of hop");
-  if (n_samples <= n_fft / 2) return fail(EVMI_ERR_INVALID_ARG, "mel: reflect padding needs n_samples > n_fft/2");
-  if (n_mels > MEL_ROWS_PER_THREAD * (MEL_THREADS / 32)) return fail(EVMI_ERR_UNSUPPORTED, "mel: n_mels > 128");
-  const int seg = (MEL_FRAMES - 1) * hop + n_fft;
-  const size_t as_words = (seg + seg / hop + 1 + 3) & ~3;
-  const size_t ls_words = (MEL_FRAMES * (n_mels + 1) + 3) & ~3;
-  const size_t budget = 160 * 1024 / sizeof(float);
+// The geometry of one launch, host arithmetic only: what evmi_mel_spectrogram_plan reports and what the launch uses.
+int mel_plan(const char* who, int n_fft, int win, int hop, int n_mels, int nb_pad, MelPlan* p) {
+  const std::string w(who);
+  if (n_fft <= 0 || n_fft % 2) return fail(EVMI_ERR_UNSUPPORTED, w + ": n_fft = " + std::to_string(n_fft) + " must be even and positive");
+  if (win < 1 || win > n_fft)
+    return fail(EVMI_ERR_INVALID_ARG, w + ": win_length = " + std::to_string(win) + " outside [1, n_fft = " + std::to_string(n_fft) + "]");
+  if (hop < 1 || hop > n_fft)
+    return fail(EVMI_ERR_INVALID_ARG, w + ": hop = " + std::to_string(hop) + " outside [1, n_fft = " + std::to_string(n_fft) + "]");
+  if (n_mels < 1) return fail(EVMI_ERR_INVALID_ARG, w + ": n_mels = " + std::to_string(n_mels) + " must be positive");
+  if (n_mels > MEL_ROWS_PER_THREAD * (MEL_THREADS / 32)) return fail(EVMI_ERR_UNSUPPORTED, w + ": n_mels = " + std::to_string(n_mels) + " > 128");
+  if (nb_pad % 16 || nb_pad < n_fft / 2 + 1) return fail(EVMI_ERR_INVALID_ARG, w + ": bad shape (n_bins_padded)");
+  const int left = (n_fft - win) / 2;
+  p->k0 = left & ~1;
+  p->k1 = (left + win + 1) & ~1;  // <= n_fft: n_fft is even
+  p->skew = (hop & 1) ? 0 : 1;    // frame rows hop + skew words apart: always odd
+  p->frame_stride = hop + p->skew;
+  const long long seg = (long long)(MEL_FRAMES - 1) * hop + (p->k1 - p->k0);
+  const long long as_words = (seg + (p->skew ? seg / hop : 0) + 1 + 3) & ~3LL;
+  const long long ls_words = (MEL_FRAMES * (n_mels + 1) + 3) & ~3;
+  const long long budget = 160 * 1024 / sizeof(float);
   const int n_col_tiles = (2 * nb_pad) / 32;
-  if (as_words + ls_words + (size_t)MEL_FRAMES * 17 > budget) return fail(EVMI_ERR_UNSUPPORTED, "mel: n_fft / hop too large for the LDS tile");
+  if (as_words + ls_words + MEL_FRAMES * 17 > budget)
+    return fail(EVMI_ERR_UNSUPPORTED, w + ": n_fft = " + std::to_string(n_fft) + ", win_length = " + std::to_string(win) + ", hop = " +
+                                          std::to_string(hop) + ": the audio tile of 32 frames does not fit the 160 KB LDS budget");
   // the largest bin chunk that fits beside the audio segment, then the chunks evened out
   int max_tiles = (int)(((budget - as_words - ls_words) / MEL_FRAMES - 1) / 16);
   if (max_tiles > n_col_tiles) max_tiles = n_col_tiles;
   const int n_chunks = (n_col_tiles + max_tiles - 1) / max_tiles;
-  const int chunk_tiles = (n_col_tiles + n_chunks - 1) / n_chunks;
-  const size_t lds = (as_words + ls_words + (size_t)MEL_FRAMES * (16 * chunk_tiles + 1)) * sizeof(float);
+  p->chunk_tiles = (n_col_tiles + n_chunks - 1) / n_chunks;
+  p->lds_bytes = (as_words + ls_words + (long long)MEL_FRAMES * (16 * p->chunk_tiles + 1)) * (long long)sizeof(float);
+  return EVMI_OK;
+}
+
+int launch_mel_frontend(const char* who, const float* audio, const float* basis_ri, const float* melb, float* out, float* energy,
+                        float* mag_out, int B, int n_samples, int n_fft, int win, int hop, int nb_pad, int n_mels, int apply_log,
+                        hipStream_t s, const int* lens) {
+  MelPlan p;
+  if (int rc = mel_plan(who, n_fft, win, hop, n_mels, nb_pad, &p)) return rc;
+  if (B <= 0 || n_samples <= 0) return fail(EVMI_ERR_INVALID_ARG, std::string(who) + ": bad shape");
+  if (n_samples <= n_fft / 2) return fail(EVMI_ERR_INVALID_ARG, std::string(who) + ": reflect padding needs n_samples > n_fft/2");
+  const int n_frames = 1 + n_samples / hop, n_bins = n_fft / 2 + 1;
   dim3 grid((n_frames + MEL_FRAMES - 1) / MEL_FRAMES, B);
-  if (int rc = launch_with_lds(mel_frontend_kernel, grid, dim3(MEL_THREADS), lds, s, audio, basis_ri, melb, out, energy, mag_out, n_samples,
-                               n_frames, n_fft, hop, nb_pad, n_bins, n_mels, apply_log, chunk_tiles, lens))
+  auto kernel = p.skew ? mel_frontend_kernel<1> : mel_frontend_kernel<0>;
+  if (int rc = launch_with_lds(kernel, grid, dim3(MEL_THREADS), (size_t)p.lds_bytes, s, audio, basis_ri, melb, out, energy, mag_out, n_samples,
+                               n_frames, n_fft, hop, nb_pad, n_bins, n_mels, apply_log, p.chunk_tiles, lens, p.k0, p.k1))
     return rc;
   EVMI_LAUNCH_CHECK("mel_frontend");
   return EVMI_OK;

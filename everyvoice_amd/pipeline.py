@@ -71,6 +71,11 @@ def save_wav(audio: torch.Tensor, path, sr: int, bits_per_sample: int = 16) -> N
         w.writeframes(pcm.tobytes())
 
 
+def pcm16_round_trip(audio: torch.Tensor) -> torch.Tensor:
+    """Host float audio as save_wav writes it and load_wav reads it back: rounded to 16-bit PCM (file-format plumbing)."""
+    return torch.round(audio.to(torch.float32) * 32768.0).clamp_(-32768.0, 32767.0) / 32768.0
+
+
 def save_tensor(tensor: torch.Tensor, path) -> None:
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
@@ -225,11 +230,12 @@ def _effects(sox_effects) -> list[Effect]:
 
 
 def process_audio_batch(wavs: list[torch.Tensor], sr: int, cfg: AudioConfig, device, normalize: bool = True, resample_rate: int | None = None,
-                        sox_effects=None):
+                        sox_effects=None, hop_size: int | None = None):
     """The device part of process_audio for a batch of gated utterances at one source rate: loudness gate -> mix-down -> the SoX
     effect chain ``sox_effects`` (sox.py; None, [] and the default ``[["channels", "1"]]`` are the mix-down alone) -> resample
-    -> peak normalise -> truncate to a multiple of the hop.  wavs: [channels_i, S_i] host tensors.  An utterance the chain leaves
-    shorter than one hop is skipped and counted under "audio_empty".
+    -> peak normalise -> truncate to a multiple of the hop (``hop_size``, default ``cfg.fft_hop_size``: process_audio(..., hop_size=),
+    preprocessor.py:131).  wavs: [channels_i, S_i] host tensors.  An utterance the chain leaves shorter than one hop is skipped and
+    counted under "audio_empty".
     -> (audio [n, t_max] on the device, lens [n] python ints (multiples of the hop), kept indices, {reason: count})."""
     from . import _lib
 
@@ -276,7 +282,8 @@ def process_audio_batch(wavs: list[torch.Tensor], sr: int, cfg: AudioConfig, dev
         _lib.check(_lib.load().evmi_peak_normalize_f32(x.data_ptr(), y.data_ptr(), lens_t.data_ptr(), x.shape[0], x.shape[1], 0.95,
                                                        _lib.current_stream_ptr(x.device)), "evmi_peak_normalize_f32")
         x = y
-    lens = [L // cfg.fft_hop_size * cfg.fft_hop_size for L in lens]
+    hop = int(hop_size or cfg.fft_hop_size)
+    lens = [L // hop * hop for L in lens]
     if effects and min(lens) == 0:  # trimmed to less than one hop (the reference fails there: torch.max of an empty tensor)
         rows = [j for j, L in enumerate(lens) if L > 0]
         counters["audio_empty"] = counters.get("audio_empty", 0) + len(lens) - len(rows)
@@ -324,6 +331,10 @@ class GpuPreprocessor:
         self.device = torch.device(device)
         self.batch_items = batch_items
         self.pitch = pitch  # also write pitch/<...>--pitch.pt (FastSpeech2's pitch targets: WORLD's DIO + StoneMask on the device, see extract_pitch)
+        in_sr, out_sr = self.cfg.input_sampling_rate, self.cfg.output_sampling_rate
+        if out_sr <= 0 or in_sr <= 0 or out_sr % in_sr:  # (the reference floors the ratio silently; nothing downstream can use such a pair)
+            raise ValueError(f"preprocessing.audio: output_sampling_rate {out_sr} must be a positive integer multiple of input_sampling_rate {in_sr}")
+        self.rate_change = out_sr // in_sr
         self.transform = MelSpectrogram(self.cfg.n_fft, self.cfg.fft_window_size, self.cfg.fft_hop_size,
                                         self.cfg.input_sampling_rate, self.cfg.n_mels, self.cfg.f_min, self.cfg.f_max)
         # spec_type "mel" / "linear" (heavy.py:59-68, 101-107): the generic transforms, one utterance at a time (the ragged one-launch
@@ -334,6 +345,14 @@ class GpuPreprocessor:
                 raise ValueError(f"preprocessing.audio.spec_type {self.cfg.spec_type!r}: a real-valued spectrogram type is needed")
             self.generic = get_spectral_transform(self.cfg.spec_type, self.cfg.n_fft, self.cfg.fft_window_size, self.cfg.fft_hop_size,
                                                   self.cfg.input_sampling_rate, self.cfg.n_mels, self.cfg.f_min, self.cfg.f_max)
+        # the output side of a vocoder that upsamples (preprocessor.py:112-121): the same transform at n_fft c / win c / hop c.  The
+        # reference hands it the INPUT sampling rate (so its mel filters sit at 1 / c of the output-rate audio's frequencies); reproduced.
+        self.output_transform = None
+        if self.rate_change > 1:
+            c = self.rate_change
+            self.output_transform = get_spectral_transform(self.cfg.spec_type, self.cfg.n_fft * c, self.cfg.fft_window_size * c,
+                                                           self.cfg.fft_hop_size * c, self.cfg.input_sampling_rate, self.cfg.n_mels,
+                                                           self.cfg.f_min, self.cfg.f_max)
         self.counters: dict[str, int] = {}
         self._interp = None
         self._source_data: dict = {}  # label -> the source_data entry of the current process() call (the .config-lock records it)
@@ -451,6 +470,8 @@ class GpuPreprocessor:
                     save_tensor(pitch_host[j, :frames].clone(), feature_path(save_dir, "pitch", *ids, "pitch.pt"))
                 self.counters["processed_files"] = self.counters.get("processed_files", 0) + 1
                 kept.append(dict(it, frames=frames, samples=n))
+            if self.rate_change > 1:
+                self._process_output_rate([group[i] for i in kept_idx], sr, effects, save_dir)
 
         for it in items:
             audio, info = gate_audio(it["wav"], self.cfg)
@@ -464,6 +485,32 @@ class GpuPreprocessor:
             flush(sr)
         self.save_config_lock(save_dir, in_progress=False)
         return kept
+
+    def _process_output_rate(self, group: list, sr: int, effects, save_dir) -> None:
+        """The output-rate side of the kept items of one batch (preprocessor.py:562-581, 898-915): the same chain from the file's rate
+        straight to output_sampling_rate, truncated to a multiple of hop c -> ``audio-{output_sr}.wav``, and its log-mel through the
+        output transform -> ``spec-{output_sr}-{spec_type}.pt``.  Counters are not touched (the reference's update_counters=False).
+        The reference saves this audio to the INPUT path (its process_spec then reads the output path): a slip, not reproduced."""
+        out_sr, hop = self.cfg.output_sampling_rate, self.cfg.fft_hop_size * self.rate_change
+        x, lens, kept_idx, _ = process_audio_batch([a for _, a in group], sr, self.cfg, self.device, True, out_sr, effects, hop_size=hop)
+        if not kept_idx:
+            return
+        # The spec is taken of the audio as the file holds it, PCM-16 rounding included: the reference's process_spec reads the saved file
+        # back (preprocessor.py:898-915).  It matters here as it does not on the input side: the band above the input rate's Nyquist
+        # frequency holds only the resampling filter's residue, and the mel rows that cover it move by 4e-3 under that rounding.
+        x_host = pcm16_round_trip(x[:, : max(lens)].cpu())
+        x = x_host.to(self.device)
+        if self.generic is None:
+            mel = self.output_transform(x, log=True, lens=torch.tensor(lens, dtype=torch.int32))
+        else:
+            mel = torch.nn.utils.rnn.pad_sequence([torch.log(torch.clamp(self.output_transform(x[j, : lens[j]]), min=1e-5)).t()
+                                                   for j in range(len(lens))], batch_first=True).transpose(1, 2)
+        mel_host = mel.cpu()
+        for j, i in enumerate(kept_idx):
+            it = group[i][0]
+            ids = (it["basename"], it.get("speaker", "default"), it.get("language", "default"))
+            save_wav(x_host[j, : lens[j]], feature_path(save_dir, "audio", *ids, f"audio-{out_sr}.wav"), out_sr, self.cfg.target_bit_depth)
+            save_tensor(mel_host[j, :, : lens[j] // hop].clone(), feature_path(save_dir, "spec", *ids, f"spec-{out_sr}-{self.cfg.spec_type}.pt"))
 
     def process_attn_prior(self, item: dict, frames: int, save_dir, overwrite: bool = False) -> list[Path]:
         """The ``attn`` stage (preprocessor.py:672-740): one beta-binomial prior [frames, tokens] (float64, computed on the device

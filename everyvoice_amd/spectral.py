@@ -6,10 +6,12 @@ feature extraction built on it:
   extract_energy(logmel)                 everyvoice/preprocessor/preprocessor.py:302-309
 
 The DFT basis (window folded in) and the librosa Slaney mel filterbank are host-built constants uploaded once;
-all per-sample arithmetic runs in libevmi_hip (evmi_mel_spectrogram_f32).  CUDA tensors only.
+all per-sample arithmetic runs in libevmi_hip (evmi_mel_spectrogram_win_f32).  CUDA tensors only.
 """
 
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 import torch
@@ -60,15 +62,34 @@ def windowed_dft_basis(n_fft: int, win_length: int | None = None) -> tuple[np.nd
     return basis.astype(np.float32), nb_pad
 
 
+# the planner's argument names -> the AudioConfig fields they come from
+_PLAN_FIELDS = (("win_length", "fft_window_size"), ("hop", "fft_hop_size"), ("n_mels", "n_mels"), ("n_fft", "n_fft"))
+
+
+def mel_frontend_plan(n_fft: int, win_length: int, hop_length: int, n_mels: int) -> dict:
+    """The geometry evmi_mel_spectrogram_win_f32 runs these sizes with (evmi_mel_spectrogram_plan: host arithmetic, no device):
+    ``k0``, ``k1`` (the DFT loop's basis rows), ``frame_stride_words``, ``chunk_tiles``, ``lds_bytes``.  Sizes the kernel refuses
+    raise a ValueError that names the AudioConfig field at fault."""
+    lib = _lib.load()
+    ints = [C.c_int() for _ in range(4)]
+    lds = C.c_longlong()
+    rc = lib.evmi_mel_spectrogram_plan(int(n_fft), int(win_length), int(hop_length), int(n_mels), *[C.byref(v) for v in ints], C.byref(lds))
+    if rc != _lib.EVMI_OK:
+        msg = (lib.evmi_last_error() or b"").decode().split(": ", 1)[-1]
+        field = next(f for arg, f in _PLAN_FIELDS if msg.startswith(arg))  # (the message opens with the argument it refuses)
+        for arg, f in _PLAN_FIELDS[:2]:
+            msg = msg.replace(arg, f)
+        raise ValueError(f"mel-librosa front end: AudioConfig.{field}: {msg}")
+    return dict(zip(("k0", "k1", "frame_stride_words", "chunk_tiles"), (v.value for v in ints)), lds_bytes=lds.value)
+
+
 class MelSpectrogram:
-    """Callable mirror of the "mel-librosa" transform; ``log=True`` adds dynamic_range_compression_torch."""
+    """Callable mirror of the "mel-librosa" transform; ``log=True`` adds dynamic_range_compression_torch.  Any window
+    ``1 <= win_length <= n_fft`` (centred in n_fft, as torch.stft places it) and any hop ``1 <= hop_length <= n_fft``."""
 
     def __init__(self, n_fft=1024, win_length=1024, hop_length=256, sample_rate=22050, n_mels=80, f_min=0, f_max=8000):
-        if win_length != n_fft:
-            raise NotImplementedError("evmi_mel_spectrogram_f32 covers win_length == n_fft (the reference's defaults)")
-        if n_fft % hop_length:
-            raise NotImplementedError("n_fft must be a multiple of hop_length")
-        self.n_fft, self.hop, self.n_mels = n_fft, hop_length, n_mels
+        self.plan = mel_frontend_plan(n_fft, win_length, hop_length, n_mels)  # refuses here, not inside the first call
+        self.n_fft, self.win, self.hop, self.n_mels = n_fft, win_length, hop_length, n_mels
         basis, self.nb_pad = windowed_dft_basis(n_fft, win_length)
         self._basis_host = torch.from_numpy(basis)
         self._mel_host = torch.from_numpy(slaney_mel_filterbank(sample_rate, n_fft, n_mels, f_min, f_max))
@@ -97,19 +118,12 @@ class MelSpectrogram:
         with torch.cuda.device(x.device):
             if lens is not None:
                 lens = lens.to(x.device, torch.int32).contiguous()
-                _lib.check(
-                    lib.evmi_mel_spectrogram_ragged_f32(x.data_ptr(), lens.data_ptr(), basis.data_ptr(), melb.data_ptr(), mel.data_ptr(),
-                                                        _lib.ptr(energy), _lib.ptr(mag), B, S, self.n_fft, self.hop, self.nb_pad, self.n_mels,
-                                                        int(log), _lib.current_stream_ptr(x.device)),
-                    "evmi_mel_spectrogram_ragged_f32",
-                )
-            else:
-                _lib.check(
-                    lib.evmi_mel_spectrogram_f32(x.data_ptr(), basis.data_ptr(), melb.data_ptr(), mel.data_ptr(), _lib.ptr(energy),
-                                                 _lib.ptr(mag), B, S, self.n_fft, self.hop, self.nb_pad, self.n_mels, int(log),
-                                                 _lib.current_stream_ptr(x.device)),
-                    "evmi_mel_spectrogram_f32",
-                )
+            _lib.check(
+                lib.evmi_mel_spectrogram_win_f32(x.data_ptr(), _lib.ptr(lens), basis.data_ptr(), melb.data_ptr(), mel.data_ptr(),
+                                                 _lib.ptr(energy), _lib.ptr(mag), B, S, self.n_fft, self.win, self.hop, self.nb_pad,
+                                                 self.n_mels, int(log), _lib.current_stream_ptr(x.device)),
+                "evmi_mel_spectrogram_win_f32",
+            )
         shape = tuple(audio.shape[:-1])
         outs = [mel[0] if squeeze else mel.reshape(shape + mel.shape[1:])]
         if return_energy:

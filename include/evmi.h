@@ -106,7 +106,10 @@ int evmi_conv_transpose1d_f32(const float* x_dev, const float* w_dev, const floa
  *                  (apply_log = 0: the linear mel)
  *   energy_dev     [B, frames] L2 norm over the mel bins of mel_dev (NULL to skip)
  *   mag_dev        [B, n_fft/2+1, frames] sqrt(|STFT|^2 + 1e-9) (NULL to skip)
- * center=True, reflect padding, one-sided, win_length == n_fft, n_fft a multiple of hop.
+ * center=True, reflect padding, one-sided.  These two entry points take win_length == n_fft; evmi_mel_spectrogram_win_f32 below
+ * takes any window.  Accepted: n_fft even, 1 <= hop <= n_fft (hop need not divide anything), n_samples > n_fft/2, n_mels <= 128,
+ * and a 32-frame audio tile within the 160 KB LDS budget (evmi_mel_spectrogram_plan tells); everything else is refused with
+ * EVMI_ERR_INVALID_ARG / EVMI_ERR_UNSUPPORTED before any HIP call.
  * ------------------------------------------------------------------------------------------ */
 int evmi_mel_spectrogram_f32(const float* audio_dev, const float* dft_basis_dev,
                              const float* mel_basis_dev, float* mel_dev, float* energy_dev,
@@ -119,6 +122,23 @@ int evmi_mel_spectrogram_ragged_f32(const float* audio_dev, const int* lens_dev,
                                     const float* mel_basis_dev, float* mel_dev, float* energy_dev, float* mag_dev, int B,
                                     int n_samples_max, int n_fft, int hop, int n_bins_padded, int n_mels, int apply_log,
                                     void* stream);
+/* The same transform with a window of 1 <= win_length <= n_fft samples: the periodic Hann window sits centred in n_fft
+ * (left = (n_fft - win_length) / 2, torch.stft's convention) and is folded into dft_basis_dev by the caller, whose rows outside
+ * [left, left + win_length) must be zero: the kernel walks the even-aligned support [k0, k1) of the window only, which gives
+ * the bits of the walk over all n_fft rows.  lens_dev NULL: every row holds n_samples_max samples (evmi_mel_spectrogram_f32);
+ * given: the ragged rule above. */
+int evmi_mel_spectrogram_win_f32(const float* audio_dev, const int* lens_dev, const float* dft_basis_dev,
+                                 const float* mel_basis_dev, float* mel_dev, float* energy_dev, float* mag_dev, int B,
+                                 int n_samples_max, int n_fft, int win_length, int hop, int n_bins_padded, int n_mels,
+                                 int apply_log, void* stream);
+/* The geometry of that launch, host arithmetic only (no HIP call): EVMI_OK, or the refusal the launch would give for these sizes.
+ *   k0, k1              the DFT loop runs over basis rows [k0, k1): left rounded down, left + win_length rounded up to even
+ *   frame_stride_words  LDS words between consecutive frames of the audio tile: hop + 1 for an even hop, hop for an odd one
+ *   chunk_tiles         16-bin column tiles of the magnitude tile held in LDS at a time (n_bins_padded = n_fft/2+1 rounded up to 16)
+ *   lds_bytes           dynamic LDS of the launch (<= 160 KB)
+ * Any output pointer may be NULL. */
+int evmi_mel_spectrogram_plan(int n_fft, int win_length, int hop, int n_mels, int* k0, int* k1, int* frame_stride_words,
+                              int* chunk_tiles, long long* lds_bytes);
 
 /* The other spec types of get_spectral_transform (everyvoice/utils/heavy.py:59-68 "mel" = torchaudio MelSpectrogram(norm="slaney"),
  * :101-114 "linear" / "raw" = torchaudio Spectrogram(power = 2 / None), :115-118 "istft" = InverseSpectrogram): the DFT itself is
