@@ -290,6 +290,7 @@ int evmi_fs2_embed_f32(const int* ids_dev, const int* lens_dev, const float* tab
 
 int evmi_fs2_add_posemb_f32(float* x_dev, const int* lens_dev, const float* inv_freq_dev, int B, int T, int D, void* stream) {
   EVMI_NONNULL(x_dev && lens_dev && inv_freq_dev, "fs2_add_posemb");
+  if (B <= 0 || T <= 0 || D <= 0 || (D & 1)) return fail(EVMI_ERR_INVALID_ARG, "fs2_add_posemb: shape");  // odd D: pe reads inv_freq[D / 2]
   hipLaunchKernelGGL(fs2_add_posemb_kernel, grid1d((long long)D * B * T), dim3(256), 0, (hipStream_t)stream, x_dev, lens_dev,
                      inv_freq_dev, B, T, D);
   EVMI_LAUNCH_CHECK("fs2_add_posemb");
@@ -298,6 +299,7 @@ int evmi_fs2_add_posemb_f32(float* x_dev, const int* lens_dev, const float* inv_
 
 int evmi_mask_cols_f32(float* x_dev, const int* lens_dev, int C, int B, int T, void* stream) {
   EVMI_NONNULL(x_dev && lens_dev, "mask_cols");
+  if (C <= 0 || B <= 0 || T <= 0) return fail(EVMI_ERR_INVALID_ARG, "mask_cols: shape");
   hipLaunchKernelGGL(mask_cols_kernel, grid1d((long long)C * B * T), dim3(256), 0, (hipStream_t)stream, x_dev, lens_dev, B, T, C);
   EVMI_LAUNCH_CHECK("mask_cols");
   return EVMI_OK;
@@ -331,6 +333,7 @@ int evmi_fs2_bucket_embed_add_f32(float* x_dev, const float* values_dev, const f
                                   int B, int L, int D, float control, void* stream) {
   EVMI_NONNULL(x_dev && values_dev && bins_dev && table_dev, "fs2_bucket_embed_add");
   if (n_bins < 2) return fail(EVMI_ERR_INVALID_ARG, "fs2_bucket_embed_add: n_bins");
+  if (B <= 0 || L <= 0 || D <= 0) return fail(EVMI_ERR_INVALID_ARG, "fs2_bucket_embed_add: shape");
   hipLaunchKernelGGL(fs2_bucket_embed_add_kernel, grid1d((long long)D * B * L), dim3(256), 0, (hipStream_t)stream, x_dev, values_dev,
                      bins_dev, table_dev, n_bins, B, L, D, control);
   EVMI_LAUNCH_CHECK("fs2_bucket_embed_add");
@@ -339,6 +342,7 @@ int evmi_fs2_bucket_embed_add_f32(float* x_dev, const float* values_dev, const f
 
 int evmi_fs2_durations_i32(const float* log_d_dev, const int* lens_dev, int* dur_dev, int B, int L, float control, void* stream) {
   EVMI_NONNULL(log_d_dev && lens_dev && dur_dev, "fs2_durations");
+  if (B <= 0 || L <= 0) return fail(EVMI_ERR_INVALID_ARG, "fs2_durations: shape");
   hipLaunchKernelGGL(fs2_durations_kernel, grid1d((long long)B * L), dim3(256), 0, (hipStream_t)stream, log_d_dev, lens_dev, dur_dev,
                      B, L, control);
   EVMI_LAUNCH_CHECK("fs2_durations");
@@ -495,6 +499,7 @@ __global__ void fs2_add_item_embedding_kernel(float* __restrict__ x, const int* 
 extern "C" int evmi_fs2_add_item_embedding_f32(float* x_dev, const int* ids_dev, const int* lens_dev, const float* table_dev, int B,
                                                int L, int D, void* stream) {
   if (!x_dev || !ids_dev || !lens_dev || !table_dev) return evmi::fail(EVMI_ERR_INVALID_ARG, "fs2_add_item_embedding: null pointer");
+  if (B <= 0 || L <= 0 || D <= 0) return evmi::fail(EVMI_ERR_INVALID_ARG, "fs2_add_item_embedding: shape");
   hipLaunchKernelGGL(evmi::fs2_add_item_embedding_kernel, dim3((unsigned)(((long long)D * B * L + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, x_dev, ids_dev, lens_dev, table_dev, B, L, D);
   EVMI_LAUNCH_CHECK("fs2_add_item_embedding");

@@ -773,7 +773,7 @@ int evmi_pitch_world_decimator(int ratio, double* a3_host, double* b2_host);
  * (`position_embedding.inv_freq` [D/2] is the tensor everyvoice/tests/data/test.ckpt holds); inv_freq NULL = no pe term. */
 int evmi_fs2_embed_f32(const int* ids_dev, const int* lens_dev, const float* table_dev,
                        const float* inv_freq_dev, float* out_dev, int B, int L, int D, void* stream);
-/* x[c][b][t] = t < lens[b] ? x + pe(t, c) : 0   (decoder input). */
+/* x[c][b][t] = t < lens[b] ? x + pe(t, c) : 0   (decoder input); D even, like evmi_fs2_embed_f32. */
 int evmi_fs2_add_posemb_f32(float* x_dev, const int* lens_dev, const float* inv_freq_dev, int B, int T,
                             int D, void* stream);
 /* x[c][b][t] = 0 for t >= lens[b]. */
@@ -820,7 +820,8 @@ int evmi_align_attention_f32(const float* q_dev, const float* k_dev, const doubl
                              float* soft_dev, float* logprob_dev, int A, int B, int T, int L, float temperature,
                              void* stream);
 /* CTC forward-sum loss per item over logprob [B][T][L] (blank with log-probability `blank_logprob` prepended, targets
- * 1..L_b, zero_infinity, divided by L_b); the batch loss is their mean. */
+ * 1..L_b, zero_infinity, divided by L_b); the batch loss is their mean.  L <= 3274: the normalised row and two lattice columns,
+ * (5 L + 11) floats, live in 64 KiB of LDS; more returns EVMI_ERR_UNSUPPORTED. */
 int evmi_forward_sum_loss_f32(const float* logprob_dev, const int* text_lens_dev, const int* mel_lens_dev,
                               float* loss_per_item_dev, int B, int T, int L, float blank_logprob, void* stream);
 /* Binarisation loss partial sums: partials[2*i] = sum log(max(soft, 1e-12)) over hard == 1, partials[2*i+1] = count. */
@@ -828,7 +829,8 @@ int evmi_binarization_partials_f64(const int* hard_dev, const float* soft_dev, d
                                    long long n, void* stream);
 /* Monotonic alignment search (the reference's hard alignments: third-party ilt-monotonic-align 1.2.1 = Glow-TTS
  * maximum_path): value [B][T][L] log-likelihoods, mel_lens / text_lens [B] -> path [B][T][L] (0/1, one token per
- * frame, monotonic, every token used) and durations [B][L] = frames per token.  scratch: B*T*L bytes. */
+ * frame, monotonic, every token used) and durations [B][L] = frames per token.  scratch: B*T*L bytes.  L <= 8192: two rows
+ * of the dynamic programme, 2 L floats, live in 64 KiB of LDS; more returns EVMI_ERR_UNSUPPORTED. */
 int evmi_monotonic_align_f32(const float* value_dev, const int* mel_lens_dev, const int* text_lens_dev,
                              int* path_dev, int* dur_dev, unsigned char* scratch_dev, int B, int T, int L,
                              void* stream);
@@ -931,7 +933,8 @@ int evmi_length_regulate_bwd_cbt_f32(const float* dframes_dev, const int* cum_de
 
 /* Alignment learning, backward side (F5).  CTC forward-sum loss per item AND grad [B][T][L] = weight / (B * L_b) * d loss_b /
  * d logprob (softmax row - state occupancy; zero outside the item's frames / tokens; zero_infinity).
- * ws: evmi_forward_sum_grad_f32_ws_elems floats (the stored alpha lattice and per-frame normalisers). */
+ * ws: evmi_forward_sum_grad_f32_ws_elems floats (the stored alpha lattice and per-frame normalisers).  L <= 1023: the 2 L + 1
+ * states of the extended target are held by 512 threads with 1, 2 or 4 states each; more returns EVMI_ERR_UNSUPPORTED. */
 long long evmi_forward_sum_grad_f32_ws_elems(int B, int T, int L);
 int evmi_forward_sum_grad_f32(const float* logprob_dev, const int* text_lens_dev, const int* mel_lens_dev,
                               float* loss_per_item_dev, float* grad_dev, float* ws_dev, long long ws_elems, int B, int T,

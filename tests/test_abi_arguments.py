@@ -122,7 +122,54 @@ def test_refused_on_the_host_with_the_documented_code(case):
     assert torch.count_nonzero(_BUF) == 0  # (nothing was written through the stand-in pointer)
 
 
-# elementwise op codes and the operands they read besides `a` (the table beside ew_reads in csrc/train_ops.hip, restated)
+# The FastSpeech2 forward and alignment entry points (csrc/fs2_ops.hip, csrc/align_train_ops.hip): non-positive sizes, an odd D of the
+# sinusoid (its second half reads inv_freq[c - D / 2]: one past the table for the last channel), and the token limits of the header.
+# (entry point, arguments, code, the name evmi_last_error() carries)
+EVMI_ERR_UNSUPPORTED = 4
+FS2_CASES = [
+    ("evmi_fs2_add_posemb_f32", (P, P, P, 2, 4, 7, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_add_posemb_f32", (P, P, P, 2, 4, 1, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_add_posemb_f32", (P, P, P, 0, 4, 8, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_add_posemb_f32", (P, P, P, 2, 0, 8, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_add_posemb_f32", (P, P, P, 2, 4, 0, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_add_posemb_f32", (P, P, P, 2, -4, 8, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_embed_f32", (P, P, P, P, P, 2, 4, 7, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_mask_cols_f32", (P, P, 0, 2, 4, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_mask_cols_f32", (P, P, 8, 0, 4, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_mask_cols_f32", (P, P, 8, 2, -1, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_bucket_embed_add_f32", (P, P, P, P, 4, 0, 4, 8, 1.0, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_bucket_embed_add_f32", (P, P, P, P, 4, 2, 0, 8, 1.0, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_bucket_embed_add_f32", (P, P, P, P, 4, 2, 4, -8, 1.0, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_bucket_embed_add_f32", (P, P, P, P, 1, 2, 4, 8, 1.0, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_durations_i32", (P, P, P, 0, 4, 1.0, None), EVMI_ERR_INVALID_ARG, "fs2_durations"),
+    ("evmi_fs2_durations_i32", (P, P, P, 2, -4, 1.0, None), EVMI_ERR_INVALID_ARG, "fs2_durations"),
+    ("evmi_fs2_add_item_embedding_f32", (P, P, P, P, 0, 4, 8, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_add_item_embedding_f32", (P, P, P, P, 2, 0, 8, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_fs2_add_item_embedding_f32", (P, P, P, P, 2, 4, 0, None), EVMI_ERR_INVALID_ARG, None),
+    ("evmi_layernorm_cbt_f32", (P, P, P, P, 1025, 2, 1e-5, None), EVMI_ERR_UNSUPPORTED, None),
+    ("evmi_forward_sum_grad_f32", (P, P, P, P, P, P, 2 * 2049 + 2, 1, 2, 1024, -1.0, 1.0, None), EVMI_ERR_UNSUPPORTED, None),   # 2049 states
+    ("evmi_forward_sum_grad_f32", (P, P, P, P, P, P, 2 * 19 + 2 - 1, 1, 2, 9, -1.0, 1.0, None), EVMI_ERR_INVALID_ARG, None),   # workspace one short
+    ("evmi_forward_sum_loss_f32", (P, P, P, P, 1, 8, 3275, -1.0, None), EVMI_ERR_UNSUPPORTED, None),   # (5 L + 11) floats > 64 KiB
+    ("evmi_monotonic_align_f32", (P, P, P, P, P, P, 1, 2, 8193, None), EVMI_ERR_UNSUPPORTED, None),    # 2 L floats > 64 KiB
+]
+
+
+@pytest.mark.parametrize("case", FS2_CASES, ids=[_case_id(c) for c in FS2_CASES])
+def test_fs2_and_alignment_entry_points_refuse_on_the_host(case):
+    name, args, code, says = case
+    refused(name, *args, code=code, says=says)
+    assert torch.count_nonzero(_BUF) == 0
+
+
+def test_the_header_states_the_token_limits():
+    from pathlib import Path
+
+    text = " ".join((Path(__file__).resolve().parent.parent / "include" / "evmi.h").read_text().split())
+    for phrase in ("L <= 1023", "L <= 3274", "L <= 8192"):
+        assert phrase in text, phrase
+
+
+# elementwise op codes and the operands they read besides `a`(the table beside ew_reads in csrc/train_ops.hip, restated)
 _EW_READS_B = {1, 3, 4, 6, 7, 10, 11, 12, 15, 17, 18, 19, 22}
 _EW_READS_C = {12, 20, 21, 22, 24}
 

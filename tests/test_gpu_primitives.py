@@ -26,39 +26,7 @@ from everyvoice_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24          # unit roundoff of fp32
-TINY = 2.0 ** -126      # smallest normal fp32: results below it may be flushed to zero
-MATH_ULP = 4            # budget of one device math-function call, in ulp of its result (ulp(x) <= 2 u |x|)
-E = MATH_ULP * 2 * U    # ... as a relative error
-NAN = float("nan")
-
-
-def gamma(n):
-    return n * U / (1.0 - n * U)
-
-
-def f32(x):
-    """A Python float rounded to fp32 (what a c_float argument becomes)."""
-    return float(torch.tensor(x, dtype=torch.float32))
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def assert_within(got, want64, bound64, what=""):
-    """|got - want| <= bound + TINY for every element, finite everywhere; reports the worst element."""
-    got64 = got.detach().cpu().double().reshape(want64.shape)
-    assert torch.isfinite(got64).all(), f"{what}: non-finite output"
-    excess = (got64 - want64).abs() - (bound64 + TINY)
-    if (excess > 0).any():
-        i = int(excess.argmax())
-        raise AssertionError(f"{what}: element {i}: got {got64.flatten()[i]!r} want {want64.flatten()[i]!r} "
-                             f"|err| {(got64 - want64).abs().flatten()[i]:.3e} > bound {float(bound64.flatten()[i] if bound64.ndim else bound64):.3e}")
+from helpers import E, MATH_ULP, NAN, TINY, U, assert_within, bits, f32, gamma, same_bits  # noqa: F401  (shared with the other primitive files)
 
 
 def ops_mod():
