@@ -19,77 +19,15 @@
 // fixed summation order: the gradients are bitwise reproducible (the checkpoint / resume test relies on that).
 #include <type_traits>
 
-#include "common.h"
+#include "attention_tiles.h"
 
 namespace evmi {
-
-// value at p (p must be a valid address for every lane), zero for lanes that are not live.  The load is unconditional and the
-// select follows it: a load under a per-lane condition is compiled as a branch around it with the memory counter drained behind
-// every one (one dependent round trip per element: 128 of them in the prologue of a 128-wide head, 32 per key tile).
-__device__ __forceinline__ float live_load(const float* __restrict__ p, bool live) {
-  const float v = *p;
-  return live ? v : 0.f;
-}
-
-
-// register r of a 32x32 accumulator <-> row index within the tile, for half-wave kh
-__device__ __forceinline__ int acc_row(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
-
-// Dropout factors (keep or 0) of the 16 accumulator registers of a 32 x 32 score tile.
-//   attn_drop_rows: the registers are keys k0 + acc_row(r, kh) of ONE query row (row_base = the row's first element): registers r, r + 1
-//                   (r even) are the two elements of a pair -- one hash for both (pairs: T even and the tensor below 2^33 elements)
-//   attn_drop_cols: the lane holds ONE key, the registers are queries q0 + acc_row(r, kh): the pair's other element sits in the
-//                   neighbouring lane (key ^ 1) at the same register -- each lane hashes the registers of its own parity and the two
-//                   exchange (one DPP move per hash)
-// Same bits as uniform01(seed, element index) per element (common.h), which the other parities / sizes take.
-__device__ __forceinline__ void attn_drop_rows(float (&dm)[16], bool pairs, unsigned long long seed, unsigned long long row_base, int k0, int kh,
-                                               float p_drop, float keep) {
-  if (pairs) {
-    const unsigned jb = (unsigned)(row_base >> 1) + (unsigned)(k0 >> 1) + 2u * (unsigned)kh;
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      float u0, u1;
-      dropout_pair(seed, jb + (unsigned)(((r & 3) >> 1) + 4 * (r >> 2)), u0, u1);
-      dm[r] = u0 >= p_drop ? keep : 0.f;
-      dm[r + 1] = u1 >= p_drop ? keep : 0.f;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dm[r] = uniform01(seed, row_base + (unsigned long long)(k0 + acc_row(r, kh))) >= p_drop ? keep : 0.f;
-  }
-}
-// (four registers at a time -- 4 g4 .. 4 g4 + 3 -- so that the factors do not stay live across the whole tile)
-__device__ __forceinline__ void attn_drop_cols(float (&dm)[4], int g4, bool pairs, unsigned long long seed, unsigned long long batch_base, int tk,
-                                               int tkc, int q0, int kh, int T, float p_drop, float keep) {
-  if (pairs) {
-    const unsigned par = (unsigned)tk & 1u, th = (unsigned)T >> 1;
-    const unsigned jb = (unsigned)((batch_base + (unsigned long long)(tk & ~1)) >> 1);  // (the pair's index: not the clamped key's)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int tq = q0 + 8 * g4 + 4 * kh + 2 * c + (int)par;  // query of register 4 g4 + 2 c + par
-      const unsigned mine = dropout_hash(seed, jb + (unsigned)min(tq, T - 1) * th, 0u);
-      const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)mine, 0xB1, 0xF, 0xF, true);  // quad_perm [1, 0, 3, 2]: lane ^ 1
-      const unsigned h0 = par ? other : mine, h1 = par ? mine : other;                              // registers 4 g4 + 2 c and + 1
-      dm[2 * c] = dropout_u16(h0, par) >= p_drop ? keep : 0.f;
-      dm[2 * c + 1] = dropout_u16(h1, par) >= p_drop ? keep : 0.f;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int tq = q0 + 8 * g4 + 4 * kh + e;
-      dm[e] = uniform01(seed, batch_base + (unsigned long long)tkc + (unsigned long long)min(tq, T - 1) * (unsigned long long)T) >= p_drop ? keep : 0.f;
-    }
-  }
-}
-static inline bool attn_drop_pairs(int B, int T) { return !(T & 1) && (unsigned long long)B * T * T < (1ull << 33); }
 
 // A [DH][32] tile of a channel-major [DH][B][T] slice, columns t0 .. t0 + 31, by LDS-direct loads straight into the operand layout: rows of 32 floats, element (d, t) at d * 32 + (t ^ (d & 31)).
 // The XOR swizzle replaces the odd row stride (a tile is read along its rows and across them: both are conflict-free), and is
 // applied on the SOURCE side -- lane (d, p) of a request fetches column p ^ (d & 31) -- because the hardware writes lane i of a
 // request to base + 4 i.  Columns past T are clamped to T - 1: finite values that only ever meet zero probabilities.  Two
 // generations of every tile: step i + 1 lands while step i computes, one barrier per step.
-typedef __attribute__((address_space(3))) float atf_lds_float_t;
-typedef __attribute__((address_space(1))) const float atf_glb_float_t;
 template <int DH>
 __device__ __forceinline__ void tile_request_swz(float* __restrict__ dst, const float* __restrict__ src, long long N, int t0, int T, int tid) {
   const int d0 = tid >> 5, p = tid & 31;
@@ -101,21 +39,6 @@ __device__ __forceinline__ void tile_request_swz(float* __restrict__ dst, const 
     __builtin_amdgcn_global_load_lds((atf_glb_float_t*)g, (atf_lds_float_t*)(l + 256 * i), 4, 0, 0);
   }
 }
-// Per-lane offsets of the two kinds of read, computed once (32 registers; the rest of an address is an instruction immediate):
-//   along a row : lane reads column ln of row 2 s + kh             -> (2 s + kh) * 32 + row_off[s & 15]
-//   across rows : lane reads column acc_row(r, kh) of row 32 i + ln -> i * 1024 + col_off[r]
-struct SwzOffsets {
-  int row_off[16], col_off[16];
-  __device__ __forceinline__ SwzOffsets(int ln, int kh) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      row_off[j] = ln ^ ((2 * j + kh) & 31);
-      col_off[j] = ln * 32 + (((j & 3) + 8 * (j >> 2) + 4 * kh) ^ ln);
-    }
-  }
-  __device__ __forceinline__ int along(int s, int kh) const { return (2 * s + kh) * 32 + row_off[s & 15]; }
-  __device__ __forceinline__ int across(int i, int r) const { return i * 1024 + col_off[r]; }
-};
 
 // ---- forward -------------------------------------------------------------------------------------------------------------
 // grid (ceil(T / 128), H, B), 256 threads: every wave owns 32 queries
@@ -416,10 +339,6 @@ __global__ __launch_bounds__(256) void attention_train_dkv_kernel(const float* _
 // registers with a full vmcnt(0) wait behind EVERY load: 32 serial round trips per tile in the dK/dV kernel.)
 // The element loops are straight-line: the probability is always computed and masked by a select, the per-query statistics of
 // the dK/dV kernel are read as 16-byte LDS vectors, dropout is a template parameter (its generator costs more than the exp).
-constexpr int ATB_PD = 8;  // bf16 row padding
-
-typedef __attribute__((address_space(3))) float at_lds_float_t;
-typedef __attribute__((address_space(1))) const float at_glb_float_t;
 
 // request the [DH][32] fp32 tile of a channel-major slice (columns t0 .. t0 + 31, clamped to T - 1) into raw[DH * 32]: element
 // v = tid + 256 i (channel v >> 5, column v & 31) lands at raw[v]
@@ -447,13 +366,6 @@ __device__ __forceinline__ void tile_convert(const float* __restrict__ raw, bf16
     if (PC) x_pc[tt * LP + d0 + 8 * i] = val;
     if (CP) x_cp[(d0 + 8 * i) * LC + tt] = val;
   }
-}
-
-// A operand of a contraction over the tile's positions: lane (channel row, half) takes positions 16 kb + 4 half + {0..3} and + 8
-__device__ __forceinline__ bf16x8 load_pos_slots(const bf16_t* __restrict__ row, int kb, int kh) {
-  const bf16x4 lo = *reinterpret_cast<const bf16x4*>(row + 16 * kb + 4 * kh);
-  const bf16x4 hi = *reinterpret_cast<const bf16x4*>(row + 16 * kb + 4 * kh + 8);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 template <int DH, int DROP>  // DROP 0: no dropout; 1: one hash per element; 2: one hash per pair of elements (attn_drop_pairs)
@@ -756,6 +668,12 @@ __global__ __launch_bounds__(256, 2) void attention_train_dkv_bf16_kernel(const 
       dk[(long long)(i * 32 + acc_row(r, kh)) * N] = acck[i][r] * scale;
       dv[(long long)(i * 32 + acc_row(r, kh)) * N] = accv[i][r];
     }
+}
+
+// step 0 of a backward for callers outside this file (attention_generic.hip): the kernel takes any head dimension
+void launch_attention_rowdot(const float* out, const float* dout, float* dsum, int B, int T, int heads, int dh, hipStream_t s) {
+  const long long n = (long long)B * heads * T;
+  hipLaunchKernelGGL(attention_rowdot_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, dout, dsum, B, T, heads, dh);
 }
 
 // body(std::integral_constant<int, DH>{}) for the head dimensions built (32 / 64 / 128)

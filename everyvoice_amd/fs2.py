@@ -202,6 +202,23 @@ def apply_variance_settings(c: "FastSpeech2ModelConfig") -> dict:
     return out
 
 
+def check_conformer_widths(c: "FastSpeech2ModelConfig") -> None:
+    """Refuses, where the configuration is read (not inside the first forward or training step), an encoder / decoder whose width the
+    kernels do not run: ``input_dim`` must be even (the sinusoidal positional term has ``input_dim / 2`` frequencies) and a multiple of
+    ``heads``, and the head dimension ``input_dim / heads`` at most 256 (csrc/attention_generic.hip; 32 / 64 / 128 run on the specialised
+    kernels).  ``ValueError`` naming the field.  Called by the model, the trainer and ``lightning.FastSpeech2Config``."""
+    for name in ("encoder", "decoder"):
+        cf = getattr(c, name)
+        d, heads = int(cf.input_dim), int(cf.heads)
+        if d <= 0 or d % 2:
+            raise ValueError(f"model.{name}.input_dim: must be positive and even, got {d}")
+        if heads <= 0 or d % heads:
+            raise ValueError(f"model.{name}.heads: input_dim {d} is not a multiple of heads {heads}")
+        if d // heads > ops.ATTENTION_MAX_HEAD_DIM:
+            raise ValueError(f"model.{name}.heads: the head dimension input_dim / heads = {d} / {heads} = {d // heads} is above "
+                             f"{ops.ATTENTION_MAX_HEAD_DIM}, the largest the attention kernels take")
+
+
 def gst_state_dict_shapes(c: "FastSpeech2ModelConfig") -> dict:
     """THE key-name table of the Global Style Token module: every tensor of its state dict except ``num_batches_tracked`` (which the
     trainer adds for each ``bns.{i}``), in declaration order.  The module lives in the absent FastSpeech2_lightning submodule, so the
@@ -317,7 +334,7 @@ class _Conformer:
             A = L["attn"]
             qkv = _ln_conv(x, A["ln_g"], A["ln_b"], A["w_in"], A["b_in"])
             att = torch.empty_like(x)
-            attn = lib.evmi_attention_cbt_bf16 if ops.CONV_BACKEND["operands"] == "bf16" else lib.evmi_attention_cbt_f32
+            attn = getattr(lib, ops.attention_entry("infer", D // self.cfg.heads))
             _chk(attn(qkv.data_ptr(), lens.data_ptr(), att.data_ptr(), B, T, D, self.cfg.heads, _s(x)), "evmi_attention_cbt")
             x = _conv_add(att, A["w_out"], A["b_out"], x)
             Cm = L["conv"]
@@ -377,6 +394,7 @@ class FastSpeech2:
         self.lang2id, self.speaker2id = lang2id or {}, speaker2id or {}
         self.audio_config = None  # the model's preprocessing.audio, where the caller knows it: the synthesis helpers make a style reference's mel with it
         self.levels = apply_variance_settings(self.config)["level"]
+        check_conformer_widths(self.config)
         if self.config.use_global_style_token_module:
             gst_state_dict_shapes(self.config)  # (refuses a size the kernels are not built for here, not inside the first forward)
         if self.device.type != "cuda":

@@ -233,7 +233,7 @@ class FastSpeech2Config:
 
     def __post_init__(self):
         from .config import PreprocessingConfig
-        from .fs2 import FastSpeech2ModelConfig, apply_variance_settings
+        from .fs2 import FastSpeech2ModelConfig, apply_variance_settings, check_conformer_widths
         from .train.fs2 import FastSpeech2TrainingConfig
 
         if isinstance(self.model, dict):
@@ -245,6 +245,7 @@ class FastSpeech2Config:
         self.model = self.model or FastSpeech2ModelConfig()
         self.training = self.training or FastSpeech2TrainingConfig()
         apply_variance_settings(self.model)  # a level outside {phone, frame} or a loss outside {mse, mae} is refused where the file / override is read
+        check_conformer_widths(self.model)  # ... and an encoder / decoder width that the attention kernels do not take
 
     # -- the two class-level entry points the driver uses (base_cli/helpers.py:85, 111; shared_types.py:90-94) ------------------
     @classmethod

@@ -33,7 +33,7 @@ from dataclasses import asdict, dataclass, field
 import torch
 
 from .. import _lib
-from ..fs2 import N_PHONOLOGICAL_FEATURES, FastSpeech2ModelConfig, Stats, apply_variance_settings
+from ..fs2 import N_PHONOLOGICAL_FEATURES, FastSpeech2ModelConfig, Stats, apply_variance_settings, check_conformer_widths
 from . import ops
 from .autograd import _ACTIVATION_ELEMS, Tape, Var, alias
 from .layers import ParamGroup, WNBatch, WNConv
@@ -921,6 +921,7 @@ class FastSpeech2Trainer(CapturedStep):
         self.config = c = config or FastSpeech2ModelConfig()
         settings = apply_variance_settings(c)  # (refuses a level / loss outside the schema's values here, not inside the first step)
         self.levels, self.loss_kinds = settings["level"], settings["loss"]
+        check_conformer_widths(c)  # (an odd width, one that is no multiple of heads or a head dimension above 256: here as well)
         self.stats = stats or Stats()
         self.training = training or FastSpeech2TrainingConfig()
         self.device = torch.device(device)

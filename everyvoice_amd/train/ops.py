@@ -1293,6 +1293,23 @@ def mask_cols_(x, lens32):
     return x
 
 
+# The attention kernels specialised on the head dimension (csrc/attention_train.hip, attention_cbt_kernel of csrc/fs2_ops.hip) and the
+# largest one the kernels of csrc/attention_generic.hip take.
+ATTENTION_SPECIALISED_HEAD_DIMS = (32, 64, 128)
+ATTENTION_MAX_HEAD_DIM = 256
+_ATTENTION_ENTRIES = {"infer": ("evmi_attention_cbt", "evmi_attention_generic"), "fwd": ("evmi_mha_fwd", "evmi_mha_generic_fwd"),
+                      "bwd": ("evmi_mha_bwd", "evmi_mha_generic_bwd")}
+
+
+def attention_entry(kind, head_dim, operands=None):
+    """Name of the C entry point of an attention pass -- kind "infer" (no log-sum-exp, no dropout), "fwd" or "bwd" (training) -- at this
+    head dimension: the specialised kernels at 32 / 64 / 128, the generic ones (same arguments) at every other one up to 256.
+    ``operands``: "f32" or "bf16" (default: CONV_BACKEND["operands"])."""
+    specialised, generic = _ATTENTION_ENTRIES[kind]
+    stem = specialised if head_dim in ATTENTION_SPECIALISED_HEAD_DIMS else generic
+    return f"{stem}_{'bf16' if (operands or CONV_BACKEND['operands']) == 'bf16' else 'f32'}"
+
+
 def attention_train_fwd(qkv, lens32, heads, p=0.0, seed=0):
     """Multi-head self-attention in training mode (evmi_mha_fwd_f32, flash-style): qkv [3D, B, T] -> (out [D, B, T], saved).
     Only the per-query log-sum-exp is kept for the backward; attention dropout as torch.nn.MultiheadAttention applies it
@@ -1301,8 +1318,7 @@ def attention_train_fwd(qkv, lens32, heads, p=0.0, seed=0):
     D = D3 // 3
     out = torch.empty(D, B, T, device=qkv.device, dtype=torch.float32)
     lse = torch.empty(B, heads, T, device=qkv.device, dtype=torch.float32)
-    lib = _lib.load()
-    fn = lib.evmi_mha_fwd_bf16 if CONV_BACKEND["operands"] == "bf16" else lib.evmi_mha_fwd_f32
+    fn = getattr(_lib.load(), attention_entry("fwd", D // heads))
     _chk(fn(qkv.data_ptr(), lens32.data_ptr(), out.data_ptr(), lse.data_ptr(), B, T, D, heads, float(p), int(seed), _lib.ptr(SEED_BASE[0]), _s(qkv)), "evmi_mha_fwd")
     return out, (out, lse, lens32)
 
@@ -1312,8 +1328,7 @@ def attention_train_bwd(qkv, saved, dout, heads, p=0.0, seed=0):
     D3, B, T = qkv.shape
     dqkv = torch.empty_like(qkv)
     dsum = torch.empty_like(lse)
-    lib = _lib.load()
-    fn = lib.evmi_mha_bwd_bf16 if CONV_BACKEND["operands"] == "bf16" else lib.evmi_mha_bwd_f32
+    fn = getattr(_lib.load(), attention_entry("bwd", D3 // 3 // heads))
     _chk(fn(qkv.data_ptr(), lens32.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dsum.data_ptr(), dqkv.data_ptr(), B, T, D3 // 3, heads,
             float(p), int(seed), _lib.ptr(SEED_BASE[0]), _s(qkv)), "evmi_mha_bwd")
     return dqkv

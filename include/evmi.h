@@ -894,6 +894,24 @@ int evmi_mha_fwd_bf16(const float* qkv_dev, const int* lens_dev, float* out_dev,
 int evmi_mha_bwd_bf16(const float* qkv_dev, const int* lens_dev, const float* out_dev, const float* dout_dev,
                       const float* lse_dev, float* dsum_dev, float* dqkv_dev, int B, int T, int D, int heads, float p_drop,
                       unsigned long long seed, const unsigned long long* seed_base_dev, void* stream);
+/* The attention passes at ANY head dimension 1 <= D / heads <= 256 (csrc/attention_generic.hip): same layouts, masking, dropout
+ * stream and reproducibility as their counterparts above, the head dimension padded inside the kernels to 32 / 64 / 96 / 128 /
+ * 192 / 256.  They also take 32 / 64 / 128 (where the hosts above use the specialised kernels), so the two can be compared.
+ * EVMI_ERR_UNSUPPORTED for D / heads > 256 and for B or heads above 65535; every refusal comes before the first HIP call. */
+int evmi_attention_generic_f32(const float* qkv_dev, const int* lens_dev, float* out_dev, int B, int T, int D,
+                               int heads, void* stream);
+int evmi_attention_generic_bf16(const float* qkv_dev, const int* lens_dev, float* out_dev, int B, int T, int D,
+                                int heads, void* stream);
+int evmi_mha_generic_fwd_f32(const float* qkv_dev, const int* lens_dev, float* out_dev, float* lse_dev, int B, int T, int D, int heads,
+                             float p_drop, unsigned long long seed, const unsigned long long* seed_base_dev, void* stream);
+int evmi_mha_generic_bwd_f32(const float* qkv_dev, const int* lens_dev, const float* out_dev, const float* dout_dev,
+                             const float* lse_dev, float* dsum_dev, float* dqkv_dev, int B, int T, int D, int heads, float p_drop,
+                             unsigned long long seed, const unsigned long long* seed_base_dev, void* stream);
+int evmi_mha_generic_fwd_bf16(const float* qkv_dev, const int* lens_dev, float* out_dev, float* lse_dev, int B, int T, int D, int heads,
+                              float p_drop, unsigned long long seed, const unsigned long long* seed_base_dev, void* stream);
+int evmi_mha_generic_bwd_bf16(const float* qkv_dev, const int* lens_dev, const float* out_dev, const float* dout_dev,
+                              const float* lse_dev, float* dsum_dev, float* dqkv_dev, int B, int T, int D, int heads, float p_drop,
+                              unsigned long long seed, const unsigned long long* seed_base_dev, void* stream);
 /* scores [B][Tq][Tk] -> softmax over the keys tk < lens[b] in place (0 beyond); with p > 0 also
  * dropped = dropout(probabilities, p) from the counter-based generator keyed by `seed`. */
 int evmi_softmax_rows_f32(float* scores_dev, float* dropped_dev, const int* lens_dev, int B, int Tq, int Tk, float p,
