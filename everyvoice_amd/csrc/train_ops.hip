@@ -342,6 +342,8 @@ __global__ void row_reduce_final_kernel(const float* __restrict__ part, float* _
 //   24: y = p0 * a / c[0]  (device scalar: a count that changes from batch to batch without changing a captured graph)
 //   21: y = a / c[0]  (device scalar)        22: op 17 with p0 / (sqrt(c[0]) sqrt(c[1])) as the first coefficient (device scalars)
 //   16: y = log(a)                          17: y = p0 * (a - b) + p1 * sign(a - b) / a   (d/da of the two STFT-loss terms, a = |Y^|, b = |Y|)
+//   26: y = a*a + b*b  (power spectrum)     27: y = p0 * a * b  (dre = 2 re dpower: the power spectrum's backward)
+//   (25 is not assigned: the ABI tests hold it as the refused code just past the table they restate, 0 .. 24)
 template <int OP>
 __global__ void ew_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
                           float* __restrict__ y, long long n, float p0, float p1) {
@@ -371,6 +373,8 @@ __global__ void ew_kernel(const float* __restrict__ a, const float* __restrict__
   else if (OP == 21) r = a[i] / c[0];
   else if (OP == 23) r = p0;
   else if (OP == 24) r = p0 * a[i] / c[0];
+  else if (OP == 26) r = a[i] * a[i] + b[i] * b[i];
+  else if (OP == 27) r = p0 * a[i] * b[i];
   else if (OP == 22) {  // op 17 with its first coefficient p0 / (||a - b|| ||b||) formed from the squared norms c[0], c[1] on the device
     const float nd = sqrtf(c[0]), ny = sqrtf(c[1]);
     const float k0 = nd > 0.f ? p0 / (nd * ny) : 0.f;
@@ -784,11 +788,11 @@ using namespace evmi;
   if (!(cond)) return fail(EVMI_ERR_INVALID_ARG, msg)
 
 // Operands an elementwise op code reads besides `a` (bit 0: b, bit 1: c), from the table above ew_kernel:
-//   b: 1 3 4 6 7 10 11 12 15 17 18 19 22      c: 12 20 21 22 24
+//   b: 1 3 4 6 7 10 11 12 15 17 18 19 22 26 27      c: 12 20 21 22 24
 static int ew_reads(int op) {
-  static const unsigned char reads[25] = {/*0*/ 0, 1, 0, 1, 1, /*5*/ 0, 1, 1, 0, 0, /*10*/ 1, 1, 3, 0, 0,
-                                          /*15*/ 1, 0, 1, 1, 1, /*20*/ 2, 2, 3, 0, 2};
-  return op >= 0 && op < 25 ? reads[op] : 0;
+  static const unsigned char reads[28] = {/*0*/ 0, 1, 0, 1, 1, /*5*/ 0, 1, 1, 0, 0, /*10*/ 1, 1, 3, 0, 0,
+                                          /*15*/ 1, 0, 1, 1, 1, /*20*/ 2, 2, 3, 0, 2, /*25*/ 0, 1, 1};
+  return op >= 0 && op < 28 ? reads[op] : 0;
 }
 
 extern "C" {
@@ -908,14 +912,14 @@ int evmi_lrelu_bwd_rowsum_f32(const float* dy_dev, const float* y_dev, float* dp
 int evmi_elementwise_f32(int op, const float* a_dev, const float* b_dev, const float* c_dev, float* y_dev, long long n,
                          float p0, float p1, void* stream) {
   EVMI_NONNULL(a_dev && y_dev, "elementwise");
-  EVMI_REQUIRE(op >= 0 && op <= 24, "elementwise: unknown op");
+  EVMI_REQUIRE(op >= 0 && op <= 27 && op != 25, "elementwise: unknown op");
   EVMI_REQUIRE(n >= 1, "elementwise: n must be positive");
   EVMI_REQUIRE(!(ew_reads(op) & 1) || b_dev, "elementwise: this op reads b");
   EVMI_REQUIRE(!(ew_reads(op) & 2) || c_dev, "elementwise: this op reads c");
   hipStream_t s = (hipStream_t)stream;
 #define EW(OPN) case OPN: hipLaunchKernelGGL(ew_kernel<OPN>, grid1d(n), dim3(256), 0, s, a_dev, b_dev, c_dev, y_dev, n, p0, p1); break;
   switch (op) {
-    EW(0) EW(1) EW(2) EW(3) EW(4) EW(5) EW(6) EW(7) EW(8) EW(9) EW(10) EW(11) EW(12) EW(13) EW(14) EW(15) EW(16) EW(17) EW(18) EW(19) EW(20) EW(21) EW(22) EW(23) EW(24)
+    EW(0) EW(1) EW(2) EW(3) EW(4) EW(5) EW(6) EW(7) EW(8) EW(9) EW(10) EW(11) EW(12) EW(13) EW(14) EW(15) EW(16) EW(17) EW(18) EW(19) EW(20) EW(21) EW(22) EW(23) EW(24) EW(26) EW(27)
     default: return fail(EVMI_ERR_INVALID_ARG, "elementwise: unknown op");
   }
 #undef EW

@@ -159,7 +159,9 @@ class HiFiGAN(_Module):
 
     def training_step(self, batch, batch_idx: int = 0):
         """batch = (spec [B, n_mels, F], audio [B, S], basenames, spec_from_audio [B, n_mels, F]) as the reference's
-        SpecDataset + DataLoader deliver it (tests/test_dataloader.py:55-65)."""
+        SpecDataset + DataLoader deliver it (tests/test_dataloader.py:55-65).  ``spec`` is at input_sampling_rate (F frames of
+        fft_hop_size samples); ``audio`` and ``spec_from_audio`` are at output_sampling_rate = c x input_sampling_rate: S = F x fft_hop_size x c
+        samples, and the frames of ``spec_from_audio`` are the output transform's (n_fft c / window c / hop c)."""
         if self.trainer_ is None:
             raise RuntimeError("HiFiGAN.training_step: move the module to a GPU first (.to('cuda:0')); there is no CPU path")
         spec, audio, _, _ = self._device_batch(batch)
@@ -169,17 +171,26 @@ class HiFiGAN(_Module):
         return out
 
     def validation_step(self, batch, batch_idx: int = 0):
-        """Generator forward on a validation item; ``validation/mel_spec_error`` (L1 between log-mels) is what the vocoder's
-        checkpoints are ranked by."""
-        from .spectral import MelSpectrogram
+        """Generator forward on a validation item; ``validation/mel_spec_error`` (L1 between the log-spectrograms of the generated
+        and the stored audio, both through the vocoder's output transform: spectral.vocoder_output_transform) is what the
+        vocoder's checkpoints are ranked by."""
+        from .spectral import get_spectral_transform, vocoder_output_transform
 
         spec, audio, _, _ = self._device_batch(batch)
         wav = self.trainer_.generate(spec)
-        a = self.config.preprocessing.audio
-        tr = getattr(self, "_val_mel", None) or MelSpectrogram(a.n_fft, a.fft_window_size, a.fft_hop_size, a.input_sampling_rate, a.n_mels, a.f_min, a.f_max)
+        tr = getattr(self, "_val_mel", None)
+        if tr is None:
+            t = vocoder_output_transform(self.config.preprocessing.audio)
+            fn = get_spectral_transform(t["spec_type"], t["n_fft"], t["win_length"], t["hop_length"], t["filter_sample_rate"], t["n_mels"], t["f_min"], t["f_max"])
+            if t["spec_type"] == "mel":  # the torchaudio mel comes out linear: log(clamp(., 1e-5)) as the preprocessor applies it
+                from .train import ops
+
+                tr = lambda x: ops.elementwise(ops.EW_LOG_CLAMP, fn(x).contiguous(), p0=1e-5)  # noqa: E731
+            else:
+                tr = lambda x: fn(x, log=True)  # noqa: E731
         self._val_mel = tr
         n = min(wav.shape[-1], audio.shape[-1])
-        err = float((tr(wav[:, 0, :n], log=True) - tr(audio[:, 0, :n], log=True)).abs().mean())
+        err = float((tr(wav[:, 0, :n]) - tr(audio[:, 0, :n])).abs().mean())
         self.log("validation/mel_spec_error", err)
         return err
 

@@ -310,6 +310,33 @@ def get_spectral_transform(spec_type, n_fft, win_length, hop_length, sample_rate
     return None
 
 
+#: the spectrogram types a vocoder can be trained on: real-valued, ``n_mels`` rows (what the generator's conv_pre is built for)
+VOCODER_SPEC_TYPES = ("mel-librosa", "mel")
+
+
+def vocoder_output_transform(audio_cfg) -> dict:
+    """The spectral transform of a vocoder's OUTPUT audio -- what the preprocessor stores as ``spec-{output_sr}-{spec_type}.pt``
+    and what the trainer's reconstruction loss and validation error are measured with.  With
+    ``c = output_sampling_rate // input_sampling_rate`` it is ``spec_type`` at ``n_fft c`` / ``fft_window_size c`` / ``fft_hop_size c``.
+
+    ``filter_sample_rate`` is the INPUT sampling rate: the reference hands its output transform ``sample_rate=input_sampling_rate``
+    (everyvoice/preprocessor/preprocessor.py:112-121), so the mel filters sit at 1 / c of the output-rate audio's frequencies.  A
+    quirk, reproduced on purpose (pipeline.GpuPreprocessor does the same): target and loss must be the same spectrogram.
+
+    Host arithmetic only.  Refusals are ValueErrors naming the field: a rate pair that is no positive integer multiple, and a
+    ``spec_type`` no vocoder can train on ("linear" has n_fft / 2 + 1 rows where conv_pre takes n_mels; "raw" / "istft" are complex)."""
+    in_sr, out_sr = int(audio_cfg.input_sampling_rate), int(audio_cfg.output_sampling_rate)
+    if out_sr <= 0 or in_sr <= 0 or out_sr % in_sr:
+        raise ValueError(f"preprocessing.audio: output_sampling_rate {out_sr} must be a positive integer multiple of input_sampling_rate {in_sr}")
+    if audio_cfg.spec_type not in VOCODER_SPEC_TYPES:
+        raise ValueError(f"preprocessing.audio.spec_type {audio_cfg.spec_type!r}: a vocoder trains on 'mel-librosa' or 'mel' "
+                         "(n_mels real-valued rows; 'linear' has n_fft / 2 + 1 rows, 'raw' and 'istft' are complex)")
+    c = out_sr // in_sr
+    return dict(c=c, spec_type=audio_cfg.spec_type, n_fft=audio_cfg.n_fft * c, win_length=audio_cfg.fft_window_size * c,
+                hop_length=audio_cfg.fft_hop_size * c, filter_sample_rate=in_sr, n_mels=audio_cfg.n_mels,
+                f_min=audio_cfg.f_min, f_max=audio_cfg.f_max)
+
+
 def extract_spectral_features(audio: torch.Tensor, transform: MelSpectrogram, normalize: bool = True, truncate: bool = True):
     """log-mel of ``audio`` [.., S]; ``truncate`` keeps S // hop frames as Preprocessor.process_spec does."""
     mel = transform(audio, log=normalize)

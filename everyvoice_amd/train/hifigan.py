@@ -30,7 +30,7 @@ import torch
 
 from .. import _lib
 from ..config import ACTIVATION_SLOPES, HiFiGANConfig
-from ..spectral import slaney_mel_filterbank, windowed_dft_basis
+from ..spectral import htk_mel_filterbank, slaney_mel_filterbank, vocoder_output_transform, windowed_dft_basis
 from . import autograd as ag
 from . import ops
 from .layers import ParamGroup, SNConv, WNBatch, WNConv, kaiming_uniform_conv_init_
@@ -304,19 +304,24 @@ class DiscriminatorST:
 
 
 class MelLoss:
-    """45 * L1(logmel(y), logmel(y_hat)) with the reference's mel-librosa front-end (heavy.py:69-100, 39-40), as
-    GEMMs: frames [n_fft, B*F] -> (cos | sin) DFT -> magnitude -> mel basis -> log-clamp."""
+    """45 * L1(logspec(y), logspec(y_hat)) with the vocoder's OUTPUT transform (spectral.vocoder_output_transform: ``spec_type`` at
+    n_fft c / window c / hop c, filters for the input rate -- the spectrogram the preprocessor stores as the output-rate target), as
+    GEMMs: frames [n_fft, B*F] -> (cos | sin) DFT -> spectrum -> mel basis -> log-clamp.
+      "mel-librosa" (heavy.py:69-100, 39-40): magnitude sqrt(re^2 + im^2 + 1e-9), librosa's Slaney basis;
+      "mel" (heavy.py:59-68, torchaudio): power re^2 + im^2, HTK-scale basis; log(clamp(., 1e-5)) as the preprocessor applies it."""
 
     def __init__(self, audio_cfg, device):
-        self.n_fft, self.hop = audio_cfg.n_fft, audio_cfg.fft_hop_size
-        basis, nb_pad = windowed_dft_basis(self.n_fft, audio_cfg.fft_window_size)
+        t = self.transform = vocoder_output_transform(audio_cfg)
+        self.power = t["spec_type"] == "mel"
+        self.n_fft, self.hop = t["n_fft"], t["hop_length"]
+        basis, nb_pad = windowed_dft_basis(self.n_fft, t["win_length"])
         nb = self.n_fft // 2 + 1
         b = torch.from_numpy(basis)  # [n_fft, 2*nb_pad] interleaved (w cos, -w sin)
         self.cos = b[:, 0 : 2 * nb : 2].t().contiguous().to(device)  # [nb, n_fft]
         self.sin = b[:, 1 : 2 * nb : 2].t().contiguous().to(device)
-        self.melb = torch.from_numpy(slaney_mel_filterbank(audio_cfg.input_sampling_rate, self.n_fft, audio_cfg.n_mels,
-                                                           audio_cfg.f_min, audio_cfg.f_max)).to(device)
-        self.nb, self.n_mels = nb, audio_cfg.n_mels
+        fbank = htk_mel_filterbank if self.power else slaney_mel_filterbank
+        self.melb = torch.from_numpy(fbank(t["filter_sample_rate"], self.n_fft, t["n_mels"], t["f_min"], t["f_max"])).to(device)
+        self.nb, self.n_mels = nb, t["n_mels"]
 
     def logmel(self, audio_bt: torch.Tensor):
         fr, F = ops.stft_frames(audio_bt, self.n_fft, self.hop)
@@ -325,7 +330,7 @@ class MelLoss:
         im = torch.empty(self.nb, N, device=fr.device)
         ops.gemm(self.cos, fr, re)
         ops.gemm(self.sin, fr, im)
-        mag = ops.elementwise(ops.EW_MAG, re, im, p0=1e-9)
+        mag = ops.elementwise(ops.EW_POWER, re, im) if self.power else ops.elementwise(ops.EW_MAG, re, im, p0=1e-9)
         mel = torch.empty(self.n_mels, N, device=fr.device)
         ops.gemm(self.melb, mag, mel)
         return ops.elementwise(ops.EW_LOG_CLAMP, mel, p0=1e-5), (re, im, mag, mel)
@@ -341,8 +346,12 @@ class MelLoss:
         dmel = ops.elementwise(ops.EW_DIV_MASK, dlog, mel, p0=1e-5)
         dmag = torch.empty_like(mag)
         ops.gemm(self.melb, dmel, dmag, ta=True)
-        dre = ops.elementwise(ops.EW_MUL_DIV, dmag, re, mag)
-        dim = ops.elementwise(ops.EW_MUL_DIV, dmag, im, mag)
+        if self.power:  # d(re^2 + im^2): dre = 2 re dpower, dim = 2 im dpower
+            dre = ops.elementwise(ops.EW_SCALED_MUL, dmag, re, p0=2.0)
+            dim = ops.elementwise(ops.EW_SCALED_MUL, dmag, im, p0=2.0)
+        else:
+            dre = ops.elementwise(ops.EW_MUL_DIV, dmag, re, mag)
+            dim = ops.elementwise(ops.EW_MUL_DIV, dmag, im, mag)
         dfr = torch.empty(self.n_fft, dre.shape[1], device=dre.device)
         ops.gemm(self.cos, dre, dfr, ta=True)
         ops.gemm(self.sin, dim, dfr, ta=True, beta=1.0)
@@ -417,6 +426,19 @@ class HiFiGANTrainer(CapturedStep):
         self.precision = precision
         self.config = config or HiFiGANConfig()
         self.device = torch.device(device)
+        # the output transform (refuses a rate pair / spec_type no vocoder trains on, before anything is allocated).  A vocoder that
+        # upsamples (output_sampling_rate = c x input_sampling_rate, c > 1): one input frame is fft_hop_size c output samples
+        out_t = vocoder_output_transform(self.config.preprocessing.audio)
+        self.rate_change, self.hop_out = out_t["c"], out_t["hop_length"]
+        if self.rate_change > 1:
+            m, a = self.config.model, self.config.preprocessing.audio
+            total = self.config.gen_istft_hop_size if m.istft_layer else 1
+            for u in m.upsample_rates:
+                total *= u
+            if total != self.hop_out:
+                raise ValueError(f"model.upsample_rates {list(m.upsample_rates)}" + (f" x gen_istft_hop_size {self.config.gen_istft_hop_size}" if m.istft_layer else "")
+                                 + f" upsample by {total}, but preprocessing.audio.output_sampling_rate {a.output_sampling_rate} = {self.rate_change} x "
+                                 f"input_sampling_rate {a.input_sampling_rate} needs fft_hop_size {a.fft_hop_size} x {self.rate_change} = {self.hop_out} output samples per frame")
         self.opt = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.optimizer, self.alpha = optimizer, alpha
         self.gan_type, self.wgan_clip_value, self.generator_warmup_steps = gan_type, float(wgan_clip_value), int(generator_warmup_steps)
@@ -735,7 +757,13 @@ class HiFiGANTrainer(CapturedStep):
     # -- one GAN step -----------------------------------------------------------------------------------------
     def training_step(self, mel_bct: torch.Tensor, audio_bct: torch.Tensor, sync: bool = True):
         """mel [B, n_mels, T/hop], audio [B, 1, T] on the device.  Returns the scalar losses: python floats (ONE device-to-host
-        read at the end of the step), or with ``sync=False`` a device tensor in LOSS_KEYS order (no host synchronisation)."""
+        read at the end of the step), or with ``sync=False`` a device tensor in LOSS_KEYS order (no host synchronisation).
+        With output_sampling_rate = c x input_sampling_rate, c > 1: mel at the input rate, audio at the output rate, T = frames hop c."""
+        if self.rate_change > 1 and audio_bct.shape[-1] != mel_bct.shape[-1] * self.hop_out:
+            a = self.config.preprocessing.audio
+            raise ValueError(f"training_step: audio of {audio_bct.shape[-1]} samples for {mel_bct.shape[-1]} frames; at preprocessing.audio."
+                             f"output_sampling_rate {a.output_sampling_rate} a frame is fft_hop_size {a.fft_hop_size} x {self.rate_change} = "
+                             f"{self.hop_out} output samples: {mel_bct.shape[-1] * self.hop_out} expected")
         with step_scope(self.device, operands=self.precision, side_wgrad=self.side_wgrad and self.device.type == "cuda"):
             if self.device.type != "cuda":
                 buf = self._eager_step(mel_bct, audio_bct)

@@ -19,6 +19,7 @@ EW_LRELU, EW_LRELU_BWD, EW_TANH, EW_TANH_BWD, EW_AXPBY, EW_SCALE, EW_MUL = 0, 1,
 EW_SIGN_DIFF, EW_SQ_GRAD, EW_LOG_CLAMP, EW_DIV_MASK, EW_MAG, EW_MUL_DIV = 7, 8, 9, 10, 11, 12
 EW_SILU, EW_RELU, EW_GLU, EW_SILU_BWD, EW_RELU_BWD, EW_CLIP_SCALE = 13, 14, 15, 18, 19, 20
 EW_DIV_SCALAR, EW_STFT_GRAD_DEV, EW_FILL, EW_SCALE_DIV_SCALAR = 21, 22, 23, 24
+EW_POWER, EW_SCALED_MUL = 26, 27  # (25 is not assigned) re^2 + im^2 and p0 * a * b (spec_type "mel": the power spectrum and its backward)
 ACT_NONE, ACT_LRELU, ACT_SILU, ACT_RELU, ACT_TANH = 0, 1, 2, 3, 4
 _ACT_EW = {ACT_LRELU: EW_LRELU, ACT_SILU: EW_SILU, ACT_RELU: EW_RELU, ACT_TANH: EW_TANH}  # the epilogue activations as a pass of their own
 

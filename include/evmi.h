@@ -624,7 +624,8 @@ int evmi_lrelu_bwd_rowsum_f32(const float* dy_dev, const float* y_dev, float* dp
 int evmi_row_reduce_f32(int mode, const float* a_dev, const float* b_dev, float* out_dev, int rows,
                         long long n_per_row, float scale, int accumulate, void* stream);
 /* Elementwise ops (op codes documented in csrc/train_ops.hip: leaky-relu / tanh and their
- * derivatives, axpby, products, L1 / LSGAN loss derivatives, log-clamp, the mel-loss chain, SiLU / ReLU / GLU). */
+ * derivatives, axpby, products, L1 / LSGAN loss derivatives, log-clamp, the mel-loss chain with the magnitude (11, 12) or the power
+ * spectrum (26, 27), SiLU / ReLU / GLU).  Op codes 0 .. 24, 26 and 27 (25 is not assigned and is refused); 26 and 27 read b. */
 int evmi_elementwise_f32(int op, const float* a_dev, const float* b_dev, const float* c_dev,
                          float* y_dev, long long n, float p0, float p1, void* stream);
 /* out[0] (+)= scale * sum f;  mode 0: |a-b|, 1: (a-p)^2, 2: a   (fixed order: reproducible). */
