@@ -249,6 +249,9 @@ SYMBOLS = {
     "evmi_conv_generic_weight_elems": (C.c_longlong, [C.c_int] * 3),
     "evmi_conv_generic_relayout_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "evmi_conv_generic_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_longlong] * 3 + [C.c_float] * 3 + [C.c_int, C.c_void_p]),
+    "evmi_istft_head_weight_elems": (C.c_longlong, [C.c_int] * 2),
+    "evmi_istft_head_frame_tile": (C.c_int, [C.c_int] * 2),
+    "evmi_istft_head_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
     "evmi_conv_tc_supported": (C.c_int, [C.c_int] * 4),
     "evmi_conv_tc_relayout_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "evmi_conv_tc_tile_layout": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3),

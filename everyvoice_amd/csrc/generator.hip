@@ -20,6 +20,7 @@
 
 #include "conv_tc_generic.h"
 #include "conv_tc_mfma.h"
+#include "istft_head_generic.h"
 #include "resblock_branch_kernel.h"
 #include "resblock_pair_kernel.h"
 
@@ -43,7 +44,7 @@ int launch_nct_f32_to_tc_bf16(const float*, bf16_t*, int, int, int, int, hipStre
 int launch_conv_post_tanh(const bf16_t*, const float*, float, float*, int, int, int, int, float, hipStream_t);
 int launch_istft_head(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, hipStream_t);
 int launch_reflect_pad_left1_f32(const float*, float*, long long, int, float, hipStream_t);
-int launch_istft_f32(const float*, float*, int, int, hipStream_t);
+int launch_istft_f32(const float*, float*, int, int, int, int, hipStream_t);
 
 struct WeightSpec {
   std::string name;
@@ -106,6 +107,8 @@ struct evmi_generator {
   std::vector<std::vector<size_t>> tc_pair_w;           // element offsets of the pair's [KS][C][C] weights (w1 then w2)
   int n_cu = 256;
   size_t istft_w_off = 0, istft_b_off = 0;
+  bool istft_generic = false;  // the generic-size head (istft_head_generic.h) instead of the specialised kernel
+  std::string istft_kernel = "istft_head";
   bool use_pairs = true;
 
   DevBuf ws;
@@ -157,6 +160,17 @@ static void build_specs(evmi_generator* g) {
   add("conv_post.bias", post_out);
 }
 
+// What no precision runs: torch.istft refuses these too (hop == n_fft: the window-square envelope reaches zero)
+static int validate_istft(const evmi_generator_config& c) {
+  if (!c.istft_layer) return EVMI_OK;
+  if (c.istft_n_fft < 2 || c.istft_n_fft % 2)
+    return fail(EVMI_ERR_INVALID_ARG, "config: gen_istft_n_fft = " + std::to_string(c.istft_n_fft) + ": must be even and at least 2");
+  if (c.istft_hop < 1 || c.istft_hop >= c.istft_n_fft)
+    return fail(EVMI_ERR_INVALID_ARG, "config: gen_istft_hop_size = " + std::to_string(c.istft_hop) + ": must be at least 1 and below gen_istft_n_fft = " +
+                                          std::to_string(c.istft_n_fft));
+  return EVMI_OK;
+}
+
 static int validate_cfg(const evmi_generator_config& c) {
   if (c.n_mels <= 0 || c.upsample_initial_channel <= 0) return fail(EVMI_ERR_INVALID_ARG, "config: channels");
   if (c.num_upsamples <= 0 || c.num_upsamples > EVMI_MAX_UPSAMPLES) return fail(EVMI_ERR_INVALID_ARG, "config: num_upsamples");
@@ -173,7 +187,7 @@ static int validate_cfg(const evmi_generator_config& c) {
     for (int m = 0; m < c.num_dilations[j]; ++m)
       if (c.resblock_dilations[j][m] <= 0) return fail(EVMI_ERR_INVALID_ARG, "config: dilation");
   }
-  return EVMI_OK;
+  return validate_istft(c);
 }
 
 // ---- bf16 weight preparation -----------------------------------------------------------------------
@@ -250,11 +264,16 @@ static std::string bf16_refusal(const evmi_generator_config& c) {
                " with kernel " + std::to_string(k) + ": (kernel - 1) * dilation exceeds the halo limit of " + std::to_string(kGenericMaxHalo) + " rows";
   }
   if (c.istft_layer) {
-    if (c.istft_n_fft != 16 || c.istft_hop != 4)
-      return "gen_istft_n_fft / gen_istft_hop_size: the iSTFT head takes only n_fft 16 / hop 4 (the reference's gen_istft_* values)";
+    if (!istft_head_nfft_ok(c.istft_n_fft))
+      return "gen_istft_n_fft = " + std::to_string(c.istft_n_fft) + ": the iSTFT head takes an even n_fft from " + std::to_string(kIstftMinNfft) +
+             " to " + std::to_string(kIstftMaxNfft);
+    if (!istft_head_hop_ok(c.istft_n_fft, c.istft_hop))
+      return "gen_istft_hop_size = " + std::to_string(c.istft_hop) + ": the iSTFT head takes a hop from 1 to gen_istft_n_fft / 2 = " +
+             std::to_string(c.istft_n_fft / 2) + " (beyond it the window-square envelope is ill-conditioned)";
     const int cl = c.upsample_initial_channel >> c.num_upsamples;
-    if (!(cl == 32 || cl == 64 || cl == 128))
-      return "upsample_initial_channel: the iSTFT head takes 32, 64 or 128 input channels, not " + std::to_string(cl);
+    if (!istft_head_channels_ok(cl))
+      return "upsample_initial_channel = " + std::to_string(c.upsample_initial_channel) + ": the iSTFT head takes at most " +
+             std::to_string(kIstftMaxC) + " input channels, not " + std::to_string(cl);
   }
   return "";
 }
@@ -376,20 +395,31 @@ static int prepare_tc(evmi_generator* g) {
     }
   }
   if (c.istft_layer) {
-    // conv_post of the iSTFT head: w[18][c][7] -> bf16 [7][32][c] (rows >= 18 zero), bias [32]
     const int cl = g->ch(c.num_upsamples);
-    if (!(cl == 32 || cl == 64 || cl == 128)) return missing("istft head c_in=" + std::to_string(cl));
     const int co = c.istft_n_fft + 2;
     const std::vector<float>& w = g->host_w["conv_post.weight"];
     const std::vector<float>& bs = g->host_w["conv_post.bias"];
+    g->istft_generic = !istft_head_specialised(cl, c.istft_n_fft, c.istft_hop);
     g->istft_w_off = warena.size();
-    warena.resize(warena.size() + (size_t)7 * 32 * cl, 0);
-    for (int m = 0; m < co; ++m)
-      for (int ci = 0; ci < cl; ++ci)
-        for (int j = 0; j < 7; ++j)
-          warena[g->istft_w_off + ((size_t)j * 32 + m) * cl + ci] = f32_to_bf16_bits(w[((size_t)m * cl + ci) * 7 + j]);
     g->istft_b_off = barena.size();
-    barena.resize(barena.size() + 32, 0.f);
+    if (g->istft_generic) {
+      // conv_post of the generic head: the zero-padded image of the generic convolution, bias [n_fft + 2]
+      char buf[48];
+      snprintf(buf, sizeof buf, "istft_head_generic<c%d,n%d,h%d>", cl, c.istft_n_fft, c.istft_hop);
+      g->istft_kernel = buf;
+      warena.resize(warena.size() + (size_t)conv_generic_weight_elems(cl, co, kIstftKs), 0);
+      relayout_conv_generic(w.data(), co, cl, cl, kIstftKs, warena, g->istft_w_off);
+      barena.resize(barena.size() + (size_t)round_up8(co), 0.f);
+    } else {
+      // conv_post of the specialised head: w[18][c][7] -> bf16 [7][32][c] (rows >= 18 zero), bias [32]
+      g->istft_kernel = "istft_head";
+      warena.resize(warena.size() + (size_t)7 * 32 * cl, 0);
+      for (int m = 0; m < co; ++m)
+        for (int ci = 0; ci < cl; ++ci)
+          for (int j = 0; j < 7; ++j)
+            warena[g->istft_w_off + ((size_t)j * 32 + m) * cl + ci] = f32_to_bf16_bits(w[((size_t)m * cl + ci) * 7 + j]);
+      barena.resize(barena.size() + 32, 0.f);
+    }
     for (int m = 0; m < co; ++m) barena[g->istft_b_off + m] = bs[m];
   } else
   // conv_post: w[1][c][7] -> [7][c] fp32
@@ -466,13 +496,19 @@ struct Recorder {
     if (_rc != EVMI_OK) return _rc; \
   } while (0)
 
-static size_t stage_elems_max(const evmi_generator* g, int B, int T) {
+// Elements of one of the five activation buffers.  f32: the exact path also keeps the iSTFT head's logits Z [B][n_fft + 2][len + 1]
+// in one of them (the bf16 heads keep theirs in LDS).
+static size_t stage_elems_max(const evmi_generator* g, int B, int T, bool f32) {
   size_t mx = (size_t)B * T * g->cfg.upsample_initial_channel;
   size_t len = T;
   for (int i = 0; i < g->cfg.num_upsamples; ++i) {
     len *= g->cfg.upsample_rates[i];
     const size_t e = (size_t)B * (len + 1) * g->ch(i + 1);  // + 1 row: the iSTFT head's reflection pad
     if (e > mx) mx = e;
+  }
+  if (f32 && g->cfg.istft_layer) {
+    const size_t z = (size_t)B * (len + 1) * (g->cfg.istft_n_fft + 2);
+    if (z > mx) mx = z;
   }
   return mx;
 }
@@ -482,7 +518,7 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, int T, hipStream_t s, Recorder& rec) {
   const auto& c = g->cfg;
   if (!g->tc_ok) return fail(EVMI_ERR_UNSUPPORTED, "bf16 MFMA path unavailable: " + g->tc_why);
-  const size_t se = align_up(stage_elems_max(g, B, T), 64);
+  const size_t se = align_up(stage_elems_max(g, B, T, false), 64);
   const size_t in_e = align_up((size_t)B * T * round_up8(c.n_mels), 64);
   EVMI_TRY(g->ws.ensure((in_e + 5 * se) * 2));
   bf16_t* base = (bf16_t*)g->ws.p;
@@ -613,8 +649,11 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
   const int cl = g->ch(c.num_upsamples);
   EVMI_TRY(rec.begin());
   if (c.istft_layer) {
-    EVMI_TRY(launch_istft_head(A, warena + g->istft_w_off, barena + g->istft_b_off, wav, B, len, cl, s));
-    EVMI_TRY(rec.end("istft_head", "conv_post+istft", 2.0 * B * (double)(len + 1) * cl * 7 * (c.istft_n_fft + 2),
+    if (g->istft_generic)
+      EVMI_TRY(launch_istft_head_generic(A, warena + g->istft_w_off, barena + g->istft_b_off, wav, B, len, cl, c.istft_n_fft, c.istft_hop, s));
+    else
+      EVMI_TRY(launch_istft_head(A, warena + g->istft_w_off, barena + g->istft_b_off, wav, B, len, cl, s));
+    EVMI_TRY(rec.end(g->istft_kernel.c_str(), "conv_post+istft", 2.0 * B * (double)(len + 1) * cl * 7 * (c.istft_n_fft + 2),
                      (double)B * len * (2.0 * cl + 4.0 * c.istft_hop)));
   } else {
     EVMI_TRY(launch_conv_post_tanh(A, (const float*)g->post_w.p, g->post_bias, wav, B, len, cl, 7, 1.f, s));
@@ -625,9 +664,7 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
 
 static int forward_f32(evmi_generator* g, const float* mel, float* wav, int B, int T, hipStream_t s, Recorder& rec) {
   const auto& c = g->cfg;
-  if (c.istft_layer && (c.istft_n_fft != 16 || c.istft_hop != 4))
-    return fail(EVMI_ERR_UNSUPPORTED, "iSTFT head: only n_fft 16 / hop 4 (the reference's gen_istft_* values)");
-  const size_t se = align_up(stage_elems_max(g, B, T), 64);
+  const size_t se = align_up(stage_elems_max(g, B, T, true), 64);
   EVMI_TRY(g->ws.ensure(5 * se * 4));
   float* buf[5];
   for (int i = 0; i < 5; ++i) buf[i] = (float*)g->ws.p + (size_t)i * se;
@@ -693,7 +730,7 @@ static int forward_f32(evmi_generator* g, const float* mel, float* wav, int B, i
     EVMI_TRY(rec.end("reflect_pad_left1_f32", "reflection_pad", 0.0, 8.0 * B * cl * len));
     EVMI_TRY(conv("conv_post", XP, "conv_post", nullptr, Z, cl, len + 1, c.istft_n_fft + 2, 7, 3, 1, 1.f, 1.f, 0));
     EVMI_TRY(rec.begin());
-    EVMI_TRY(launch_istft_f32(Z, wav, B, len + 1, s));
+    EVMI_TRY(launch_istft_f32(Z, wav, B, len + 1, c.istft_n_fft, c.istft_hop, s));
     return rec.end("istft_f32", "istft", 0.0, 4.0 * B * len * (c.istft_n_fft + 2 + c.istft_hop));
   }
   EVMI_TRY(conv("conv_post", A, "conv_post", nullptr, wav, cl, len, 1, 7, 3, 1, c.post_lrelu_slope, 1.f, 0));
@@ -789,6 +826,7 @@ int evmi_generator_bf16_check(const evmi_generator_config* cfg) {
   const evmi_generator_config& c = *cfg;
   bool counts_ok = c.num_upsamples > 0 && c.num_upsamples <= EVMI_MAX_UPSAMPLES && c.num_kernels > 0 && c.num_kernels <= EVMI_MAX_RESBLOCK_KERNELS;
   for (int j = 0; counts_ok && j < c.num_kernels; ++j) counts_ok = c.num_dilations[j] > 0 && c.num_dilations[j] <= EVMI_MAX_DILATIONS;
+  EVMI_TRY(validate_istft(c));  // what no precision runs is an invalid argument, not a bf16 refusal
   if (counts_ok) {  // (bf16_refusal walks the arrays by these counts)
     const std::string why = bf16_refusal(c);
     if (!why.empty()) return fail(EVMI_ERR_UNSUPPORTED, why);
@@ -800,7 +838,7 @@ int evmi_generator_hop(const evmi_generator* g) { return g ? g->hop() : 0; }
 
 int64_t evmi_generator_workspace_bytes(const evmi_generator* g, int B, int T, int precision) {
   if (!g || B <= 0 || T <= 0) return 0;
-  const size_t se = align_up(stage_elems_max(g, B, T), 64);
+  const size_t se = align_up(stage_elems_max(g, B, T, precision != EVMI_PREC_BF16), 64);
   if (precision == EVMI_PREC_BF16) return (int64_t)((align_up((size_t)B * T * round_up8(g->cfg.n_mels), 64) + 5 * se) * 2);
   return (int64_t)(5 * se * 4);
 }

@@ -1,6 +1,6 @@
 // iSTFTNet output head: reflection pad (1,0) -> conv_post (C -> n_fft+2, k7) -> exp / sin -> inverse STFT
-// (n_fft 16, hop 4, periodic hann, centred) -> waveform.  One fused kernel on the bf16 path; small fp32
-// kernels for the exact-arithmetic path.
+// (n_fft 16, hop 4, periodic hann, centred) -> waveform.  One fused kernel on the bf16 path (this size on 32 / 64 / 128 channels;
+// every other size: istft_head_generic.hip); small fp32 kernels for the exact-arithmetic path, at any n_fft / hop.
 //
 //   z[f][c]   = b[c] + sum_{j<7} sum_ci W[c][ci][j] * xpad[f + j - 3][ci],   xpad[0] = x[1], xpad[q] = x[q-1]
 //   mag[f][b] = exp(z[f][b]),  phi[f][b] = sin(z[f][9 + b]),   b in [0, 8]
@@ -157,31 +157,30 @@ __global__ void reflect_pad_left1_f32_kernel(const float* __restrict__ x, float*
   xp[idx] = v > 0.f ? v : v * slope;
 }
 
-// z [B][18][F] (conv_post output) -> wav [B][4 (F-1)]
-__global__ void istft_f32_kernel(const float* __restrict__ z, float* __restrict__ wav, int F) {
-  const int n_out = IS_HOP * (F - 1);
+// z [B][n_fft + 2][F] (conv_post output) -> wav [B][hop (F-1)]; any even n_fft >= 2, 1 <= hop < n_fft
+__global__ void istft_f32_kernel(const float* __restrict__ z, float* __restrict__ wav, int F, int n_fft, int hop) {
+  const int n_out = hop * (F - 1);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
   if (t >= n_out) return;
-  const float* zb = z + (long long)b * 2 * IS_BINS * F;
-  const int p = t + IS_NFFT / 2;
+  const int bins = n_fft / 2 + 1;
+  const float* zb = z + (long long)b * 2 * bins * F;
+  const int p = t + n_fft / 2;
   float s = 0.f, env = 0.f;
-  for (int d = 0; d < IS_NFFT / IS_HOP; ++d) {
-    const int f = p / IS_HOP - d;
-    const int k = p - IS_HOP * f;
-    if (f < 0 || f >= F) continue;
+  for (int f = p / hop, k = p - hop * f; k < n_fft && f >= 0; --f, k += hop) {
+    if (f >= F) continue;
     float acc = 0.f;
-    for (int bb = 0; bb < IS_BINS; ++bb) {
+    for (int bb = 0; bb < bins; ++bb) {
       const float m = expf(zb[(long long)bb * F + f]);
-      const float phi = sinf(zb[(long long)(IS_BINS + bb) * F + f]);
-      const float th = 6.283185307179586f * ((bb * k) % IS_NFFT) / IS_NFFT;
+      const float phi = sinf(zb[(long long)(bins + bb) * F + f]);
+      const float th = 6.283185307179586f * (int)(((long long)bb * k) % n_fft) / n_fft;
       const float re = m * cosf(phi), im = m * sinf(phi);
       if (bb == 0) acc += re;
-      else if (bb == IS_BINS - 1) acc += (k & 1) ? -re : re;
+      else if (bb == bins - 1) acc += (k & 1) ? -re : re;
       else acc += 2.f * (re * cosf(th) - im * sinf(th));
     }
-    const float wk = hann16(k);
-    s += acc * wk * (1.f / IS_NFFT);
+    const float wk = 0.5f - 0.5f * cosf(6.283185307179586f * k / n_fft);
+    s += acc * wk * (1.f / n_fft);
     env += wk * wk;
   }
   wav[(long long)b * n_out + t] = s / env;
@@ -207,9 +206,11 @@ int launch_reflect_pad_left1_f32(const float* x, float* xp, long long n_rows, in
   return EVMI_OK;
 }
 
-int launch_istft_f32(const float* z, float* wav, int B, int F, hipStream_t s) {
-  const int n_out = IS_HOP * (F - 1);
-  hipLaunchKernelGGL(istft_f32_kernel, dim3((n_out + 255) / 256, B), dim3(256), 0, s, z, wav, F);
+int launch_istft_f32(const float* z, float* wav, int B, int F, int n_fft, int hop, hipStream_t s) {
+  if (n_fft < 2 || n_fft % 2 || hop < 1 || hop >= n_fft) return fail(EVMI_ERR_INVALID_ARG, "istft_f32: n_fft must be even, 1 <= hop < n_fft");
+  if ((long long)hop * (F - 1) > 0x7fffffffll - n_fft) return fail(EVMI_ERR_INVALID_ARG, "istft_f32: more than 2^31 samples per item");
+  const int n_out = hop * (F - 1);
+  hipLaunchKernelGGL(istft_f32_kernel, dim3((n_out + 255) / 256, B), dim3(256), 0, s, z, wav, F, n_fft, hop);
   EVMI_LAUNCH_CHECK("istft_f32");
   return EVMI_OK;
 }

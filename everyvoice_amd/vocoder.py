@@ -106,6 +106,13 @@ class Generator(nn.Module):
         post_out = config.gen_istft_n_fft + 2 if m.istft_layer else 1
         self.conv_post = _ConvParams(post_out, ch_last, 7, bias=post_out)
         self._c_cfg = _model_cfg_to_c(config)
+        if m.istft_layer:
+            # what no precision runs (torch.istft refuses it too) is refused here, before any device work
+            n_fft, hop = config.gen_istft_n_fft, config.gen_istft_hop_size
+            if n_fft < 2 or n_fft % 2:
+                raise ValueError(f"gen_istft_n_fft = {n_fft}: the iSTFT head needs an even n_fft of at least 2")
+            if hop < 1 or hop >= n_fft:
+                raise ValueError(f"gen_istft_hop_size = {hop}: the iSTFT head needs 1 <= hop < gen_istft_n_fft = {n_fft}")
         if precision == "bf16":
             # what the bf16 kernels cannot take is refused here, not by the first forward (host arithmetic: no GPU needed)
             lib = _lib.load()

@@ -174,8 +174,8 @@ typedef struct evmi_generator_config {
   float lrelu_slope;      /* activation_function: original_hifigan_leaky_relu = 0.1          */
   float post_lrelu_slope; /* slope before conv_post (upstream F.leaky_relu default 0.01)     */
   int istft_layer;        /* 0: conv_post -> tanh ; 1: iSTFTNet head                         */
-  int istft_n_fft;        /* 16 */
-  int istft_hop;          /* 4  */
+  int istft_n_fft;        /* gen_istft_n_fft (16): even, >= 2; EVMI_PREC_BF16: 4 .. 128            */
+  int istft_hop;          /* gen_istft_hop_size (4): 1 <= hop < n_fft; EVMI_PREC_BF16: <= n_fft / 2 */
 } evmi_generator_config;
 
 typedef struct evmi_generator evmi_generator; /* opaque */
@@ -203,7 +203,9 @@ int evmi_generator_finalize(evmi_generator* g);
  * EVMI_ERR_UNSUPPORTED / EVMI_ERR_INVALID_ARG with evmi_last_error() naming the field.  bf16 takes any n_mels, any stage channel
  * count that is a multiple of 8, any odd resblock kernel with (kernel - 1) * dilation <= 256, any upsampler with kernel >= rate
  * and (kernel - rate) even; shapes outside the specialised kernel tables run on the generic-shape kernel (evmi_conv_generic_bf16).
- * The iSTFT head: gen_istft_n_fft 16 / hop 4 and 32 / 64 / 128 input channels only. */
+ * The iSTFT head: gen_istft_n_fft even in [4, 128], 1 <= gen_istft_hop_size <= n_fft / 2, at most 512 input channels
+ * (evmi_istft_head_bf16); n_fft 16 / hop 4 on 32 / 64 / 128 channels keeps its specialised kernel.  An odd n_fft, a hop < 1 or
+ * >= n_fft is EVMI_ERR_INVALID_ARG here and in evmi_generator_create: no precision runs it. */
 int evmi_generator_bf16_check(const evmi_generator_config* cfg);
 
 /* Samples produced per mel frame (prod(upsample_rates) [* istft_hop]). */
@@ -473,6 +475,26 @@ int evmi_conv_generic_relayout_f32(const float* w_dev, void* dst_bf16_dev, int c
 int evmi_conv_generic_bf16(const void* x, const void* w_laid, const float* bias_dev, const void* res, void* out, int B, int t_in, int n_rows,
                            int c_in, int c_out, int ks, int dil, int pad, long long out_row_stride, long long out_shift, long long out_limit,
                            float pre_slope, float post_slope, float out_scale, int accumulate, void* stream);
+/* ---- The iSTFTNet output head alone (csrc/istft_head.hip: the specialised kernel; csrc/istft_head_generic.hip: any size):
+ * reflection pad (1, 0) -> conv_post (C -> n_fft + 2, k 7) -> exp / sin -> torch.istft(mag * e^{i phi}, n_fft, hop, n_fft, periodic
+ * hann, center = True).  The logits stay fp32 from the MFMA accumulators to the waveform.
+ *   x_dev      bf16 [B][L][C], time-major, the 0.01 leaky-relu in front of conv_post already applied
+ *   w_dev      fp32 [n_fft + 2][C][7] (torch layout), bias_dev fp32 [n_fft + 2]
+ *   w_laid_dev device scratch of evmi_istft_head_weight_elems(C, n_fft) bf16 elements (16-byte aligned): the call writes the kernel's
+ *              weight image there on `stream` before the launch
+ *   wav_dev    fp32 [B][hop * L]
+ *   variant    0: the kernel the generator picks (the specialised one exactly at n_fft 16 / hop 4 on 32 / 64 / 128 channels, the
+ *              generic one elsewhere); 1: always the generic one
+ * Domain: C a multiple of 8 in [8, 512]; n_fft even in [4, 128]; 1 <= hop <= n_fft / 2 (beyond it the window-square envelope
+ * falls to w^2[1] and the division is ill-conditioned).  Outside it: EVMI_ERR_UNSUPPORTED; null pointers, B < 1, L < 1, an
+ * unknown variant: EVMI_ERR_INVALID_ARG; both before any launch.
+ *   evmi_istft_head_weight_elems  0 outside the domain
+ *   evmi_istft_head_frame_tile    frames per workgroup of the generic kernel at (n_fft, hop) (0 outside the domain): a workgroup
+ *                                 yields hop * (tile - 2 * ((n_fft / 2 - 1) / hop) - 1) samples and recomputes the halo frames */
+long long evmi_istft_head_weight_elems(int C, int n_fft);
+int evmi_istft_head_frame_tile(int n_fft, int hop);
+int evmi_istft_head_bf16(const void* x_dev, const float* w_dev, const float* bias_dev, void* w_laid_dev, float* wav_dev, int B, int L,
+                         int C, int n_fft, int hop, int variant, void* stream);
 long long evmi_conv1d_wgrad_tm_bf16_ws_elems(long long rows, int c_in, int c_out, int k, int dil);
 int evmi_conv1d_wgrad_tm_bf16(const void* x_tm, const void* dy_tm, float* dw_dev, float* ws_dev, long long ws_elems, long long rows,
                               int c_in, int c_out, int k, int pad, int dil, int accumulate, void* stream);
