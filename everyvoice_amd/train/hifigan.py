@@ -26,6 +26,9 @@ different discriminators overlap on the device instead of queueing behind each o
 
 from __future__ import annotations
 
+import os
+from dataclasses import dataclass
+
 import torch
 
 from .. import _lib
@@ -122,8 +125,6 @@ class GeneratorT:
         self.fused_pairs = True  # residual pairs as ag.resblock_pair (False: the unfused op sequence, for A/B tests)
         # precision="bf16": the residual stacks in time-major bf16 on the inference convolution kernels (train/mrf_tm.py) where
         # those kernels take the stage's shapes; False: the channel-major packed path everywhere (A/B switch, other configurations)
-        import os
-
         self.time_major = os.environ.get("EVMI_TRAIN_TM", "1") == "1"
         self._tm_stages: dict = {}
         self.istft = bool(m.istft_layer)
@@ -245,9 +246,7 @@ def _chain_for(disc, period: int, x: torch.Tensor):
     return ch if ch.ok else None
 
 
-import os as _os
-
-_DISC_CHAIN = _os.environ.get("EVMI_DISC_CHAIN", "1") == "1"
+_DISC_CHAIN = os.environ.get("EVMI_DISC_CHAIN", "1") == "1"
 
 
 class DiscriminatorPT:
@@ -407,6 +406,70 @@ class MultiResolutionSTFTLoss:
         return grad
 
 
+@dataclass(frozen=True)
+class _DiscFacts:
+    """What the step's schedule needs to know of one discriminator (fixed at construction)."""
+    spectral: bool  # spectral norm: real and generated waveforms go through two calls (each runs its own power iteration)
+    scale: int      # pyramid level of its input: 0 the waveform itself (period discriminators, first scale), 1.. the pooled scales
+    slot: int       # its stream in the discriminator step (a spectral-norm one: slot and slot + 1)
+
+    @property
+    def reads_waveform(self) -> bool:
+        return self.scale == 0
+
+
+@dataclass(frozen=True)
+class _Chain:
+    """One branch of the generator step's discriminator pass (``g_step_routing``)."""
+    disc: int | None  # index into ``discriminators()``; None: the reconstruction loss
+    role: str         # "g_both" ([real | generated] as one batch), "g_fake", "g_real" or "recon"
+    kind: str | None  # its input: "pair", "fake", "real"
+    level: int        # ... at this pyramid level
+    branch: int       # fork / join branch = pool stream
+    order: int        # position in host issue order
+
+
+def g_step_routing(facts, pair_mode: bool) -> list:
+    """Which discriminator sees which input on which stream in which host order, in the generator step.  A two-call discriminator
+    runs "g_fake" (with backward) and "g_real" (forward only); the others run ONE "g_both" chain over [real | generated].  Two-call:
+    every discriminator without ``pair_mode`` (packed chains: precision "bf16"), the spectral-norm ones with it.  Branches: the
+    gradient-carrying chain of discriminator i on i, then the real chains, then the reconstruction loss.  Host order decides which
+    prepared spectral-norm call a chain receives: the real chains of those discriminators are issued first."""
+    two_call = [i for i, f in enumerate(facts) if f.spectral or not pair_mode]
+    rows = [(i, "g_fake", "fake") if i in two_call else (i, "g_both", "pair") for i in range(len(facts))]
+    rows += [(i, "g_real", "real") for i in two_call] + [(None, "recon", None)]
+    first = [j for j, (i, role, _) in enumerate(rows) if role == "g_real" and facts[i].spectral]
+    issue = first + [j for j in range(len(rows)) if j not in first]
+    return [_Chain(i, role, kind, 0 if i is None else facts[i].scale, j, issue.index(j)) for j, (i, role, kind) in enumerate(rows)]
+
+
+def routing_pyramids(chains) -> list:
+    """The inputs whose pooled pyramid the generator step builds, in the order it records them: [real | generated] whenever a chain
+    reads it; real and generated only when a two-call discriminator sits behind the pooling."""
+    kinds = ["pair"] if any(c.kind == "pair" for c in chains) else []
+    return kinds + (["real", "fake"] if any(c.kind == "fake" and c.level > 0 for c in chains) else [])
+
+
+@dataclass
+class _Step:
+    """The state of one GAN step, handed from phase to phase."""
+    B: int = 0
+    y: torch.Tensor | None = None      # the real waveforms [1, B, T]
+    y_hat: ag.Var | None = None        # the generated ones
+    g_tape: ag.Tape | None = None
+    d_layers: tuple = ()
+    frag_join: object = None           # joins the weight-normed chains' fragments started beside the generator's forward
+    d_ins: list | None = None          # discriminator step: [real | generated] at every discriminator's pyramid level
+    # data parallel only: the generator's backward is handed out bucket by bucket
+    g_segmented: bool = False
+    g_stop: object = None              # stop(tag) -> bool: the cuts worth a stretch boundary
+    g_segments: object = None          # the iterator of ``g_tape.backward_segments``
+
+    def clear(self):
+        """Drop every reference (a captured graph's pool must not be kept alive by one)."""
+        self.__dict__.update(_Step().__dict__)
+
+
 class HiFiGANTrainer(CapturedStep):
     """Generator + MPD + MSD with two optimisers; ``training_step`` is one full GAN step."""
 
@@ -450,6 +513,11 @@ class HiFiGANTrainer(CapturedStep):
         self.msd = [DiscriminatorST(self.d_params, f"msd.discriminators.{i}", spectral=(i == 0)) for i in range(m.msd_layers)]
         self.g_params.finalize()
         self.d_params.finalize()
+        self._disc_facts, slot = [], 0
+        for i, d in enumerate(self.discriminators()):
+            spectral = any(isinstance(layer, SNConv) for layer in d.layers())
+            self._disc_facts.append(_DiscFacts(spectral, max(0, i - len(self.mpd)), slot))
+            slot += 2 if spectral else 1
         # weight norm of all layers of an optimiser in one launch (forward), one launch per gradient bucket (backward)
         self._wn_batches = [WNBatch(self.g_params, self.generator.layers()), WNBatch(self.d_params, self.d_layers())]
         self.mel_loss = MelLoss(self.config.preprocessing.audio, self.device)
@@ -479,8 +547,6 @@ class HiFiGANTrainer(CapturedStep):
         # segmentation fault inside hipStreamEndCapture on ROCm 7.0, and graph mode is the faster one
         self.side_wgrad = bool(side_wgrad) and parallel_streams and not self.use_graph
         self._graph_init()
-        import os
-
         self.phase_times = {} if os.environ.get("EVMI_PHASE_TIMES") else None
         self.branch_times = None
         if self.phase_times is not None:
@@ -603,12 +669,6 @@ class HiFiGANTrainer(CapturedStep):
                 if ch is not None:
                     ch.epoch += 1
 
-    def _reducer(self, group: ParamGroup):
-        """Bucketed all-reduce of one optimiser's flat gradient buffer, overlapped with backward (None on one GPU)."""
-        if self.pg is None:
-            return None
-        return BucketReducer(group.grad, self.pg if self.pg is not True else None)
-
     @staticmethod
     def _bucket_range(group: ParamGroup, layers):
         """[lo, hi) of the flat buffers that the parameters of `layers` (a contiguous run in declaration order) occupy."""
@@ -617,10 +677,11 @@ class HiFiGANTrainer(CapturedStep):
         hi = max(group.offset_of(n) + (group.gradient(group._index[n]).numel() + 3) // 4 * 4 for n in names)
         return lo, hi
 
-    def _bucket_hook(self, tape, group: ParamGroup, layers, reducer):
+    def _bucket_hook(self, tape, group: ParamGroup, layers, cut: bool = False):
         """Record, BEFORE the forward of `layers`, the closure that backward runs AFTER all of their gradient closures: turn
-        the effective-weight gradients into parameter gradients and hand the now-final slice of the flat gradient buffer to the
-        reducer (on whatever stream this bucket's backward ran on)."""
+        the effective-weight gradients into parameter gradients (on whatever stream this bucket's backward ran on); their slice of
+        the flat gradient buffer is final then.  ``cut`` (the generator's tape): mark that point with the slice's range, for a
+        data-parallel step that hands the backward out bucket by bucket (backward reaches `done` first, then the cut)."""
         def done():
             ops.wgrad_join()  # this bucket's weight-gradient kernels (queued beside the chain) before their results are used
             batches = {}
@@ -632,8 +693,8 @@ class HiFiGANTrainer(CapturedStep):
                     batches.setdefault(id(b), (b, []))[1].append(layer)
             for b, ls in batches.values():
                 b.finish(ls)
-            if reducer is not None:
-                reducer.launch(*self._bucket_range(group, layers))
+        if cut:
+            tape.cut(tag=self._bucket_range(group, layers))
         tape.record(done)
 
     # -- discriminators --------------------------------------------------------------------------------------
@@ -666,7 +727,7 @@ class HiFiGANTrainer(CapturedStep):
             ops.elementwise(ops.EW_SQ_GRAD, logits, out=grad, p0=1.0 / n, p1=tgt)
 
     def _sn_layers(self):
-        return [layer for layer in self.d_layers() if isinstance(layer, SNConv)]
+        return [layer for d, f in zip(self.discriminators(), self._disc_facts) if f.spectral for layer in d.layers()]
 
     def _fragments_beside(self, probe: torch.Tensor, generator_step: bool):
         """The weight-normed chains' fragments (280 MB of weights re-laid: ~0.6 ms when it runs alone) on a side stream, forked here;
@@ -689,11 +750,11 @@ class HiFiGANTrainer(CapturedStep):
         the optimiser step, so this part runs early, beside other work: ``_fragments_beside``), "sn" (the spectral-norm scale: its
         per-call weights exist once ``_prepare_spectral_norm`` has run) or "all"."""
         jobs = []
-        for d in self.discriminators():
+        for d, facts in zip(self.discriminators(), self._disc_facts):
             chain = _chain_for(d, getattr(d, "period", 1), probe)
             if chain is None:
                 continue
-            sn = any(isinstance(layer, SNConv) for layer in d.layers())
+            sn = facts.spectral
             if which != "all" and sn != (which == "sn"):
                 continue
             # spectral norm: two calls (real, generated) with their own weights; in the generator step only the generated call runs backward
@@ -718,18 +779,15 @@ class HiFiGANTrainer(CapturedStep):
         else:
             self._logit_loss(o.data, o.grad, kind == "real", o.data.numel(), slot)
 
-    def _d_branch(self, tape, i: int, d, pair: ag.Var, reducer):
+    def _d_branch(self, tape, i: int, d, pair: ag.Var):
         """Discriminator step of one weight-normed discriminator: real and generated waveforms as ONE batch of 2B items (columns
         of the same GEMMs), its loss terms (into slot i); the recorded backward ends with its gradient bucket."""
-        self._bucket_hook(tape, self.d_params, d.layers(), reducer)
+        self._bucket_hook(tape, self.d_params, d.layers())
         self._d_losses(d.forward(tape, pair)[0], "pair", self._slots[0, i : i + 1])
 
     def _d_branch_sn(self, tape, i: int, d, audio: torch.Tensor, kind: str):
         """One of the two forward calls of the spectral-norm scale (each sees its own power iteration): a chain of its own."""
         self._d_losses(d.forward(tape, ag.Var(audio, needs_grad=False), role=kind)[0], kind, self._slots[3 if kind == "fake" else 0, i : i + 1])
-
-    def _g_forward(self, tape, d, x: ag.Var, role: str):
-        return d.forward(tape, x, role=role)
 
     def _g_losses(self, i: int, real, fake):
         """Adversarial and feature-matching terms of one discriminator (into slots i) with their gradients."""
@@ -797,28 +855,12 @@ class HiFiGANTrainer(CapturedStep):
                 ev.record(torch.cuda.current_stream(self.device))
                 marks.append((name, ev))
 
-        mark("start")
-        ctx = self._phase_generator_forward(mel_bct, audio_bct, d_step=not warm)
-        mark("generator forward")
-        if not warm:
-            d_red = self._reducer(self.d_params)
-            self._phase_d_backward(ctx, d_red)
-            if d_red is not None:
-                d_red.launch(0, min(self.d_params.offset_of(n) for n in self.d_params.names()))  # alignment padding in front, if any
-                d_red.finish()
-            mark("discriminator step: forward + backward")
-            self._phase_d_update(ctx)
-            mark("discriminator update + weight norm")
-        g_red = self._reducer(self.g_params)
-        ctx["g_reducer"][0] = g_red
-        self._phase_g_backward(ctx, adversarial=not warm)
-        if g_red is not None:
-            g_red.launch(0, min(self.g_params.offset_of(n) for n in self.g_params.names()))
-            g_red.finish()
-        mark("generator step: discriminators + losses + generator backward")
-        self._phase_g_update(ctx)
-        mark("generator update")
-
+        step = _Step()
+        try:
+            mark("start")
+            self._single_gpu_phases(step, mel_bct, audio_bct, warm, mark)
+        finally:
+            step.clear()
         if marks:
             marks[-1][1].synchronize()
             if self.branches.timing:
@@ -828,53 +870,47 @@ class HiFiGANTrainer(CapturedStep):
         return self._loss_buf
 
     # ---- the phases of a step (each one a stretch without communication: what a HIP graph captures) ----
-    def _phase_generator_forward(self, mel_bct, audio_bct, d_step: bool = True):
-        B = audio_bct.shape[0]
+    def _single_gpu_phases(self, step, mel_bct, audio_bct, warm, mark=lambda name: None):
+        """The step on one GPU: what `_eager_step` runs (marking the end of every phase) and what the whole-step graph captures."""
+        self._phase_generator_forward(step, mel_bct, audio_bct, d_step=not warm)
+        mark("generator forward")
+        if not warm:
+            self._phase_d_backward(step)
+            mark("discriminator step: forward + backward")
+            self._phase_d_update(step)
+            mark("discriminator update + weight norm")
+        self._phase_g_backward(step, adversarial=not warm)
+        mark("generator step: discriminators + losses + generator backward")
+        self._phase_g_update(step)
+        mark("generator update")
+
+    def _phase_generator_forward(self, step, mel_bct, audio_bct, d_step: bool = True):
+        B = step.B = audio_bct.shape[0]
         y = audio_bct.to(torch.float32).reshape(1, B, -1)  # [B,1,T] and [1,B,T] are the same bytes
         if not y.is_contiguous():
             y = ops.copy(y.contiguous())
+        step.y = y
         mel = _to_cbt_kernel(mel_bct.to(torch.float32))  # [B, C, T] -> [C, B, T]: layout change only
         ops.fill_(self._loss_buf, 0.0)
         ops.fill_(self._slots, 0.0)
-        g_layers, d_layers = self.generator.layers(), self.d_layers()
+        g_layers, step.d_layers = self.generator.layers(), self.d_layers()
         self._materialize(g_layers)
         # Every step re-derives what it reads from the discriminators' parameters -- effective weights here, the weight-normed chains'
         # fragments beside the generator's forward -- although both stand since the previous step's update: a captured step is then
         # self-contained (parameters written between two replays -- a checkpoint loaded into a live trainer, a lock-step tool -- are
         # picked up by the next replay; round 5's host-side version gate baked "nothing to do" into the graph: ADVICE r05) at 0.04 ms.
-        self._materialize(d_layers)
+        self._materialize(step.d_layers)
         # the discriminator step's weight fragments run UNDER the generator's forward
-        frag_join = self._fragments_beside(y, generator_step=False) if d_step else None
-        g_tape = ag.Tape()
-        g_reducer = [None]  # filled in before the generator's backward (the reducer object is created per phase)
-        y_hat = self.generator.forward(
-            g_tape, ag.Var(mel, needs_grad=False),
-            lambda layers: self._bucket_hook_late(g_tape, self.g_params, layers, g_reducer), branches=self.branches)
-        return dict(B=B, y=y, y_hat=y_hat, g_tape=g_tape, g_reducer=g_reducer, d_layers=d_layers, frag_join=frag_join)
+        step.frag_join = self._fragments_beside(y, generator_step=False) if d_step else None
+        g_tape = step.g_tape = ag.Tape()
+        step.y_hat = self.generator.forward(g_tape, ag.Var(mel, needs_grad=False),
+                                            lambda layers: self._bucket_hook(g_tape, self.g_params, layers, cut=True), branches=self.branches)
 
-    def _bucket_hook_late(self, tape, group, layers, reducer_box):
-        """As `_bucket_hook`, with the reducer looked up when backward runs (the generator's tape is recorded long before it)."""
-        def done():
-            ops.wgrad_join()
-            batches = {}
-            for layer in layers:
-                b = getattr(layer, "_batch", None)
-                if b is None:
-                    layer.finish_grads()
-                else:
-                    batches.setdefault(id(b), (b, []))[1].append(layer)
-            for b, ls in batches.values():
-                b.finish(ls)
-            if reducer_box[0] is not None:
-                reducer_box[0].launch(*self._bucket_range(group, layers))
-        tape.cut(tag=self._bucket_range(group, layers))  # (backward reaches `done` first, then this point)
-        tape.record(done)
-
-    def _phase_d_backward(self, ctx, reducer):
+    def _phase_d_backward(self, step):
         """Discriminator step up to its gradients: the discriminators side by side, the spectral-norm scale's two calls too."""
-        self._phase_d_prelude(ctx)
-        self._phase_d_group(ctx, range(len(self.discriminators())), reducer)
-        self._phase_d_epilogue(ctx)
+        self._phase_d_prelude(step)
+        self._phase_d_group(step, range(len(self.discriminators())))
+        self._phase_d_epilogue(step)
 
     def d_bucket_groups(self):
         """The discriminators as gradient-bucket groups for a captured data-parallel step: [period discriminators] (164 MB of
@@ -882,66 +918,65 @@ class HiFiGANTrainer(CapturedStep):
         n_p = len(self.mpd)
         return [list(range(n_p)), list(range(n_p, n_p + len(self.msd)))]
 
-    def _phase_d_prelude(self, ctx):
-        y, y_hat, B = ctx["y"], ctx["y_hat"], ctx["B"]
+    def _real_and_generated(self, step, tape, needs_grad: bool):
+        """[real | generated] along the batch axis as ONE waveform batch of 2B items (the generated half: y_hat detached) and its
+        pooled pyramid, recorded on `tape` -> one Var per pyramid level."""
+        B, T = step.B, step.y.shape[-1]
+        pair_t = torch.empty(1, 2 * B, T, device=self.device, dtype=torch.float32)
+        ops.copy(step.y, out=pair_t[:, :B])
+        ops.copy(step.y_hat.data, out=pair_t[:, B:])
+        return self._scale_inputs(tape, ag.Var(pair_t, needs_grad=needs_grad))
+
+    def _phase_d_prelude(self, step):
         self.d_params.zero_grad()
-        for layer in ctx["d_layers"]:
+        for layer in step.d_layers:
             layer.frozen = False
         self._prepare_spectral_norm(2)  # real call, then generated call
-        self._prepare_chain_fragments(y, generator_step=False, which="sn")
-        join = ctx.pop("frag_join", None)
-        if join is not None:
-            join()  # (the weight-normed chains' fragments, started beside the generator's forward)
+        self._prepare_chain_fragments(step.y, generator_step=False, which="sn")
+        if step.frag_join is not None:
+            step.frag_join()  # (the weight-normed chains' fragments, started beside the generator's forward)
+            step.frag_join = None
         else:
-            self._prepare_chain_fragments(y, generator_step=False, which="wn")
-        T = y.shape[-1]
-        pair_t = torch.empty(1, 2 * B, T, device=self.device, dtype=torch.float32)
-        ops.copy(y, out=pair_t[:, :B])
-        ops.copy(y_hat.data, out=pair_t[:, B:])  # y_hat.detach()
-        pair = ag.Var(pair_t, needs_grad=False)
-        pairs = [pair]
-        pool_tape = ag.Tape()  # (the pyramid of a gradient-free input: nothing to run backward)
-        for _ in self.msd[1:]:
-            pairs.append(ag.avgpool4s2(pool_tape, pairs[-1]))
-        ctx["d_ins"] = [pair] * len(self.mpd) + pairs
+            self._prepare_chain_fragments(step.y, generator_step=False, which="wn")
+        pairs = self._real_and_generated(step, ag.Tape(), needs_grad=False)  # (a gradient-free input: nothing to run backward)
+        step.d_ins = [pairs[f.scale] for f in self._disc_facts]
 
-    def _phase_d_group(self, ctx, idxs, reducer):
-        """Forward + backward of the discriminators `idxs`, side by side; every one's gradient bucket is finished (and, eagerly,
-        its all-reduce launched) as its stream leaves it."""
-        y, y_hat, ins = ctx["y"], ctx["y_hat"], ctx["d_ins"]
+    def _phase_d_group(self, step, idxs):
+        """Forward + backward of the discriminators `idxs`, side by side; every one's gradient bucket is finished as its stream
+        leaves it."""
+        y, y_hat, ins = step.y, step.y_hat, step.d_ins
         d_tape = ag.Tape()
-        ds = self.discriminators()
         idxs = set(idxs)
-        items = []  # (stream index, fn): every chain keeps the stream it has when all discriminators run together -- the
-        slot = 0    # per-stream workspaces the eager warm-up steps grew are the ones a captured stretch of a subset finds
-        for i, d in enumerate(ds):
-            sn = any(isinstance(layer, SNConv) for layer in d.layers())
-            if i in idxs:
-                if sn:
-                    # its bucket closes on the main stream once both chains' backward has been joined
-                    self._bucket_hook(d_tape, self.d_params, d.layers(), reducer)
-                    items.append((slot, lambda sub, i=i, d=d: self._d_branch_sn(sub, i, d, y, "real")))
-                    items.append((slot + 1, lambda sub, i=i, d=d: self._d_branch_sn(sub, i, d, y_hat.data, "fake")))
-                else:
-                    items.append((slot, lambda sub, i=i, d=d: self._d_branch(sub, i, d, ins[i], reducer)))
-            slot += 2 if sn else 1
+        # (stream index, fn): every chain keeps the stream it has when all discriminators run together -- the per-stream workspaces
+        # the eager warm-up steps grew are the ones a captured stretch of a subset finds
+        items = []
+        for i, (d, f) in enumerate(zip(self.discriminators(), self._disc_facts)):
+            if i not in idxs:
+                continue
+            if f.spectral:
+                # its bucket closes on the main stream once both chains' backward has been joined
+                self._bucket_hook(d_tape, self.d_params, d.layers())
+                items.append((f.slot, lambda sub, i=i, d=d: self._d_branch_sn(sub, i, d, y, "real")))
+                items.append((f.slot + 1, lambda sub, i=i, d=d: self._d_branch_sn(sub, i, d, y_hat.data, "fake")))
+            else:
+                items.append((f.slot, lambda sub, i=i, d=d: self._d_branch(sub, i, d, ins[i])))
         subs = [ag.Tape() for _ in items]
         self.branches.run_indexed([(j, (lambda k=k, fn=fn: fn(subs[k]))) for k, (j, fn) in enumerate(items)])
         d_tape.record(lambda: self.branches.run_indexed([(j, subs[k].backward) for k, (j, _) in enumerate(items)]))
         d_tape.backward()
 
-    def _phase_d_epilogue(self, ctx):
+    def _phase_d_epilogue(self, step):
         for layer in self._sn_layers():
             layer.release()  # every stream has been joined: the prepared spectral-norm tensors may go
         ops.scalar_reduce(2, self._slots[0], None, self._loss_buf[0:1])
         ops.scalar_reduce(2, self._slots[3], None, self._loss_buf[0:1], accumulate=True)
-        ctx.pop("d_ins", None)
+        step.d_ins = None
         if self.keep_grads:
             self.last_grads["d"] = {k: v.clone() for k, v in self.d_params.gradients().items()}
 
-    def _phase_d_update(self, ctx):
+    def _phase_d_update(self, step):
         self.d_params.optimizer_step(clip=self.wgan_clip_value if self.gan_type == "wgan" else 0.0, **self._opt_kw())
-        self._materialize(ctx["d_layers"])  # the generator step sees the updated discriminators
+        self._materialize(step.d_layers)  # the generator step sees the updated discriminators
 
     def _recon_grad(self, y, y_hat_t, B):
         """Reconstruction losses (45 x mel-L1 and / or the multi-resolution STFT loss) and their gradient wrt y_hat [1, B, T]."""
@@ -953,129 +988,94 @@ class HiFiGANTrainer(CapturedStep):
             total = d_stft if total is None else ops.axpby(1.0, total, 1.0, d_stft, out=total)
         return total
 
-    def _phase_g_backward(self, ctx, adversarial=True):
-        y, y_hat, B = ctx["y"], ctx["y_hat"], ctx["B"]
+    def _phase_g_backward(self, step, adversarial=True):
+        y_hat = step.y_hat
         self.g_params.zero_grad()
-        for layer in ctx["d_layers"]:
+        for layer in step.d_layers:
             layer.frozen = True  # gradients flow through the discriminators to y_hat only
         y_hat_in = ag.Var(y_hat.data)  # boundary between the discriminator tape and the generator tape
-        recon = [None]
-        if adversarial:
-            frag_join = self._fragments_beside(y, generator_step=True)  # (under the spectral-norm power iterations)
-            self._prepare_spectral_norm(2)  # real call, then generated call
-            self._prepare_chain_fragments(y, generator_step=True, which="sn")
-            frag_join()
-            gd_tape = ag.Tape()
-            real = ag.Var(y, needs_grad=False)
-            ds = self.discriminators()
-            nd = len(ds)
-            n_p = len(self.mpd)
-            is_sn = [any(isinstance(l, SNConv) for l in d.layers()) for d in ds]
-            # Packed chains (precision "bf16"): every weight-normed discriminator sees [real | generated] as ONE batch -- forward once
-            # over 2B waveforms (half the launches of two B-waveform passes, each better filled), backward over the generated half,
-            # feature matching between the two halves of the same tensors.  The spectral-norm scale keeps its two calls (each call
-            # runs its own power iteration: two different effective weights).
-            pair_mode = all(sn or _chain_for(d, getattr(d, "period", 1), y) is not None for d, sn in zip(ds, is_sn)) and not all(is_sn)
-            res_r, res_f = [None] * nd, [None] * nd
-            pair_in = None
-            if pair_mode:
-                T = y.shape[-1]
-                pair_t = torch.empty(1, 2 * B, T, device=self.device, dtype=torch.float32)
-                ops.copy(y, out=pair_t[:, :B])
-                ops.copy(y_hat.data, out=pair_t[:, B:])
-                pair_in = ag.Var(pair_t)
-                xs_p = self._scale_inputs(gd_tape, pair_in)
-                sn_pooled = any(is_sn[i] and i > n_p for i in range(nd))  # (a spectral-norm scale behind the pooling: not in the upstream model)
-                xs_r = self._scale_inputs(gd_tape, real) if sn_pooled else [real]
-                xs_f = self._scale_inputs(gd_tape, y_hat_in) if sn_pooled else [y_hat_in]
-                n_wave = sum(1 for i in range(nd) if not is_sn[i] and i <= n_p)  # chains reading the waveform itself: the periods (+ scale 0 when weight-normed)
-                p_leaves = fan_out(gd_tape, pair_in, n_wave)
-                f_leaves = fan_out(gd_tape, y_hat_in, sum(1 for i in range(nd) if is_sn[i] and i <= n_p))
-                ins_p, ins_r, ins_f = [None] * nd, [None] * nd, [None] * nd
-                pi = fi = 0
-                for i in range(nd):
-                    scale = max(0, i - n_p)
-                    if is_sn[i]:
-                        ins_r[i] = xs_r[scale]
-                        if scale == 0:
-                            ins_f[i] = f_leaves[fi]
-                            fi += 1
-                        else:
-                            ins_f[i] = fan_out(gd_tape, xs_f[scale], 1)[0]
-                    elif scale == 0:
-                        ins_p[i] = p_leaves[pi]
-                        pi += 1
-                    else:
-                        ins_p[i] = fan_out(gd_tape, xs_p[scale], 1)[0]
-
-                def fwd_pair(i):
-                    return lambda sub: res_f.__setitem__(i, ds[i].forward(sub, ins_p[i], role="g_both", grad_from=B))
-
-                def fwd_real(i):
-                    return lambda sub: res_r.__setitem__(i, self._g_forward(sub, ds[i], ins_r[i], "g_real"))
-
-                def fwd_fake(i):
-                    return lambda sub: res_f.__setitem__(i, self._g_forward(sub, ds[i], ins_f[i], "g_fake"))
-
-                sn_idx = [i for i in range(nd) if is_sn[i]]
-                order_a = [fwd_fake(i) if is_sn[i] else fwd_pair(i) for i in range(nd)]
-                order_b = [fwd_real(i) for i in sn_idx]
-                # host order decides which prepared spectral-norm call a chain receives: issue the real chains of those scales first
-                self._ordered_section(gd_tape, order_a, order_b + [lambda sub: recon.__setitem__(0, self._recon_grad(y, y_hat.data, B))],
-                                      first=[nd + j for j in range(len(sn_idx))])
-            else:
-                xs_r = self._scale_inputs(gd_tape, real)
-                xs_f = self._scale_inputs(gd_tape, y_hat_in)
-                fake_leaves = fan_out(gd_tape, y_hat_in, n_p + 1)
-                ins_r = [real] * (n_p + 1) + xs_r[1:]
-                ins_f = [*fake_leaves[:n_p], fake_leaves[-1], *[fan_out(gd_tape, x, 1)[0] for x in xs_f[1:]]]
-                # generated-waveform chains on streams 0 .. nd-1 (their backward too), real-waveform chains (forward only) and the
-                # reconstruction loss on the streams after them; the spectral-norm scale hands out its real call first
-
-                def fwd_real(i):
-                    return lambda sub: res_r.__setitem__(i, self._g_forward(sub, ds[i], ins_r[i], "g_real"))
-
-                def fwd_fake(i):
-                    return lambda sub: res_f.__setitem__(i, self._g_forward(sub, ds[i], ins_f[i], "g_fake"))
-
-                sn_first = [i for i in range(nd) if is_sn[i]]
-                order_fake = [fwd_fake(i) for i in range(nd)]
-                order_real = [fwd_real(i) for i in range(nd)]
-                # host order decides which prepared spectral-norm call a chain receives: issue the real chains of those scales first
-                self._ordered_section(gd_tape, order_fake, order_real + [lambda sub: recon.__setitem__(0, self._recon_grad(y, y_hat.data, B))], first=[nd + i for i in sn_first])
-            self.branches.run([(lambda i=i: self._g_losses(i, res_r[i], res_f[i])) for i in range(nd)])
-            gd_tape.backward()
-            if pair_in is not None and pair_in.grad is not None:  # the generated half of the batched chains' waveform gradient
-                y_hat_in.accumulate(ops.copy(pair_in.grad[:, B:].contiguous()))
-            ops.scalar_reduce(2, self._slots[1], None, self._loss_buf[1:2])
-            ops.scalar_reduce(2, self._slots[2], None, self._loss_buf[2:3])
-            for layer in ctx["d_layers"]:
-                if isinstance(layer, SNConv):
-                    layer._calls.clear()  # frozen: no parameter gradients from this pass
-                    layer.release()
-            total = recon[0]
-        else:
-            total = self._recon_grad(y, y_hat.data, B)
+        # (`_held`: the pass's inputs and feature maps stay allocated through the generator's backward, as they always have -- freed
+        # here, the backward's temporaries would reuse their blocks: other addresses in a captured graph's pool)
+        total, _held = self._g_step_discriminators(step, y_hat_in) if adversarial else (self._recon_grad(step.y, y_hat.data, step.B), None)
         if y_hat_in.grad is not None:
             total = ops.axpby(1.0, total, 1.0, y_hat_in.grad, out=total)
         y_hat.grad = total
-        if ctx.get("g_segmented"):  # captured data-parallel step: the generator's backward is run bucket by bucket by the caller
-            ctx["g_segments"] = ctx["g_tape"].backward_segments(ctx.get("g_stop"))
+        if step.g_segmented:  # captured data-parallel step: the generator's backward is run bucket by bucket by the caller
+            step.g_segments = step.g_tape.backward_segments(step.g_stop)
             return
-        ctx["g_tape"].backward()  # buckets: conv_post, the upsampling stages, conv_pre
+        step.g_tape.backward()  # buckets: conv_post, the upsampling stages, conv_pre
         if self.keep_grads:
             self.last_grads["g"] = {k: v.clone() for k, v in self.g_params.gradients().items()}
             self.last_grads["y_hat"] = y_hat.data.clone()
 
-    def _ordered_section(self, tape, fns_a, fns_b, first=()):
-        """A parallel section over fns_a + fns_b (branch j on stream j) whose HOST issue order starts with the indices in `first`."""
-        fns = list(fns_a) + list(fns_b)
+    def _pair_mode(self, probe: torch.Tensor) -> bool:
+        """Packed chains (precision "bf16"): every weight-normed discriminator sees [real | generated] as ONE batch -- forward once
+        over 2B waveforms (half the launches of two B-waveform passes, each better filled), backward over the generated half,
+        feature matching between the two halves of the same tensors.  The spectral-norm scale keeps its two calls."""
+        facts = self._disc_facts
+        return (all(f.spectral or _chain_for(d, getattr(d, "period", 1), probe) is not None for d, f in zip(self.discriminators(), facts))
+                and not all(f.spectral for f in facts))
+
+    def _g_step_inputs(self, step, tape, chains, y_hat_in: ag.Var):
+        """The input Var of every chain of ``g_step_routing`` (by branch) and the [real | generated] Var (None without one).  What is
+        recorded on `tape` here fixes the summation order of the waveform gradient: the pyramids (pair, real, generated), one
+        fan-out group per input for the chains that read the waveform itself (pair, generated), then one fan-out per pooled chain
+        in branch order."""
+        built = routing_pyramids(chains)
+        pyr = {"pair": self._real_and_generated(step, tape, needs_grad=True)} if "pair" in built else {}
+        for kind, var in (("real", ag.Var(step.y, needs_grad=False)), ("fake", y_hat_in)):
+            pyr[kind] = self._scale_inputs(tape, var) if kind in built else [var]
+        wave = {kind: iter(fan_out(tape, pyr[kind][0], sum(c.kind == kind and c.level == 0 for c in chains)))
+                for kind in ("pair", "fake") if kind in pyr}
+        ins = []
+        for c in chains:
+            if c.kind in (None, "real"):  # no gradient: every real chain reads the same Var
+                ins.append(None if c.kind is None else pyr["real"][c.level])
+            else:
+                ins.append(next(wave[c.kind]) if c.level == 0 else fan_out(tape, pyr[c.kind][c.level], 1)[0])
+        return ins, pyr["pair"][0] if "pair" in pyr else None
+
+    def _g_step_discriminators(self, step, y_hat_in: ag.Var):
+        """The generator step's pass through the (frozen) discriminators: the chains of ``g_step_routing`` and the reconstruction loss
+        side by side, the adversarial and feature-matching losses, backward down to the waveform (into ``y_hat_in.grad``).  Returns
+        the reconstruction losses' gradient and the tensors of the pass (for the caller to keep or drop)."""
+        y, B = step.y, step.B
+        frag_join = self._fragments_beside(y, generator_step=True)  # (under the spectral-norm power iterations)
+        self._prepare_spectral_norm(2)  # real call, then generated call
+        self._prepare_chain_fragments(y, generator_step=True, which="sn")
+        frag_join()
+        gd_tape = ag.Tape()
+        ds = self.discriminators()
+        chains = g_step_routing(self._disc_facts, self._pair_mode(y))
+        ins, pair_in = self._g_step_inputs(step, gd_tape, chains, y_hat_in)
+        res_r, res_f, recon = [None] * len(ds), [None] * len(ds), [None]
+
+        def run(c):
+            if c.role == "recon":
+                return lambda sub: recon.__setitem__(0, self._recon_grad(y, step.y_hat.data, B))
+            out = res_r if c.role == "g_real" else res_f
+            grad_from = B if c.role == "g_both" else None
+            return lambda sub: out.__setitem__(c.disc, ds[c.disc].forward(sub, ins[c.branch], role=c.role, grad_from=grad_from))
+
+        self._ordered_section(gd_tape, [run(c) for c in chains], sorted(range(len(chains)), key=lambda j: chains[j].order))
+        self.branches.run([(lambda i=i: self._g_losses(i, res_r[i], res_f[i])) for i in range(len(ds))])
+        gd_tape.backward()
+        if pair_in is not None and pair_in.grad is not None:  # the generated half of the batched chains' waveform gradient
+            y_hat_in.accumulate(ops.copy(pair_in.grad[:, B:].contiguous()))
+        ops.scalar_reduce(2, self._slots[1], None, self._loss_buf[1:2])
+        ops.scalar_reduce(2, self._slots[2], None, self._loss_buf[2:3])
+        for layer in self._sn_layers():
+            layer._calls.clear()  # frozen: no parameter gradients from this pass
+            layer.release()
+        return recon[0], (res_r, res_f, ins, pair_in)
+
+    def _ordered_section(self, tape, fns, order):
+        """A parallel section over fns (branch j on stream j, its backward too) whose forward is issued by the HOST in `order`."""
         subs = [ag.Tape() for _ in fns]
-        order = list(first) + [j for j in range(len(fns)) if j not in first]
         self.branches.run_indexed([(j, (lambda j=j: fns[j](subs[j]))) for j in order])
         tape.record(lambda: self.branches.run_indexed([(j, subs[j].backward) for j in range(len(fns))]))
 
-    def _phase_g_update(self, ctx):
+    def _phase_g_update(self, step):
         self.g_params.optimizer_step(**self._opt_kw())
 
     # ---- HIP-graph execution of the step ----------------------------------------------------------------------------
@@ -1126,26 +1126,17 @@ class HiFiGANTrainer(CapturedStep):
             raise RuntimeError("capture failure forced by a test")
         mel_s = mel_bct.to(torch.float32).contiguous().clone()
         audio_s = audio_bct.to(torch.float32).contiguous().clone()
-        ctx = {}
-
-        def whole():
-            ctx.update(self._phase_generator_forward(mel_s, audio_s, d_step=not warm))
-            if not warm:
-                self._phase_d_backward(ctx, None)
-                self._phase_d_update(ctx)
-            self._phase_g_backward(ctx, adversarial=not warm)
-            self._phase_g_update(ctx)
-
+        step = _Step()
         try:
             if self.pg is None:
-                cap(whole)
+                cap(lambda: self._single_gpu_phases(step, mel_s, audio_s, warm))
             else:
-                self._capture_data_parallel(cap, ctx, mel_s, audio_s, warm)
+                self._capture_data_parallel(cap, step, mel_s, audio_s, warm)
         finally:
-            ctx.clear()
+            step.clear()  # (a captured graph's pool must not be kept alive by a Python reference)
         return dict(mel=mel_s, audio=audio_s, warm=warm)
 
-    def _capture_data_parallel(self, cap_raw, ctx, mel_s, audio_s, warm):
+    def _capture_data_parallel(self, cap_raw, step, mel_s, audio_s, warm):
         """The data-parallel schedule with every stretch captured and every exchange stored for the replay loop."""
         thens = []
 
@@ -1156,21 +1147,21 @@ class HiFiGANTrainer(CapturedStep):
         def emit(then):
             thens[-1] = then
 
-        self._data_parallel_schedule(run, emit, ctx, mel_s, audio_s, warm)
+        self._data_parallel_schedule(run, emit, step, mel_s, audio_s, warm)
 
     def _eager_data_parallel_step(self, mel_bct, audio_bct, warm):
         """The data-parallel schedule executed eagerly: the SAME stretches and the SAME exchanges between them as the captured step
         (`_capture_data_parallel`), so a rank that runs eagerly -- a shape not captured yet, a capture that failed on this rank only --
         issues exactly the collective sequence of a rank that replays (the reference: every rank runs the same DDP bucket sequence,
         everyvoice/base_cli/interfaces.py:90-97 -> base_cli/helpers.py:252-270).  No agreement between ranks is needed any more."""
-        ctx = {}
+        step = _Step()
         try:
-            self._data_parallel_schedule(lambda fn: fn(), lambda then: then(), ctx, mel_bct, audio_bct, warm)
+            self._data_parallel_schedule(lambda fn: fn(), lambda then: then(), step, mel_bct, audio_bct, warm)
         finally:
-            ctx.clear()
+            step.clear()
         return self._loss_buf
 
-    def _data_parallel_schedule(self, run, emit, ctx, mel_s, audio_s, warm):
+    def _data_parallel_schedule(self, run, emit, step, mel_s, audio_s, warm):
         """``run(fn)``: execute (or capture) one stretch; ``emit(then)``: the exchange that follows it (called at once, or stored)."""
         if getattr(self, "_dp_reducers", None) is None:
             pg = self.pg if self.pg is not True else None
@@ -1178,9 +1169,9 @@ class HiFiGANTrainer(CapturedStep):
         d_red, g_red = self._dp_reducers
 
         def first():
-            ctx.update(self._phase_generator_forward(mel_s, audio_s, d_step=not warm))
+            self._phase_generator_forward(step, mel_s, audio_s, d_step=not warm)
             if not warm:
-                self._phase_d_prelude(ctx)
+                self._phase_d_prelude(step)
 
         if warm:
             run(first)
@@ -1195,9 +1186,9 @@ class HiFiGANTrainer(CapturedStep):
                 def stretch(gi=gi, idxs=idxs, last=last):
                     if gi == 0:
                         first()
-                    self._phase_d_group(ctx, idxs, None)
+                    self._phase_d_group(step, idxs)
                     if last:
-                        self._phase_d_epilogue(ctx)
+                        self._phase_d_epilogue(step)
 
                 run(stretch)
                 if last:  # the discriminators' optimiser comes next: wait for every bucket, scale by 1 / world
@@ -1206,7 +1197,7 @@ class HiFiGANTrainer(CapturedStep):
                     emit(lambda lo=lo, hi=hi: d_red.launch(lo, hi))
         # generator step: the first stretch runs the discriminators' update, the generator-step discriminator pass, the losses
         # and the generator's backward down to the first bucket boundary worth a cut; then one stretch per further bucket
-        ctx["g_segmented"] = True
+        step.g_segmented = True
         pending = [0]
 
         def stop(tag):  # small buckets (conv_post, the narrow late stages) ride with the next one
@@ -1216,19 +1207,19 @@ class HiFiGANTrainer(CapturedStep):
                 return True
             return False
 
-        ctx["g_stop"] = stop
+        step.g_stop = stop
         state = {"cut": None, "done": False}
 
         def advance():
             try:
-                state["cut"] = next(ctx["g_segments"])[0]  # gradients from here to the previous cut are final
+                state["cut"] = next(step.g_segments)[0]  # gradients from here to the previous cut are final
             except StopIteration:
                 state["cut"], state["done"] = 0, True
 
         def g_first():
             if not warm:
-                self._phase_d_update(ctx)
-            self._phase_g_backward(ctx, adversarial=not warm)
+                self._phase_d_update(step)
+            self._phase_g_backward(step, adversarial=not warm)
             advance()
 
         hi = self.g_params.grad.numel()
@@ -1244,8 +1235,8 @@ class HiFiGANTrainer(CapturedStep):
         def g_last():
             if self.keep_grads:  # (tests; never while capturing: keep_grads keeps a step eager)
                 self.last_grads["g"] = {k: v.clone() for k, v in self.g_params.gradients().items()}
-                self.last_grads["y_hat"] = ctx["y_hat"].data.clone()
-            self._phase_g_update(ctx)
+                self.last_grads["y_hat"] = step.y_hat.data.clone()
+            self._phase_g_update(step)
 
         run(g_last)
 

@@ -142,35 +142,33 @@ class _ScheduleHost:
     def _bucket_range(group, layers):
         return 10 * min(layers) + 2, 10 * max(layers) + 12
 
-    def _phase_generator_forward(self, mel, audio, d_step=True):
+    def _phase_generator_forward(self, step, mel, audio, d_step=True):
         self.log.append(("phase", "generator forward"))
-        return {}
 
-    def _phase_d_prelude(self, ctx):
+    def _phase_d_prelude(self, step):
         self.log.append(("phase", "d prelude"))
 
-    def _phase_d_group(self, ctx, idxs, reducer):
-        assert reducer is None
+    def _phase_d_group(self, step, idxs):
         self.log.append(("phase", "d group", tuple(idxs)))
 
-    def _phase_d_epilogue(self, ctx):
+    def _phase_d_epilogue(self, step):
         self.log.append(("phase", "d epilogue"))
 
-    def _phase_d_update(self, ctx):
+    def _phase_d_update(self, step):
         self.log.append(("phase", "d update"))
 
-    def _phase_g_backward(self, ctx, adversarial=True):
+    def _phase_g_backward(self, step, adversarial=True):
         self.log.append(("phase", "g backward"))
-        stop = ctx["g_stop"]
+        stop = step.g_stop
 
         def segments():  # gradient ranges becoming final from the end of the buffer downwards; the schedule cuts where `stop` says so
             for lo, hi in ((17, 20), (14, 17), (8, 14), (6, 8), (3, 6)):
                 if stop((lo, hi)):
                     yield (lo, hi)
 
-        ctx["g_segments"] = segments()
+        step.g_segments = segments()
 
-    def _phase_g_update(self, ctx):
+    def _phase_g_update(self, step):
         self.log.append(("phase", "g update"))
 
 
@@ -179,15 +177,15 @@ def test_eager_and_captured_data_parallel_steps_issue_the_same_collectives():
     eager step calls every stretch and every exchange at once, the capture stores the exchanges and the replay loop calls them between
     the graphs -- so a rank that runs eagerly (new shape, failed capture) pairs its all-reduces with a replaying rank's one for one
     (the reference: every rank, the same DDP buckets: everyvoice/base_cli/helpers.py:252-270).  Host logic only: phases are stubs."""
-    from everyvoice_amd.train.hifigan import HiFiGANTrainer
+    from everyvoice_amd.train.hifigan import HiFiGANTrainer, _Step
 
     for warm in (False, True):
         eager_log, cap_log = [], []
         host = _ScheduleHost(eager_log)
-        HiFiGANTrainer._data_parallel_schedule(host, lambda fn: fn(), lambda then: then(), {}, None, None, warm)
+        HiFiGANTrainer._data_parallel_schedule(host, lambda fn: fn(), lambda then: then(), _Step(), None, None, warm)
         host = _ScheduleHost(cap_log)
         stored = []
-        HiFiGANTrainer._data_parallel_schedule(host, lambda fn: (fn(), stored.append(None)), lambda then: stored.__setitem__(-1, then), {}, None, None, warm)
+        HiFiGANTrainer._data_parallel_schedule(host, lambda fn: (fn(), stored.append(None)), lambda then: stored.__setitem__(-1, then), _Step(), None, None, warm)
         n_capture_time = len(cap_log)
         assert not [e for e in cap_log if e[0] != "phase"], "a capture must not issue collectives"
         for then in stored:  # the replay loop: graph i, then its exchange

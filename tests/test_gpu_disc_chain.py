@@ -36,7 +36,7 @@ def _run_d_step(tr, d, audio, dl_seed, chain):
                 layer.frozen = False
             tr._materialize(d.layers())
             tape = ag.Tape()
-            tr._bucket_hook(tape, tr.d_params, d.layers(), None)
+            tr._bucket_hook(tape, tr.d_params, d.layers())
             out, fm = d.forward(tape, ag.Var(audio, needs_grad=False))
             g = torch.Generator(device="cpu").manual_seed(dl_seed)
             out.grad = (torch.randn(out.data.shape, generator=g) / out.data.numel()).to(audio.device)
