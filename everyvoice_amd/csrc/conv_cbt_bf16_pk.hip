@@ -885,6 +885,83 @@ __global__ __launch_bounds__(256) void layernorm_pack_kernel(const float* __rest
   }
 }
 
+// The same at 256 < C <= 1024, C a multiple of 32 (a thread's slice of C / 4 channels is still whole octets): the slice length is a
+// run-time value under the register array's CPT, as in layernorm_cbt_kernel<256>, whose arithmetic and order these are -- the packed
+// tensor is the pack of that kernel's output.
+template <int CPT>  // C / 4 <= CPT
+__global__ __launch_bounds__(256) void layernorm_pack_wide_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, uint4* __restrict__ xp, int C, long long N,
+                                                                 long long plane, float eps, int slack_units, unsigned n_ln, WfragArgs f1,
+                                                                 WfragArgs f2) {
+  if (blockIdx.x >= n_ln) {  // (the weight-fragment workgroups of layernorm_pack_kernel)
+    unsigned b = blockIdx.x - n_ln;
+    const unsigned n1 = (unsigned)f1.gx * f1.gy * f1.gz;
+    const WfragArgs& f = b < n1 ? f1 : f2;
+    if (b >= n1) b -= n1;
+    const unsigned q = b % f.gx, r = b / f.gx;
+    wfrag_pk_block(f, (int)q, (int)(r % f.gy), (int)(r / f.gy));
+    return;
+  }
+  __shared__ float red[2][4][64];
+  const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
+  const long long n = (long long)blockIdx.x * 64 + lane;
+  const bool live = n < N;
+  if (blockIdx.x == 0) {
+    uint4* tail = xp + (long long)(C / 8) * plane;
+    for (int i = threadIdx.x; i < slack_units; i += 256) tail[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  const int per = C >> 2, c0 = slice * per;
+  // (whole octets under one uniform test each, every load unconditional: a lane past column N - 1 reads that column and writes nothing)
+  const float* xc = x + (long long)c0 * N + (live ? n : N - 1);
+  float v[CPT];
+  float s = 0.f;
+#pragma unroll
+  for (int o = 0; o < CPT / 8; ++o) {
+    const bool on = 8 * o < per;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[8 * o + e] = on ? xc[(long long)(8 * o + e) * N] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) s += v[i];
+  red[0][slice][lane] = s;
+  __syncthreads();
+  const float mean = (red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane]) / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) {
+    const float d = i < per ? v[i] - mean : 0.f;
+    q = fmaf(d, d, q);
+  }
+  red[1][slice][lane] = q;
+  __syncthreads();
+  const float var = (red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane]) / (float)C;
+  const float rstd = 1.f / sqrtf(var + eps);
+  if (!live) {
+    if (n < plane) {
+#pragma unroll
+      for (int o = 0; o < CPT / 8; ++o)
+        if (8 * o < per) xp[(long long)(c0 / 8 + o) * plane + n] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    return;
+  }
+#pragma unroll
+  for (int o = 0; o < CPT / 8; ++o) {
+    if (8 * o >= per) break;
+    float r[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = c0 + 8 * o + e;
+      r[e] = (v[8 * o + e] - mean) * rstd * gamma[c] + beta[c];
+    }
+    uint4 out;
+    out.x = pk_bf16x2(r[0], r[1]);
+    out.y = pk_bf16x2(r[2], r[3]);
+    out.z = pk_bf16x2(r[4], r[5]);
+    out.w = pk_bf16x2(r[6], r[7]);
+    xp[(long long)(c0 / 8 + o) * plane + n] = out;
+  }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 struct PkTile { int bm, bn; };
 // (index 7, 8: eight-wave forms of 128 x 256 and 128 x 128 -- 64 x 64 / 64 x 32 per wave)
@@ -1438,7 +1515,7 @@ int evmi_conv1d_cbt_bf16pk(const float* x_dev, const float* w_dev, const float* 
 }
 
 /* LayerNorm in front of a pointwise layer, written as that layer's packed input (the layers of evmi_conv1d_bf16pk_shares_packed: tight
- * items, B * t a multiple of 64; c_in 128 or 256), and the layer itself on an input that is already packed in the head of ws:
+ * items, B * t a multiple of 64; c_in 128 or 256, or a multiple of 32 above 256 up to 1024), and the layer itself on an input that is already packed in the head of ws:
  *   evmi_layernorm_pack_bf16pk(x, gamma, beta, ws, ...)   ws head <- packed bf16 LayerNorm(x) (+ the zero slack the kernels read past it)
  *   evmi_conv1d_cbt_bf16pk_prepacked(w, bias, y, ws, ...) y = act(conv(that) + bias); ws as evmi_conv1d_cbt_bf16pk's, same geometry
  * The normalised tensor is never stored in fp32; the head of ws is what the layer's weight gradient reads again (..._wgrad_..._prepacked). */
@@ -1446,7 +1523,8 @@ static int layernorm_pack_impl(const float* x_dev, const float* gamma_dev, const
                                int c_out, float eps, const float* w_dev, const float* w2_dev, float* ws2_dev, long long ws2_elems, int c_out2,
                                void* stream) {
   if (!x_dev || !gamma_dev || !beta_dev || !ws_dev) return fail(EVMI_ERR_INVALID_ARG, "layernorm_pack_bf16pk: null pointer");
-  if (c_in != 128 && c_in != 256) return fail(EVMI_ERR_UNSUPPORTED, "layernorm_pack_bf16pk: 128 or 256 channels");
+  if (c_in != 128 && c_in != 256 && !(c_in > 256 && c_in <= 1024 && c_in % 32 == 0))
+    return fail(EVMI_ERR_UNSUPPORTED, "layernorm_pack_bf16pk: 128 or 256 channels, or a multiple of 32 above 256 up to 1024");
   if (!pk_shared_items(B, t_in)) return fail(EVMI_ERR_UNSUPPORTED, "layernorm_pack_bf16pk: B * t must be a multiple of 64 (or one item)");
   ConvPkArgs a = {};
   PkPlan pl;
@@ -1474,7 +1552,9 @@ static int layernorm_pack_impl(const float* x_dev, const float* gamma_dev, const
   const long long n_blk = (long long)n_ln + (long long)f1.gx * f1.gy * f1.gz + (long long)f2.gx * f2.gy * f2.gz;
   if (n_blk > 0x7fffffffLL) return fail(EVMI_ERR_UNSUPPORTED, "layernorm_pack_bf16pk: grid limits");
   const dim3 grid((unsigned)n_blk);
-  if (c_in == 256) hipLaunchKernelGGL(layernorm_pack_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, x_dev, gamma_dev, beta_dev, xp, c_in, N, plane, eps, slack, n_ln, f1, f2);
+  if (c_in > 512) hipLaunchKernelGGL(layernorm_pack_wide_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, x_dev, gamma_dev, beta_dev, xp, c_in, N, plane, eps, slack, n_ln, f1, f2);
+  else if (c_in > 256) hipLaunchKernelGGL(layernorm_pack_wide_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, x_dev, gamma_dev, beta_dev, xp, c_in, N, plane, eps, slack, n_ln, f1, f2);
+  else if (c_in == 256) hipLaunchKernelGGL(layernorm_pack_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, x_dev, gamma_dev, beta_dev, xp, c_in, N, plane, eps, slack, n_ln, f1, f2);
   else hipLaunchKernelGGL(layernorm_pack_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, x_dev, gamma_dev, beta_dev, xp, c_in, N, plane, eps, slack, n_ln, f1, f2);
   EVMI_LAUNCH_CHECK("layernorm_pack");
   return EVMI_OK;

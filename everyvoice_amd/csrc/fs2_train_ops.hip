@@ -128,6 +128,143 @@ __global__ __launch_bounds__(64 * SL) void layernorm_bwd_cbt_kernel(const float*
   }
 }
 
+// 512 < C <= 1024: sixteen slices of up to 64 channels.  A 1024-thread workgroup leaves every wave 128 registers, and x and dy of a
+// slice would fill them, so only x stays in registers (it is needed three times: mean, variance, xhat) and dy is read TWICE: once for
+// the partial sums and the two column means, once more where dx is written (4/3 of the single-pass traffic; the second read of a
+// workgroup's 64 x C tile comes from the L2 more often than not).  Same partial sums, same order of every sum as the kernel above.
+// Every load is unconditional on a clamped address (rows past the slice repeat its last row, lanes past column N - 1 repeat that
+// column) and the value is dropped afterwards: 64 predicated loads are 64 branches and 64 lane masks kept in scalar registers.
+// (row offsets WALK, one 64-bit add per row behind an empty asm: written as base + i * N the compiler keeps all 64 row offsets of the
+// four passes in scalar registers, spills them into vector lanes and those into scratch)
+__device__ __forceinline__ void ln_walk(long long& off, long long step) {
+  off += step;
+  asm volatile("" : "+v"(off));
+}
+// (and every pass compares against a copy of the slice's last row index of its own: shared, the 64 compare results of one pass are kept
+// for the next ones, in scalar registers again)
+__device__ __forceinline__ int ln_fresh(int v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
+template <int CPT, int SL>
+__global__ __launch_bounds__(64 * SL) void layernorm_bwd_cbt_wide_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ dy, float* __restrict__ dx,
+                                                                     float* __restrict__ part, int C, long long N, float eps,
+                                                                     int accumulate) {
+  constexpr int EB = 8, SB = 4;
+  static_assert(CPT % EB == 0, "batches of eight rows");
+  __shared__ float red[4][SL][64];
+  // (the slice as a scalar: `row is in my slice` is then a scalar compare)
+  const int lane = threadIdx.x & 63, slice = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long n = (long long)blockIdx.x * 64 + lane;
+  const bool live = n < N;
+  const int per = (C + SL - 1) / SL, c0 = slice * per, c1 = min(C, c0 + per), last = c1 - c0 - 1;  // (C > 15 * 15: no slice is empty)
+  const long long col = (long long)c0 * N + (live ? n : N - 1);
+  const float keep = live ? 1.f : 0.f;
+  float v[CPT];
+  float s = 0.f;
+  {
+    const int la = ln_fresh(last);
+    long long off = col;
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const float t = x[off];
+      v[i] = i <= la ? t : 0.f;
+      ln_walk(off, i < la ? N : 0);
+      s += v[i];
+    }
+  }
+  red[0][slice][lane] = s;
+  __syncthreads();
+  float mean = 0.f;
+#pragma unroll
+  for (int q = 0; q < SL; ++q) mean += red[0][q][lane];
+  mean /= (float)C;
+  float qs = 0.f;
+  {
+    const int lb = ln_fresh(last);
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      v[i] = i <= lb ? v[i] - mean : 0.f;  // (centred in place: zero past the slice from here on)
+      qs = fmaf(v[i], v[i], qs);
+    }
+  }
+  red[1][slice][lane] = qs;
+  __syncthreads();
+  float var = 0.f;
+#pragma unroll
+  for (int q = 0; q < SL; ++q) var += red[1][q][lane];
+  const float rstd = 1.f / sqrtf(var / (float)C + eps);
+  float s1 = 0.f, s2 = 0.f;
+  {
+    float* pg = part + (long long)blockIdx.x * 2 * C;
+    const int lc = ln_fresh(last);
+    long long off = col;
+    // batches of four rows, fenced: left to itself the scheduler requests all 64 rows of dy (and gamma) at once and spills
+#pragma unroll
+    for (int i0 = 0; i0 < CPT; i0 += SB) {
+      float d[SB];
+#pragma unroll
+      for (int e = 0; e < SB; ++e) {
+        d[e] = dy[off] * (i0 + e <= lc ? keep : 0.f);  // (a dead lane or a repeated row adds nothing to any sum)
+        ln_walk(off, i0 + e < lc ? N : 0);
+      }
+      float pa = 0.f, pb = 0.f;  // lane e: the two column sums of row i0 + e (one store per batch, no branch per row)
+#pragma unroll
+      for (int e = 0; e < SB; ++e) {
+        const int i = i0 + e;
+        v[i] *= rstd;  // xhat
+        const float a = wave_sum(d[e] * v[i]), b = wave_sum(d[e]);
+        pa = lane == e ? a : pa;
+        pb = lane == e ? b : pb;
+        const float g = d[e] * gamma[c0 + min(i, lc)];  // dy * gamma
+        s1 += g;
+        s2 = fmaf(g, v[i], s2);
+      }
+      if (lane < SB && i0 + lane <= lc) {
+        pg[c0 + i0 + lane] = pa;
+        pg[C + c0 + i0 + lane] = pb;
+      }
+      asm volatile("" : "+v"(s1), "+v"(s2));  // (the two running sums are DUE here: their adds otherwise sink to the end of the pass, all 64 dy * gamma live until then)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  red[2][slice][lane] = s1;
+  red[3][slice][lane] = s2;
+  __syncthreads();
+  float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+  for (int q = 0; q < SL; ++q) {
+    m1 += red[2][q][lane];
+    m2 += red[3][q][lane];
+  }
+  m1 /= (float)C;
+  m2 /= (float)C;
+  if (!live) return;
+  const int ld = ln_fresh(last);
+  long long off = col, to = col;
+  // loads in front of stores, eight rows at a time (see the accumulate branch above)
+#pragma unroll
+  for (int i0 = 0; i0 < CPT; i0 += EB) {
+    if (i0 > ld) break;  // (scalar)
+    float d[EB], old[EB];
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+      d[e] = dy[off];
+      old[e] = accumulate ? dx[off] : 0.f;
+      ln_walk(off, i0 + e < ld ? N : 0);
+    }
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+      const int i = i0 + e;
+      if (i <= ld) dx[to] = old[e] + rstd * (d[e] * gamma[c0 + min(i, ld)] - m1 - v[i] * m2);
+      ln_walk(to, N);  // (past the slice's last row nothing is stored)
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // out0[c] += sum_blk part[blk][0][c]; out1[c] += sum_blk part[blk][1][c]: 16 channels x 16 segments of the partial list per
 // workgroup, segment sums combined in a fixed order
 __global__ __launch_bounds__(256) void colsum_partials_kernel(const float* __restrict__ part, float* __restrict__ out0,
@@ -608,11 +745,15 @@ long long evmi_layernorm_bwd_cbt_f32_ws_elems(int C, long long n_cols) { return 
 int evmi_layernorm_bwd_cbt_f32(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, float* ws,
                                long long ws_elems, int C, long long n_cols, float eps, int accumulate_dx, void* stream) {
   if (!x || !gamma || !dy || !dx || !ws || (dgamma == nullptr) != (dbeta == nullptr)) return fail(EVMI_ERR_INVALID_ARG, "layernorm_bwd: null pointer");
-  if (C < 1 || C > 256 || n_cols < 1) return fail(EVMI_ERR_INVALID_ARG, "layernorm_bwd: 1 <= C <= 256 and n_cols >= 1 required");
+  if (C < 1 || C > 1024 || n_cols < 1) return fail(EVMI_ERR_INVALID_ARG, "layernorm_bwd: 1 <= C <= 1024 and n_cols >= 1 required");
   if (ws_elems < evmi_layernorm_bwd_cbt_f32_ws_elems(C, n_cols)) return fail(EVMI_ERR_INVALID_ARG, "layernorm_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const unsigned nblk = (unsigned)((n_cols + 63) / 64);
-  if (C <= 64) hipLaunchKernelGGL((layernorm_bwd_cbt_kernel<16, 4>), dim3(nblk), dim3(256), 0, s, x, gamma, dy, dx, ws, C, n_cols, eps, accumulate_dx);
+  // above 256 channels (the forward's range ends at 1024): sixteen slices of 32 channels keep x and dy in registers up to 512, the
+  // re-reading form takes the rest
+  if (C > 512) hipLaunchKernelGGL((layernorm_bwd_cbt_wide_kernel<64, 16>), dim3(nblk), dim3(1024), 0, s, x, gamma, dy, dx, ws, C, n_cols, eps, accumulate_dx);
+  else if (C > 256) hipLaunchKernelGGL((layernorm_bwd_cbt_kernel<32, 16>), dim3(nblk), dim3(1024), 0, s, x, gamma, dy, dx, ws, C, n_cols, eps, accumulate_dx);
+  else if (C <= 64) hipLaunchKernelGGL((layernorm_bwd_cbt_kernel<16, 4>), dim3(nblk), dim3(256), 0, s, x, gamma, dy, dx, ws, C, n_cols, eps, accumulate_dx);
   // fewer workgroups than CUs (the encoder's 4.5 k columns): sixteen slices of 16 channels -- twice the waves on each of the few CUs
   // that work (21.6 -> 16.8 us); with every CU busy the eight-slice form is the faster one (35.9 vs 43.0 us at 26 k columns)
   else if (nblk <= 256) hipLaunchKernelGGL((layernorm_bwd_cbt_kernel<16, 16>), dim3(nblk), dim3(1024), 0, s, x, gamma, dy, dx, ws, C, n_cols, eps, accumulate_dx);
@@ -632,7 +773,7 @@ int evmi_layernorm_bwd_partials_reduce(int n_jobs, const evmi_ln_partials* jobs,
     q.blk_start[0] = 0;
     for (int j = 0; j < q.n; ++j) {
       const evmi_ln_partials& jb = jobs[j0 + j];
-      if (!jb.ws || !jb.dgamma || !jb.dbeta || jb.C < 1 || jb.C > 256 || jb.n_cols < 1)
+      if (!jb.ws || !jb.dgamma || !jb.dbeta || jb.C < 1 || jb.C > 1024 || jb.n_cols < 1)
         return fail(EVMI_ERR_INVALID_ARG, "layernorm_bwd_partials_reduce: null pointer or bad shape");
       q.part[j] = jb.ws; q.out0[j] = jb.dgamma; q.out1[j] = jb.dbeta; q.C[j] = jb.C; q.nblk[j] = (int)((jb.n_cols + 63) / 64);
       q.blk_start[j + 1] = q.blk_start[j] + (2 * jb.C + 15) / 16;

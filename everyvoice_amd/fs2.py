@@ -206,7 +206,8 @@ def check_conformer_widths(c: "FastSpeech2ModelConfig") -> None:
     """Refuses, where the configuration is read (not inside the first forward or training step), an encoder / decoder whose width the
     kernels do not run: ``input_dim`` must be even (the sinusoidal positional term has ``input_dim / 2`` frequencies) and a multiple of
     ``heads``, and the head dimension ``input_dim / heads`` at most 256 (csrc/attention_generic.hip; 32 / 64 / 128 run on the specialised
-    kernels).  ``ValueError`` naming the field.  Called by the model, the trainer and ``lightning.FastSpeech2Config``."""
+    kernels), and ``input_dim`` itself at most 1024, the widest column the LayerNorm kernels (forward, backward, packed) normalise.
+    ``ValueError`` naming the field.  Called by the model, the trainer and ``lightning.FastSpeech2Config``."""
     for name in ("encoder", "decoder"):
         cf = getattr(c, name)
         d, heads = int(cf.input_dim), int(cf.heads)
@@ -217,6 +218,8 @@ def check_conformer_widths(c: "FastSpeech2ModelConfig") -> None:
         if d // heads > ops.ATTENTION_MAX_HEAD_DIM:
             raise ValueError(f"model.{name}.heads: the head dimension input_dim / heads = {d} / {heads} = {d // heads} is above "
                              f"{ops.ATTENTION_MAX_HEAD_DIM}, the largest the attention kernels take")
+        if d > ops.LAYERNORM_MAX_CHANNELS:
+            raise ValueError(f"model.{name}.input_dim: {d} is above {ops.LAYERNORM_MAX_CHANNELS}, the widest the LayerNorm kernels take")
 
 
 def gst_state_dict_shapes(c: "FastSpeech2ModelConfig") -> dict:

@@ -34,6 +34,7 @@ _ACT_EW = {ACT_LRELU: EW_LRELU, ACT_SILU: EW_SILU, ACT_RELU: EW_RELU, ACT_TANH: 
 CONV_BACKEND = {"fwd": "mfma", "dgrad": "mfma", "wgrad": "mfma", "operands": "f32", "packed": True}
 SIDE_WGRAD = {"on": False}  # weight gradients on a sibling stream ("weight gradients beside the input-gradient chain" below)
 SIDE_GROUP = [int(os.environ.get("EVMI_SIDE_GROUP", "8"))]  # launches per fork of that stream (<= 1: a fork per layer)
+LAYERNORM_MAX_CHANNELS = 1024  # evmi_layernorm_cbt_f32, evmi_layernorm_bwd_cbt_f32, evmi_layernorm_pack_bf16pk: the widest column
 LN_DEFER = {"on": False}  # LayerNorm parameter gradients reduced once per backward chain (layernorm_flush)
 # A device-resident base added to every dropout seed ([1] int64 tensor, or None): the FastSpeech2 trainer stores
 # (seed, step, rank) << 16 there before each step and passes the draw's index as `seed`, so a step captured into a HIP graph
@@ -43,6 +44,9 @@ SEED_BASE = [None]
 # in a layer's epilogue (conv1d_fwd_resdrop)
 FFN_PACKED = [os.environ.get("EVMI_FS2_FFN_PACKED", "1") != "0"]
 RESDROP_FUSION = [os.environ.get("EVMI_FS2_RESDROP", "1") != "0"]
+# The packed feed-forward chain above 256 channels: built and measured SLOWER than the separate operators (26.5 vs 25.7 ms
+# per captured step at 384, 36.2 vs 35.3 at 512), so it is not dispatched there; "1" takes it anyway (tools/fs2_wide_bench.py measures both).
+FFN_PACKED_WIDE = [os.environ.get("EVMI_FS2_FFN_PACKED_WIDE", "0") == "1"]
 UNSET = object()  # "not given" where None is a value (SEED_BASE[0] is None outside a step)
 
 
@@ -756,7 +760,10 @@ def ffn_fused_supported(B, t, c_mid, c_out) -> bool:
 
 def ln_dense_fused_supported(B, t, c_in, c_out) -> bool:
     """True where LayerNorm -> pointwise layer runs with the normalised tensor written straight into the layer's packed input."""
-    return c_in in (128, 256) and pointwise_shares_packed(B, t, (c_in, c_out), dgrad=False)
+    # (128 / 256: layernorm_pack_kernel; above 256 any multiple of 32 -- a thread's quarter of the column stays whole octets -- up to the
+    # LayerNorm kernels' 1024.  Other widths up to 256 keep the separate operators they always took.)
+    wide = 256 < c_in <= LAYERNORM_MAX_CHANNELS and c_in % 32 == 0
+    return (c_in in (128, 256) or wide) and pointwise_shares_packed(B, t, (c_in, c_out), dgrad=False)
 
 
 def resdrop_fused_supported(B, t, c_in, c_out) -> bool:
@@ -768,7 +775,8 @@ def resdrop_fused_supported(B, t, c_in, c_out) -> bool:
 def ffn_packed_supported(B, t, c_in, c_mid, c_out) -> bool:
     """True where LayerNorm -> dense(c_in -> c_mid) -> SiLU -> dropout -> dense(c_mid -> c_out) -> (+ residual, dropout) runs as the packed
     chain of ffn_packed_fwd / ffn_packed_bwd (every fusion it is built from is available)."""
-    return bool(FFN_PACKED[0] and c_mid % 8 == 0 and ffn_fused_supported(B, t, c_mid, c_out) and ln_dense_fused_supported(B, t, c_in, c_mid)
+    return bool(FFN_PACKED[0] and (c_in <= 256 or FFN_PACKED_WIDE[0]) and c_mid % 8 == 0 and ffn_fused_supported(B, t, c_mid, c_out)
+                and ln_dense_fused_supported(B, t, c_in, c_mid)
                 and resdrop_fused_supported(B, t, c_mid, c_out))
 
 

@@ -377,8 +377,8 @@ int evmi_conv1d_dgrad_cbt_bf16pk_ffn_down(const float* w_dev, float* ws_dev, lon
                                           long long next_ws_elems, int B, int c_in, int t, int c_mid, int c_out, float p,
                                           unsigned long long seed_value, const unsigned long long* seed_base_dev, void* stream);
 /* LayerNorm in front of a pointwise layer written as that layer's packed input, and the layer on an input already packed in the head
- * of ws (the Conformer's LayerNorm -> Linear pairs; layers of evmi_conv1d_bf16pk_shares_packed, 128 or 256 input channels): the
- * normalised tensor is never stored in fp32.  ws: evmi_conv1d_cbt_bf16pk_ws_elems floats of the layer (k = 1, stride 1, no padding). */
+ * of ws (the Conformer's LayerNorm -> Linear pairs; layers of evmi_conv1d_bf16pk_shares_packed; 128 or 256 input channels, or any
+ * multiple of 32 above 256 up to 1024): the normalised tensor is never stored in fp32.  ws: evmi_conv1d_cbt_bf16pk_ws_elems floats of the layer (k = 1, stride 1, no padding). */
 int evmi_layernorm_pack_bf16pk(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* ws_dev, long long ws_elems, int B,
                                int c_in, int t_in, int c_out, float eps, void* stream);
 /* ... with the weight fragments of the layer(s) behind the LayerNorm prepared by the SAME launch: w_dev [c_out][c_in] into ws_dev (run the
@@ -864,7 +864,8 @@ int evmi_monotonic_align_f32(const float* value_dev, const int* mel_lens_dev, co
  * submodule FastSpeech2_lightning (driver contract: everyvoice/base_cli/helpers.py:173-195).  Dense
  * layers use evmi_conv1d_cbt_f32 / evmi_conv1d_dgrad_cbt_f32 / evmi_conv1d_wgrad_cbt_f32 (k = 1).
  * ------------------------------------------------------------------------------------------ */
-/* LayerNorm over channels, backward: dx (+)= ..., dgamma += sum_cols dy * xhat, dbeta += sum_cols dy (C <= 256).
+/* LayerNorm over channels, backward: dx (+)= ..., dgamma += sum_cols dy * xhat, dbeta += sum_cols dy (1 <= C <= 1024, the range of
+ * evmi_layernorm_cbt_f32; above 512 channels dy is read twice).
  * ws: evmi_layernorm_bwd_cbt_f32_ws_elems floats (per-workgroup partial sums, reduced in a fixed order). */
 long long evmi_layernorm_bwd_cbt_f32_ws_elems(int C, long long n_cols);
 int evmi_layernorm_bwd_cbt_f32(const float* x_dev, const float* gamma_dev, const float* dy_dev, float* dx_dev,
