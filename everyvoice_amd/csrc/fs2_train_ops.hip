@@ -9,6 +9,8 @@
 //                                except embedding tables, where rows collide by construction)
 //   batchnorm_{stats,apply,bwd}  training-mode BatchNorm1d (batch statistics over every column, padded ones included:
 //                                torchaudio's Conformer does not mask them) with SiLU / tanh fused behind it
+//   batchnorm_{fwd,bwd}_valid    the same over the valid prefix of every item only (per-item counts from device memory: the
+//                                length-masked reference encoder of the style-token module)
 //   dwconv_bwd_{dx,dw}           depthwise convolution backward
 //   softmax_rows / softmax_bwd   key-masked softmax rows (+ dropout) and its backward, in place on [B][Tq][Tk]
 //   glu_bwd, dropout             elementwise
@@ -439,6 +441,112 @@ __global__ __launch_bounds__(NT) void batchnorm_bwd_cbt_kernel(const float* __re
   });
 }
 
+// ---- BatchNorm over the valid prefix of every item -------------------------------------------------------------------------------------
+// The pair above with per-item lengths from device memory: item b owns columns b T .. b T + T - 1 of every channel row and its first
+// valid[b] (clamped to [0, T]) columns count.  Statistics and gradient sums run over the valid columns of all items only (count = the sum
+// of valid[b]); invalid columns are never read (x and dy there may hold anything) and y / dx there are written as zero.  One workgroup per
+// channel, items in order, row_walk inside an item: fixed-order sums, no float atomics.
+__device__ __forceinline__ long long bn_valid_count(const int* __restrict__ valid, int B, int T) {
+  long long n = 0;
+  for (int b = 0; b < B; ++b) n += min(max(valid[b], 0), T);
+  return n;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void batchnorm_fwd_valid_cbt_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, float* __restrict__ y,
+                                                                     float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                                     float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                                     const int* __restrict__ valid, int B, int T, float eps, float momentum,
+                                                                     int act) {
+  __shared__ double sh[NT / 64];
+  const int c = blockIdx.x;
+  const float* xr = x + (long long)c * B * T;
+  float* yr = y + (long long)c * B * T;
+  float mean, rstd;
+  if (momentum < 0.f) {  // evaluation mode: the running statistics normalise, nothing is updated
+    mean = running_mean[c];
+    rstd = 1.f / sqrtf(running_var[c] + eps);
+  } else {
+    const long long cnt = bn_valid_count(valid, B, T);
+    const double N = (double)(cnt > 0 ? cnt : 1);
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) {
+      const float* xb = xr + (long long)b * T;
+      row_walk<NT>(min(max(valid[b], 0), T), [&](long long i) { return xb[i]; }, [&](long long, float v) { s += (double)v; });
+    }
+    mean = (float)(block_sum<NT>(s, sh) / N);
+    double q = 0.0;
+    for (int b = 0; b < B; ++b) {
+      const float* xb = xr + (long long)b * T;
+      row_walk<NT>(min(max(valid[b], 0), T), [&](long long i) { return xb[i]; }, [&](long long, float v) { const float d = v - mean; q += (double)(d * d); });
+    }
+    const double ss = block_sum<NT>(q, sh);
+    rstd = 1.f / sqrtf((float)(ss / N) + eps);
+    if (threadIdx.x == 0 && running_mean) {
+      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
+      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(ss / (double)(cnt > 1 ? cnt - 1 : 1));
+    }
+  }
+  if (threadIdx.x == 0) { mean_out[c] = mean; rstd_out[c] = rstd; }
+  const float ga = gamma[c] * rstd, be = beta[c];
+  for (int b = 0; b < B; ++b) {
+    const float* xb = xr + (long long)b * T;
+    float* yb = yr + (long long)b * T;
+    const int n = min(max(valid[b], 0), T);
+    row_walk<NT>(n, [&](long long i) { return xb[i]; }, [&](long long i, float v) { yb[i] = bn_act((v - mean) * ga + be, act); });
+    for (int i = n + threadIdx.x; i < T; i += NT) yb[i] = 0.f;
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void batchnorm_bwd_valid_cbt_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, const float* __restrict__ mean_in,
+                                                                     const float* __restrict__ rstd_in, const float* __restrict__ dy,
+                                                                     float* __restrict__ dx, float* __restrict__ dgamma,
+                                                                     float* __restrict__ dbeta, const int* __restrict__ valid, int B, int T,
+                                                                     int act) {
+  __shared__ double sh[NT / 64];
+  const int c = blockIdx.x;
+  const float* xr = x + (long long)c * B * T;
+  const float* dr = dy + (long long)c * B * T;
+  float* dxr = dx + (long long)c * B * T;
+  const float mean = mean_in[c], rstd = rstd_in[c], ga = gamma[c], be = beta[c];
+  const long long cnt = bn_valid_count(valid, B, T);
+  const double N = (double)(cnt > 0 ? cnt : 1);
+  double s1 = 0.0, s2 = 0.0;
+  struct XD { float x, d; };
+  for (int b = 0; b < B; ++b) {
+    const float* xb = xr + (long long)b * T;
+    const float* db = dr + (long long)b * T;
+    row_walk<NT>(min(max(valid[b], 0), T), [&](long long i) { return XD{xb[i], db[i]}; }, [&](long long, XD v) {
+      const float xh = (v.x - mean) * rstd;
+      const float dz = v.d * bn_act_grad(xh * ga + be, act);
+      s1 += (double)dz;
+      s2 += (double)(dz * xh);
+    });
+  }
+  const double t1 = block_sum<NT>(s1, sh);
+  const double t2 = block_sum<NT>(s2, sh);
+  if (threadIdx.x == 0) {
+    dbeta[c] += (float)t1;
+    dgamma[c] += (float)t2;
+  }
+  const float m1 = (float)(t1 / N), m2 = (float)(t2 / N);
+  for (int b = 0; b < B; ++b) {
+    const float* xb = xr + (long long)b * T;
+    const float* db = dr + (long long)b * T;
+    float* dxb = dxr + (long long)b * T;
+    const int n = min(max(valid[b], 0), T);
+    row_walk<NT>(n, [&](long long i) { return XD{xb[i], db[i]}; }, [&](long long i, XD v) {
+      const float xh = (v.x - mean) * rstd;
+      const float dz = v.d * bn_act_grad(xh * ga + be, act);
+      dxb[i] = ga * rstd * (dz - m1 - xh * m2);
+    });
+    for (int i = n + threadIdx.x; i < T; i += NT) dxb[i] = 0.f;
+  }
+}
+
 // ---- depthwise convolution backward ----------------------------------------------------------------------------------
 // dx[c][b][t] = sum_j w[c][j] * dy[c][b][t + pad - j]
 __global__ void dwconv_bwd_dx_kernel(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx, int C, int B,
@@ -814,6 +922,43 @@ int evmi_batchnorm_bwd_cbt_f32(const float* x, const float* gamma, const float* 
     hipLaunchKernelGGL(batchnorm_bwd_cbt_kernel<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, mean, rstd, dy, dx, dgamma,
                        dbeta, n_cols, act);
   EVMI_LAUNCH_CHECK("batchnorm_bwd_cbt");
+  return EVMI_OK;
+}
+
+int evmi_batchnorm_fwd_valid_cbt_f32(const float* x, const float* gamma, const float* beta, float* y, float* mean_out, float* rstd_out,
+                                     float* running_mean, float* running_var, int C, long long n_cols, float eps, float momentum, int act,
+                                     const int* valid_dev, int B, int T, void* stream) {
+  if (!x || !gamma || !beta || !y || !mean_out || !rstd_out || !valid_dev) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd_valid: null pointer");
+  if ((running_mean == nullptr) != (running_var == nullptr)) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd_valid: running_mean and running_var go together");
+  if (C < 1 || n_cols < 1) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd_valid: empty input");
+  if (B < 1 || T < 1 || (long long)B * T != n_cols) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd_valid: n_cols must be B * T (item b owns columns b T .. b T + T - 1)");
+  if (act != 0 && act != 2 && act != 3 && act != 4) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd_valid: act must be 0 (none), 2 (SiLU), 3 (ReLU) or 4 (tanh)");
+  if (momentum < 0.f && (!running_mean || !running_var)) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_fwd_valid: evaluation mode (momentum < 0) needs the running statistics");
+  if (n_cols >= BN_LONG_ROW)
+    hipLaunchKernelGGL(batchnorm_fwd_valid_cbt_kernel<1024>, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, gamma, beta, y, mean_out, rstd_out,
+                       running_mean, running_var, valid_dev, B, T, eps, momentum, act);
+  else
+    hipLaunchKernelGGL(batchnorm_fwd_valid_cbt_kernel<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean_out, rstd_out,
+                       running_mean, running_var, valid_dev, B, T, eps, momentum, act);
+  EVMI_LAUNCH_CHECK("batchnorm_fwd_valid_cbt");
+  return EVMI_OK;
+}
+
+int evmi_batchnorm_bwd_valid_cbt_f32(const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                     const float* dy, float* dx, float* dgamma, float* dbeta, int C, long long n_cols, int act,
+                                     const int* valid_dev, int B, int T, void* stream) {
+  if (!x || !gamma || !beta || !mean || !rstd || !dy || !dx || !dgamma || !dbeta || !valid_dev)
+    return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd_valid: null pointer");
+  if (C < 1 || n_cols < 1) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd_valid: empty input");
+  if (B < 1 || T < 1 || (long long)B * T != n_cols) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd_valid: n_cols must be B * T (item b owns columns b T .. b T + T - 1)");
+  if (act != 0 && act != 2 && act != 3 && act != 4) return fail(EVMI_ERR_INVALID_ARG, "batchnorm_bwd_valid: act must be 0 (none), 2 (SiLU), 3 (ReLU) or 4 (tanh)");
+  if (n_cols >= BN_LONG_ROW)
+    hipLaunchKernelGGL(batchnorm_bwd_valid_cbt_kernel<1024>, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, gamma, beta, mean, rstd, dy, dx,
+                       dgamma, dbeta, valid_dev, B, T, act);
+  else
+    hipLaunchKernelGGL(batchnorm_bwd_valid_cbt_kernel<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, mean, rstd, dy, dx,
+                       dgamma, dbeta, valid_dev, B, T, act);
+  EVMI_LAUNCH_CHECK("batchnorm_bwd_valid_cbt");
   return EVMI_OK;
 }
 

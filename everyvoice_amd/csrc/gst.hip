@@ -6,6 +6,8 @@
 //                               weights are workgroup-uniform (scalar loads).
 //   gst_gru_{fwd,bwd}           the recurrence of a single-layer GRU in ONE launch for all steps: a workgroup per item, a thread per
 //                               gate row, its row (backward: its column piece) of W_hh in registers for all steps, h in LDS.
+//   gst_conv_fwd_rows, gst_gru_{fwd,bwd}_steps  the same with per-item lengths read from device memory: rows / steps beyond an
+//                               item's length are absent (never read), what is written there is zero.
 //   gst_attention_{fwd,bwd}     one query per item against the style tokens' keys / values, `heads` heads.
 // Every sum is taken in a fixed order (no float atomics): the training step is bit-reproducible run to run.
 #include "common.h"
@@ -38,6 +40,63 @@ __global__ __launch_bounds__(kConvThreads) void gst_conv_fwd_kernel(const float*
     for (int kw = 0; kw < 3; ++kw) {
       const int ih = 2 * oh - 1 + kh, iw = 2 * ow - 1 + kw;
       ok[kh * 3 + kw] = ih >= 0 && ih < H && iw >= 0 && iw < W;
+      off[kh * 3 + kw] = ok[kh * 3 + kw] ? ih * W + iw : 0;
+    }
+  float acc[kFwdCoTile];
+#pragma unroll
+  for (int j = 0; j < kFwdCoTile; ++j) acc[j] = (bias && co0 + j < Cout) ? bias[co0 + j] : 0.f;
+  const long long plane = (long long)H * W;
+  for (int ci = 0; ci < Cin; ++ci) {
+    const float* xp = x + ((long long)ci * B + b) * plane;
+    float v[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) v[t] = ok[t] ? xp[off[t]] : 0.f;
+#pragma unroll
+    for (int j = 0; j < kFwdCoTile; ++j) {
+      if (co0 + j >= Cout) break;
+      const float* wp = w + ((long long)(co0 + j) * Cin + ci) * 9;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) acc[j] = fmaf(v[t], wp[t], acc[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kFwdCoTile; ++j) {
+    if (co0 + j >= Cout) break;
+    float r = acc[j];
+    if (act == 3) r = fmaxf(r, 0.f);
+    y[((long long)(co0 + j) * B + b) * OH * OW + (long long)oh * OW + ow] = r;
+  }
+}
+
+// ---- forward with per-item row counts: rows at or beyond rows_in[b] are absent (never read), output rows beyond conv_out(rows_in[b])
+// are written as zero.  The per-output sum (input channels outer, nine taps inner) is gst_conv_fwd_kernel's: with rows_in[b] == H for
+// every item the two are bit-equal.  A thread of an invalid output row stores its zeros and leaves before the channel loop.
+__global__ __launch_bounds__(kConvThreads) void gst_conv_fwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                         const float* __restrict__ bias, float* __restrict__ y,
+                                                                         const int* __restrict__ rows_in, int Cin, int Cout, int B, int H,
+                                                                         int W, int OH, int OW, int act) {
+  const long long n = (long long)blockIdx.x * kConvThreads + threadIdx.x;
+  const long long total = (long long)B * OH * OW;
+  if (n >= total) return;
+  const int co0 = blockIdx.y * kFwdCoTile;
+  const int ow = (int)(n % OW), oh = (int)((n / OW) % OH), b = (int)(n / ((long long)OW * OH));
+  const int rows = min(max(rows_in[b], 0), H);
+  if (rows < 1 || oh >= conv_out(rows)) {
+#pragma unroll
+    for (int j = 0; j < kFwdCoTile; ++j) {
+      if (co0 + j >= Cout) break;
+      y[((long long)(co0 + j) * B + b) * OH * OW + (long long)oh * OW + ow] = 0.f;
+    }
+    return;
+  }
+  int off[9];
+  bool ok[9];
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const int ih = 2 * oh - 1 + kh, iw = 2 * ow - 1 + kw;
+      ok[kh * 3 + kw] = ih >= 0 && ih < rows && iw >= 0 && iw < W;
       off[kh * 3 + kw] = ok[kh * 3 + kw] ? ih * W + iw : 0;
     }
   float acc[kFwdCoTile];
@@ -305,6 +364,124 @@ __global__ __launch_bounds__(3 * H) void gst_gru_bwd_kernel(const float* __restr
   }
 }
 
+// ---- GRU recurrence with per-item step counts --------------------------------------------------------------------------------------
+// Item b runs n = clamp(steps[b], 1, T) steps: hlast is the state after step n - 1, the saved tensors and dgi / dgh are zero at later
+// steps (so the dense weight gradients over all B * T columns pick up nothing from them) and gi there is never read.  n is read once
+// into a workgroup-uniform value: every __syncthreads() is reached by all threads.  With steps[b] == T the loops are those above.
+template <int H>
+__global__ __launch_bounds__(3 * H) void gst_gru_fwd_steps_kernel(const float* __restrict__ gi, const float* __restrict__ whh,
+                                                                  const float* __restrict__ bhh, float* __restrict__ rzn,
+                                                                  float* __restrict__ hn, float* __restrict__ hprev,
+                                                                  float* __restrict__ hlast, const int* __restrict__ steps, int B, int T) {
+  __shared__ __attribute__((aligned(16))) float h[H];
+  __shared__ float gate[2 * H];
+  const int b = blockIdx.x, j = threadIdx.x;
+  const int n_steps = __builtin_amdgcn_readfirstlane(min(max(steps[b], 1), T));
+  float w[H];
+#pragma unroll
+  for (int k = 0; k < H; ++k) w[k] = whh[(long long)j * H + k];
+  const float bj = bhh[j];
+  if (j < H) h[j] = 0.f;
+  __syncthreads();
+  const long long row = ((long long)j * B + b) * T;
+  for (int t = 0; t < n_steps; ++t) {
+    const float x = gi[row + t];
+    float acc = bj;
+#pragma unroll
+    for (int k = 0; k < H; k += 4) {
+      const f32x4 hv = *reinterpret_cast<const f32x4*>(h + k);
+      acc = fmaf(w[k], hv[0], acc);
+      acc = fmaf(w[k + 1], hv[1], acc);
+      acc = fmaf(w[k + 2], hv[2], acc);
+      acc = fmaf(w[k + 3], hv[3], acc);
+    }
+    if (j < 2 * H) {
+      const float v = sigmoid_(x + acc);
+      gate[j] = v;
+      if (rzn) rzn[row + t] = v;
+    }
+    __syncthreads();  // every product has read h; r and z are in LDS
+    if (j >= 2 * H) {
+      const int k = j - 2 * H;
+      const float r = gate[k], z = gate[H + k], hp = h[k];
+      const float n = tanhf(x + r * acc);
+      if (rzn) {
+        rzn[row + t] = n;
+        hn[((long long)k * B + b) * T + t] = acc;
+        hprev[((long long)k * B + b) * T + t] = hp;
+      }
+      h[k] = (1.f - z) * n + z * hp;
+    }
+    __syncthreads();
+  }
+  if (j < H) hlast[(long long)j * B + b] = h[j];
+  if (rzn)
+    for (int t = n_steps; t < T; ++t) {
+      rzn[row + t] = 0.f;
+      if (j < H) {
+        hn[row + t] = 0.f;  // (j < H: row is also the [H][B][T] offset of hidden unit j)
+        hprev[row + t] = 0.f;
+      }
+    }
+}
+
+template <int H>
+__global__ __launch_bounds__(3 * H) void gst_gru_bwd_steps_kernel(const float* __restrict__ rzn, const float* __restrict__ hn,
+                                                                  const float* __restrict__ hprev, const float* __restrict__ whh,
+                                                                  const float* __restrict__ dhlast, float* __restrict__ dgi,
+                                                                  float* __restrict__ dgh, const int* __restrict__ steps, int B, int T) {
+  __shared__ __attribute__((aligned(16))) float dg[3 * H];
+  __shared__ float part[3 * H];
+  __shared__ float dh[H];
+  const int b = blockIdx.x, j = threadIdx.x, g = j / H, k = j % H;
+  const int n_steps = __builtin_amdgcn_readfirstlane(min(max(steps[b], 1), T));
+  float wt[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) wt[i] = whh[((long long)g * H + i) * H + k];
+  if (g == 0) dh[k] = dhlast[(long long)k * B + b];
+  __syncthreads();
+  const long long BT = (long long)B * T;
+  const long long col = ((long long)k * B + b) * T;
+  for (int t = n_steps; t < T; ++t) {  // the absent steps: thread (g, k) zeroes gate row g H + k of both outputs
+    dgi[(long long)g * H * BT + col + t] = 0.f;
+    dgh[(long long)g * H * BT + col + t] = 0.f;
+  }
+  for (int t = n_steps - 1; t >= 0; --t) {
+    float carry = 0.f;
+    if (g == 0) {
+      const float r = rzn[col + t], z = rzn[(long long)H * BT + col + t], n = rzn[2ll * H * BT + col + t];
+      const float a = hn[col + t], hp = hprev[col + t], d = dh[k];
+      const float dn = d * (1.f - z) * (1.f - n * n);
+      const float dz = d * (hp - n) * z * (1.f - z);
+      const float dr = dn * a * r * (1.f - r);
+      dgi[col + t] = dr;
+      dgi[(long long)H * BT + col + t] = dz;
+      dgi[2ll * H * BT + col + t] = dn;
+      dgh[col + t] = dr;
+      dgh[(long long)H * BT + col + t] = dz;
+      dgh[2ll * H * BT + col + t] = dn * r;
+      dg[k] = dr;
+      dg[H + k] = dz;
+      dg[2 * H + k] = dn * r;
+      carry = d * z;
+    }
+    __syncthreads();
+    float p = 0.f;
+#pragma unroll
+    for (int i = 0; i < H; i += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(dg + g * H + i);
+      p = fmaf(wt[i], v[0], p);
+      p = fmaf(wt[i + 1], v[1], p);
+      p = fmaf(wt[i + 2], v[2], p);
+      p = fmaf(wt[i + 3], v[3], p);
+    }
+    part[j] = p;
+    __syncthreads();
+    if (g == 0) dh[k] = carry + ((part[k] + part[H + k]) + part[2 * H + k]);
+    __syncthreads();
+  }
+}
+
 // ---- style-token attention ---------------------------------------------------------------------------------------------------------
 // q [E][B], keys / values [E][N] (channel-major, as the dense layers write them); style [B][E]; probs [B][heads][N]
 constexpr int kMaxTokens = 16;
@@ -427,6 +604,19 @@ int evmi_gst_conv2d_fwd_f32(const float* x, const float* w, const float* bias, f
   return EVMI_OK;
 }
 
+int evmi_gst_conv2d_fwd_rows_f32(const float* x, const float* w, const float* bias, float* y, const int* rows_in_dev, int Cin, int Cout, int B,
+                                 int H, int W, int act, void* stream) {
+  if (!x || !w || !y || !rows_in_dev || !conv_shape_ok(Cin, Cout, B, H, W)) return fail(EVMI_ERR_INVALID_ARG, "gst_conv2d_fwd_rows: bad arguments");
+  if (act != 0 && act != 3) return fail(EVMI_ERR_INVALID_ARG, "gst_conv2d_fwd_rows: act must be 0 (none) or 3 (ReLU)");
+  const int OH = conv_out(H), OW = conv_out(W);
+  const long long total = (long long)B * OH * OW;
+  const dim3 grid((unsigned)((total + kConvThreads - 1) / kConvThreads), (unsigned)((Cout + kFwdCoTile - 1) / kFwdCoTile));
+  hipLaunchKernelGGL(gst_conv_fwd_rows_kernel, grid, dim3(kConvThreads), 0, (hipStream_t)stream, x, w, bias, y, rows_in_dev, Cin, Cout, B, H, W,
+                     OH, OW, act);
+  EVMI_LAUNCH_CHECK("gst_conv2d_fwd_rows");
+  return EVMI_OK;
+}
+
 int evmi_gst_conv2d_dgrad_f32(const float* dy, const float* w, float* dx, int Cin, int Cout, int B, int H, int W, void* stream) {
   if (!dy || !w || !dx || !conv_shape_ok(Cin, Cout, B, H, W)) return fail(EVMI_ERR_INVALID_ARG, "gst_conv2d_dgrad: bad arguments");
   const int OH = conv_out(H), OW = conv_out(W);
@@ -489,6 +679,39 @@ int evmi_gst_gru_bwd_f32(const float* rzn, const float* hn, const float* hprev, 
   else
     return fail(EVMI_ERR_UNSUPPORTED, "gst_gru_bwd: hidden size 32, 64 or 128 (encoder.input_dim 64, 128 or 256)");
   EVMI_LAUNCH_CHECK("gst_gru_bwd");
+  return EVMI_OK;
+}
+
+int evmi_gst_gru_fwd_steps_f32(const float* gi, const float* whh, const float* bhh, float* rzn, float* hn, float* hprev, float* hlast,
+                               const int* steps_dev, int B, int T, int H, void* stream) {
+  if (!gi || !whh || !bhh || !hlast || !steps_dev || B < 1 || T < 1) return fail(EVMI_ERR_INVALID_ARG, "gst_gru_fwd_steps: bad arguments");
+  if ((rzn != nullptr) != (hn != nullptr) || (rzn != nullptr) != (hprev != nullptr))
+    return fail(EVMI_ERR_INVALID_ARG, "gst_gru_fwd_steps: the saved tensors (gates, hn, hprev) go together");
+  if (H == 128)
+    hipLaunchKernelGGL(gst_gru_fwd_steps_kernel<128>, dim3(B), dim3(384), 0, (hipStream_t)stream, gi, whh, bhh, rzn, hn, hprev, hlast, steps_dev, B, T);
+  else if (H == 64)
+    hipLaunchKernelGGL(gst_gru_fwd_steps_kernel<64>, dim3(B), dim3(192), 0, (hipStream_t)stream, gi, whh, bhh, rzn, hn, hprev, hlast, steps_dev, B, T);
+  else if (H == 32)
+    hipLaunchKernelGGL(gst_gru_fwd_steps_kernel<32>, dim3(B), dim3(96), 0, (hipStream_t)stream, gi, whh, bhh, rzn, hn, hprev, hlast, steps_dev, B, T);
+  else
+    return fail(EVMI_ERR_UNSUPPORTED, "gst_gru_fwd_steps: hidden size 32, 64 or 128 (encoder.input_dim 64, 128 or 256)");
+  EVMI_LAUNCH_CHECK("gst_gru_fwd_steps");
+  return EVMI_OK;
+}
+
+int evmi_gst_gru_bwd_steps_f32(const float* rzn, const float* hn, const float* hprev, const float* whh, const float* dhlast, float* dgi,
+                               float* dgh, const int* steps_dev, int B, int T, int H, void* stream) {
+  if (!rzn || !hn || !hprev || !whh || !dhlast || !dgi || !dgh || !steps_dev || B < 1 || T < 1)
+    return fail(EVMI_ERR_INVALID_ARG, "gst_gru_bwd_steps: bad arguments");
+  if (H == 128)
+    hipLaunchKernelGGL(gst_gru_bwd_steps_kernel<128>, dim3(B), dim3(384), 0, (hipStream_t)stream, rzn, hn, hprev, whh, dhlast, dgi, dgh, steps_dev, B, T);
+  else if (H == 64)
+    hipLaunchKernelGGL(gst_gru_bwd_steps_kernel<64>, dim3(B), dim3(192), 0, (hipStream_t)stream, rzn, hn, hprev, whh, dhlast, dgi, dgh, steps_dev, B, T);
+  else if (H == 32)
+    hipLaunchKernelGGL(gst_gru_bwd_steps_kernel<32>, dim3(B), dim3(96), 0, (hipStream_t)stream, rzn, hn, hprev, whh, dhlast, dgi, dgh, steps_dev, B, T);
+  else
+    return fail(EVMI_ERR_UNSUPPORTED, "gst_gru_bwd_steps: hidden size 32, 64 or 128 (encoder.input_dim 64, 128 or 256)");
+  EVMI_LAUNCH_CHECK("gst_gru_bwd_steps");
   return EVMI_OK;
 }
 

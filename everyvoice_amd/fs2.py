@@ -97,6 +97,9 @@ class FastSpeech2ModelConfig:
     use_global_style_token_module: bool = False
     # not in the reference's schema (fixed inside the absent module; the GST paper's / GST-Tacotron's values)
     gst_num_heads: int = 8
+    # the reference encoder treats frames beyond a reference's length as absent: the style embedding of an
+    # utterance then does not depend on the padding or on what else is in its batch.  False = consume the padded tensor as torch.nn would
+    gst_mask_padding: bool = False
     gst_num_tokens: int = 10
     gst_ref_enc_filters: tuple = (32, 32, 64, 64, 128, 128)
 
@@ -277,18 +280,39 @@ class StyleTokens:
         self.values = put(sd[a + "W_value.weight"].float().cpu() @ tokens.t())
         self.w_q = put(sd[a + "W_query.weight"].unsqueeze(-1))
 
-    def forward(self, mel: torch.Tensor) -> torch.Tensor:
+    def forward(self, mel: torch.Tensor, lens: torch.Tensor | None = None) -> torch.Tensor:
+        """``lens`` (int32 [B] on the device, 1 <= lens[b] <= T): frames at or beyond lens[b] are absent, whatever they hold -- row b is
+        the embedding of that reference alone at its own length.  None: the mel is consumed as given."""
         B, T, F = mel.shape
         x = mel.view(1, B, T, F)
-        for w, b in self.convs:
-            x = ops.gst_conv2d_fwd(x, w, b, ops.ACT_RELU)
+        rows = [lens] + ops.gst_valid_rows(lens, len(self.convs)) if lens is not None else [None] * (len(self.convs) + 1)
+        for (w, b), n in zip(self.convs, rows):
+            x = ops.gst_conv2d_fwd(x, w, b, ops.ACT_RELU, rows=n)
         C, _, T2, F2 = x.shape
         seq = x.permute(0, 3, 1, 2).reshape(C * F2, 1, B * T2)  # the GRU's input features: channel-major (c, bin), one column per (item, step)
         with ops.exact_f32():
             gi = ops.conv1d_fwd(seq, self.w_ih, self.b_ih).view(-1, B, T2)
-            h, _ = ops.gst_gru_fwd(gi, self.w_hh, self.b_hh, save=False)
+            h, _ = ops.gst_gru_fwd(gi, self.w_hh, self.b_hh, save=False, steps=rows[-1])
             q = ops.conv1d_fwd(h.view(-1, 1, B), self.w_q, None).view(-1, B)
         return ops.gst_attention_fwd(q, self.keys, self.values, self.heads, save=False)[0]
+
+
+def check_style_lens(style_lens, style_mel_shape, what="style_lens"):
+    """Host-side refusals for the per-reference lengths that go with ``style_mel`` [n, Ts, n_mels]: ``style_lens`` must be an integer
+    [n] with 1 <= length <= Ts.  Values are looked at only where the lengths live on the host (a device tensor is not synchronised
+    with); the kernels clamp what they read."""
+    if style_lens is None:
+        return None
+    if style_mel_shape is None:
+        raise ValueError(f"`{what}` given without `style_mel`")
+    if not isinstance(style_lens, torch.Tensor):
+        style_lens = torch.as_tensor(style_lens)
+    n, Ts = int(style_mel_shape[0]), int(style_mel_shape[1])
+    if style_lens.dim() != 1 or style_lens.shape[0] != n or style_lens.dtype.is_floating_point or style_lens.dtype == torch.bool:
+        raise ValueError(f"{what}: expected {n} integer lengths (one per row of style_mel), got {style_lens.dtype} {tuple(style_lens.shape)}")
+    if style_lens.device.type == "cpu" and n and (int(style_lens.min()) < 1 or int(style_lens.max()) > Ts):
+        raise ValueError(f"{what}: lengths must be between 1 and Ts = {Ts}, got {style_lens.tolist()}")
+    return style_lens
 
 
 class _Conformer:
@@ -538,17 +562,20 @@ class FastSpeech2:
     @torch.no_grad()
     def __call__(self, ids: torch.Tensor, lens: torch.Tensor, duration_control=1.0, pitch_control=1.0, energy_control=1.0,
                  durations: torch.Tensor | None = None, speakers: torch.Tensor | None = None, languages: torch.Tensor | None = None,
-                 style_mel: torch.Tensor | None = None):
+                 style_mel: torch.Tensor | None = None, style_lens: torch.Tensor | None = None):
         """ids [B, L] (0 = padding), lens [B] -> (mel [B, T, n_mels], postnet mel, durations [B, L], pitch, energy, mel_lens [B]) on the
         device.  ``pitch`` / ``energy`` (the predictions times their control, zero at padded positions) are [B, L] for a phone-level
         predictor and [B, T] for a frame-level one (``variance_predictors.<name>.level``).  ``style_mel`` (a model with the Global Style Token module needs it, any other
-        refuses it): the style reference's mel [B, Ts, n_mels], or [1, Ts, n_mels] for one reference serving the whole batch."""
+        refuses it): the style reference's mel [B, Ts, n_mels], or [1, Ts, n_mels] for one reference serving the whole batch.
+        ``style_lens`` ([B] or [1], matching ``style_mel``): the references' frame counts; frames beyond them are absent (DESIGN.md
+        section 25).  None: the references are consumed as given, padding included."""
         if not self._ready:
             raise RuntimeError("load_state_dict() or init_random() first")
+        style_lens = check_style_lens(style_lens, None if style_mel is None else style_mel.shape)
         with ops.mode(operands=self.precision):
-            return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel)
+            return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel, style_lens)
 
-    def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None):
+    def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None, style_lens=None):
         lib, dev, c = _lib.load(), self.device, self.config
         B, L = ids.shape[:2]
         if L > c.max_length:
@@ -585,7 +612,8 @@ class FastSpeech2:
                      "evmi_fs2_add_item_embedding_f32")
         if self.gst is not None:
             # the style matrix [B or 1, E] is the "table" of the same masked add; one reference: every item takes row 0 (computed once)
-            style = self.gst.forward(style_mel.to(dev, torch.float32).contiguous())
+            style = self.gst.forward(style_mel.to(dev, torch.float32).contiguous(),
+                                     None if style_lens is None else style_lens.to(dev, torch.int32).contiguous())
             rows = torch.arange(B, device=dev, dtype=torch.int32) if style.shape[0] == B else torch.zeros(B, device=dev, dtype=torch.int32)
             _chk(lib.evmi_fs2_add_item_embedding_f32(x.data_ptr(), rows.data_ptr(), lens32.data_ptr(), style.data_ptr(), B, L, D, _s(x)),
                  "evmi_fs2_add_item_embedding_f32")

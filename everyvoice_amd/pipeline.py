@@ -686,6 +686,20 @@ def style_reference_mel(style_reference, cfg: AudioConfig | None = None, device=
     return mel.transpose(0, 1)[None].contiguous()
 
 
+def style_reference_batch(references, cfg: AudioConfig | None = None, device="cuda:0", sampling_rate: int | None = None):
+    """One style reference per item (each a wav path or a 1-D waveform, as ``style_reference_mel`` takes them) ->
+    (mel [n, Tmax, n_mels] zero padded, lens int32 [n]) on the device: what ``FastSpeech2.__call__`` takes as ``style_mel`` /
+    ``style_lens``, so that every item's style embedding is that of its own reference alone."""
+    if isinstance(references, (str, Path)) or torch.is_tensor(references) or isinstance(references, np.ndarray) or not len(references):
+        raise ValueError("style_reference_batch: a non-empty list of references (wav paths or 1-D waveforms), one per item")
+    mels = [style_reference_mel(r, cfg, device, sampling_rate)[0] for r in references]
+    lens = torch.tensor([m.shape[0] for m in mels], dtype=torch.int32)
+    mel = torch.zeros(len(mels), int(lens.max()), mels[0].shape[1], device=mels[0].device, dtype=torch.float32)
+    for i, m in enumerate(mels):
+        mel[i, : m.shape[0]] = m
+    return mel, lens.to(mel.device)
+
+
 def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, out_dir, basenames: list[str], speaker: str = "default",
                          language: str = "default", output_types=("wav", "spec"), sr: int = 22050, hop: int = 256,
                          duration_control: float = 1.0, global_step: int | None = None, style_reference=None,
@@ -696,12 +710,19 @@ def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, ou
     ``<out_dir>/wav/<basename>--<speaker>--<language>--pred.wav`` and ``<out_dir>/synthesized_spec/...--spec-pred....pt``
     holding ``[n_mels, T]``.  Text normalisation / g2p (CPU string work) stays with the caller: ``ids`` are symbol ids, 0 pads.
     ``style_reference`` (a wav path, or a 1-D waveform at ``style_reference_sampling_rate``; ``audio_config``: the model's
-    ``preprocessing.audio``, default as in ``synthesize_helper``): a model with the Global Style Token module needs it, any other refuses it."""
+    ``preprocessing.audio``, default as in ``synthesize_helper``): a model with the Global Style Token module needs it, any other refuses it.
+    A list of references gives every item its own (``style_reference_batch``: padded together, passed with their lengths)."""
     kw = {}
     if style_reference is not None:
         if not _has_style_tokens(fs2):
             raise ValueError("style_reference given, but this model has no Global Style Token module (model.use_global_style_token_module)")
-        kw["style_mel"] = style_reference_mel(style_reference, _style_audio_config(fs2, audio_config), fs2.device, style_reference_sampling_rate)
+        cfg = _style_audio_config(fs2, audio_config)
+        if isinstance(style_reference, (list, tuple)):  # one reference per item, each embedded alone at its own length
+            if len(style_reference) != ids.shape[0]:
+                raise ValueError(f"style_reference: a list needs one reference per item ({ids.shape[0]}), got {len(style_reference)}")
+            kw["style_mel"], kw["style_lens"] = style_reference_batch(style_reference, cfg, fs2.device, style_reference_sampling_rate)
+        else:
+            kw["style_mel"] = style_reference_mel(style_reference, cfg, fs2.device, style_reference_sampling_rate)
     mel, post, durations, _, _, mel_lens = fs2(ids, lens, duration_control=duration_control, **kw)
     wav = vocoder(post.transpose(1, 2).contiguous()) if "wav" in output_types else None
     results = []

@@ -271,13 +271,16 @@ def layernorm(tape: Tape, x: Var, ln: Affine) -> Var:
     return y
 
 
-def batchnorm(tape: Tape, x: Var, bn: Affine, act=ops.ACT_NONE) -> Var:
+def batchnorm(tape: Tape, x: Var, bn: Affine, act=ops.ACT_NONE, valid=None, items=None) -> Var:
+    """``valid`` (int32 [items] on the device): the statistics run over the first valid[b] columns of each of the ``items`` equal column
+    blocks only; the other columns come out as zero and their incoming gradient is ignored."""
     if _EVAL[0]:
-        return Var(ops.batchnorm_fwd(x.data, bn.gamma(), bn.beta(), bn.running_mean, bn.running_var, act, momentum=-1.0)[0])
-    out, mean, rstd = ops.batchnorm_fwd(x.data, bn.gamma(), bn.beta(), bn.running_mean, bn.running_var, act)
+        return Var(ops.batchnorm_fwd(x.data, bn.gamma(), bn.beta(), bn.running_mean, bn.running_var, act, momentum=-1.0, valid=valid, items=items)[0])
+    out, mean, rstd = ops.batchnorm_fwd(x.data, bn.gamma(), bn.beta(), bn.running_mean, bn.running_var, act, valid=valid, items=items)
     bn.batches += 1
     y = Var(out)
-    tape.record(lambda: y.grad is not None and x.accumulate(ops.batchnorm_bwd(x.data, bn.gamma(), bn.beta(), mean, rstd, y.grad, bn.dgamma(), bn.dbeta(), act)))
+    tape.record(lambda: y.grad is not None and x.accumulate(ops.batchnorm_bwd(x.data, bn.gamma(), bn.beta(), mean, rstd, y.grad, bn.dgamma(), bn.dbeta(), act,
+                                                                              valid=valid, items=items)))
     return y
 
 
@@ -754,8 +757,9 @@ class _AlignerT:
 
 class _StyleTokensT:
     """The Global Style Token module in training (architecture and key names: ``everyvoice_amd.fs2.gst_state_dict_shapes``): the
-    utterance's own target mel is the style reference.  The module consumes the zero-padded batch tensor exactly as ``torch.nn`` would
-    (an unpinned choice, like the Conformer's BatchNorm): no length masking, BatchNorm statistics over every position.  fp32 in both
+    utterance's own target mel is the style reference.  Without ``lens`` the module consumes the zero-padded batch tensor exactly as
+    ``torch.nn`` would (an unpinned choice, like the Conformer's BatchNorm): no length masking, BatchNorm statistics over every position.
+    With ``lens`` (``model.gst_mask_padding``) frames beyond an item's length are absent in every layer.  fp32 in both
     precision modes; its weight gradients are issued in place (``ops.exact_f32``), every sum in a fixed order."""
 
     def __init__(self, g: ParamGroup, c):
@@ -802,12 +806,13 @@ class _StyleTokensT:
         tape.record(bwd)
         return y
 
-    def _conv(self, tape: Tape, x: Var, H: int, W: int, i_w: int, i_b: int, shape) -> Var:
-        """x [Cin, B, H * W] -> [Cout, B, OH * OW] (the BatchNorm's [C, B, columns] view of the channel-major tensor)."""
+    def _conv(self, tape: Tape, x: Var, H: int, W: int, i_w: int, i_b: int, shape, rows=None) -> Var:
+        """x [Cin, B, H * W] -> [Cout, B, OH * OW] (the BatchNorm's [C, B, columns] view of the channel-major tensor).  With ``rows`` the
+        backward is the unmasked one: x is zero at its invalid rows and so is dy (the masked BatchNorm's dx)."""
         g = self.group
         cin, B = x.data.shape[:2]
         w, dw, b, db = g.data(i_w).view(shape), g.gradient(i_w).view(shape), g.data(i_b), g.gradient(i_b)
-        y = Var(ops.gst_conv2d_fwd(x.data.view(cin, B, H, W), w, b).view(shape[0], B, -1))
+        y = Var(ops.gst_conv2d_fwd(x.data.view(cin, B, H, W), w, b, rows=rows).view(shape[0], B, -1))
 
         def bwd():
             if y.grad is None:
@@ -820,27 +825,35 @@ class _StyleTokensT:
         tape.record(bwd)
         return y
 
-    def forward(self, tape: Tape, mel: torch.Tensor) -> Var:
-        """mel [B, T, n_mels] (zero padded) -> style embeddings [B, E]."""
+    def forward(self, tape: Tape, mel: torch.Tensor, lens: torch.Tensor | None = None) -> Var:
+        """mel [B, T, n_mels] (zero padded) -> style embeddings [B, E].  ``lens`` (int32 [B] on the device): frames at or beyond lens[b]
+        are absent, whatever they hold; the per-layer lengths are integer ops on the device (no host sync: a replayed graph follows the
+        new batch's lengths)."""
         g = self.group
         B, H, W = mel.shape
+        rows = [None] * (len(self.convs) + 1)
+        if lens is not None:
+            rows = [lens] + ops.gst_valid_rows(lens, len(self.convs))
+            # layer 1's weight gradient reads its input unmasked: select the padding away once (a select, not a product: NaN stays out)
+            mel = torch.where(torch.arange(H, device=mel.device, dtype=torch.int32).view(1, H, 1) < lens.view(B, 1, 1), mel, 0.0)
         x = Var(mel.reshape(1, B, H * W), needs_grad=False)
-        for i_w, i_b, shape, bn in self.convs:
-            x = batchnorm(tape, self._conv(tape, x, H, W, i_w, i_b, shape), bn, ops.ACT_RELU)
+        for li, (i_w, i_b, shape, bn) in enumerate(self.convs):
+            y = self._conv(tape, x, H, W, i_w, i_b, shape, rows[li])
             H, W = ops.gst_conv_out(H), ops.gst_conv_out(W)
+            x = batchnorm(tape, y, bn, ops.ACT_RELU, valid=None if lens is None else rows[li + 1] * W, items=None if lens is None else B)
         C, T2 = x.data.shape[0], H
         # the GRU's input features, channel-major: row c * W + bin, one column per (item, step)
         seq = Var(x.data.view(C, B, T2, W).permute(0, 3, 1, 2).reshape(C * W, 1, B * T2))
         tape.record(lambda: seq.grad is not None and x.accumulate(seq.grad.view(C, W, B, T2).permute(0, 2, 3, 1).reshape(C, B, T2 * W)))
         gi = self._dense(tape, seq, self.ih)
         whh = self.hh.effective(True)[0].view(3 * self.H, self.H)
-        hlast, saved = ops.gst_gru_fwd(gi.data.view(-1, B, T2), whh, self.hh.bias_data(), save=not _EVAL[0])
+        hlast, saved = ops.gst_gru_fwd(gi.data.view(-1, B, T2), whh, self.hh.bias_data(), save=not _EVAL[0], steps=rows[-1])
         h = Var(hlast.view(self.H, 1, B))
 
         def gru_bwd():
             if h.grad is None:
                 return
-            dgi, dgh = ops.gst_gru_bwd(saved, whh, h.grad.reshape(self.H, B))
+            dgi, dgh = ops.gst_gru_bwd(saved, whh, h.grad.reshape(self.H, B), steps=rows[-1])
             with ops.exact_f32():  # dW_hh = dgh . hprev^T, db_hh = row sums of dgh: a dense layer's weight gradient
                 ops.conv1d_bwd(saved[2].view(self.H, 1, B * T2), whh.view(3 * self.H, self.H, 1), dgh.view(3 * self.H, 1, B * T2), 1, 0, 1, 1,
                                need_dx=False, dw_out=self.hh.effective(True)[1], db_out=self.hh.db_sink(), accumulate=True)
@@ -1266,7 +1279,7 @@ class FastSpeech2Trainer(CapturedStep):
             if table is not None:
                 x = add_item_embedding(st.tape, x, b[key], lens, table.data(), table.grad())
         if self.gst is not None:
-            style = self.gst.forward(st.tape, b["mel_btf"])
+            style = self.gst.forward(st.tape, b["mel_btf"], b["mel_lens"] if self.config.gst_mask_padding else None)
             x = add_item_embedding(st.tape, x, torch.arange(st.meta["B"], device=self.device, dtype=torch.int32), lens, style.data, style)
         return x
 

@@ -1222,19 +1222,39 @@ def layernorm_bwd(x, gamma, dy, dgamma, dbeta, eps=1e-5, acc_into=None):
     return dx
 
 
-def batchnorm_fwd(x, gamma, beta, running_mean, running_var, act=ACT_NONE, eps=1e-5, momentum=0.1):
+def batchnorm_fwd(x, gamma, beta, running_mean, running_var, act=ACT_NONE, eps=1e-5, momentum=0.1, valid=None, items=None):
+    """``valid`` (int32 [items] on the device; x's columns are ``items`` equal blocks): only the first valid[b] columns of item b count
+    towards the statistics, the others are not read and come out as zero."""
     C, N = x.shape[0], x.shape[1] * x.shape[2]
     y = torch.empty_like(x)
     mean = torch.empty(C, device=x.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
     # momentum < 0: evaluation mode (running statistics normalise and stay as they are)
+    if valid is not None:
+        B, T = _bn_items(valid, items, N)
+        _chk(_lib.load().evmi_batchnorm_fwd_valid_cbt_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                          _lib.ptr(running_mean), _lib.ptr(running_var), C, N, eps, momentum, act, valid.data_ptr(), B, T,
+                                                          _s(x)), "evmi_batchnorm_fwd_valid_cbt_f32")
+        return y, mean, rstd
     _chk(_lib.load().evmi_batchnorm_fwd_cbt_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                                 _lib.ptr(running_mean), _lib.ptr(running_var), C, N, eps, momentum, act, _s(x)), "evmi_batchnorm_fwd_cbt_f32")
     return y, mean, rstd
 
 
-def batchnorm_bwd(x, gamma, beta, mean, rstd, dy, dgamma, dbeta, act=ACT_NONE):
+def _bn_items(valid, items, N):
+    if items is None or items < 1 or N % items or valid.dtype != torch.int32 or valid.numel() != items or not valid.is_contiguous():
+        raise ValueError(f"batchnorm: `valid` must be a contiguous int32 [items] and `items` ({items}) must divide the {N} columns")
+    return items, N // items
+
+
+def batchnorm_bwd(x, gamma, beta, mean, rstd, dy, dgamma, dbeta, act=ACT_NONE, valid=None, items=None):
     dx = torch.empty_like(x)
+    if valid is not None:  # dy at the invalid columns is ignored, dx there is zero
+        B, T = _bn_items(valid, items, x.shape[1] * x.shape[2])
+        _chk(_lib.load().evmi_batchnorm_bwd_valid_cbt_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dy.data_ptr(),
+                                                          dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), x.shape[0], B * T, act, valid.data_ptr(), B, T,
+                                                          _s(x)), "evmi_batchnorm_bwd_valid_cbt_f32")
+        return dx
     _chk(_lib.load().evmi_batchnorm_bwd_cbt_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dy.data_ptr(),
                                                 dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), x.shape[0], x.shape[1] * x.shape[2], act, _s(x)),
          "evmi_batchnorm_bwd_cbt_f32")
@@ -1396,13 +1416,33 @@ def gst_conv_out(n: int) -> int:
     return (n - 1) // 2 + 1
 
 
-def gst_conv2d_fwd(x, w, bias, act=ACT_NONE):
-    """x [Cin, B, H, W], w [Cout, Cin, 3, 3] -> y [Cout, B, OH, OW]; act: ACT_NONE or ACT_RELU (inference: folded BatchNorm + ReLU)."""
+def gst_valid_rows(lens, n_layers: int):
+    """The valid frame count after each of ``n_layers`` reference-encoder layers: a list of n_layers tensors shaped and typed like
+    ``lens`` (integer; on its device, without a host sync), entry i = gst_conv_out applied i + 1 times.  n -> (n - 1) // 2 + 1 halves
+    n - 1 each time, so layer i is ((n - 1) >> (i + 1)) + 1: all layers in three launches."""
+    shifts = torch.arange(1, n_layers + 1, device=lens.device, dtype=lens.dtype).view(-1, 1)
+    return list(torch.bitwise_right_shift((lens - 1).view(1, -1), shifts).add_(1).view(n_layers, *lens.shape).unbind(0))
+
+
+def _lens_arg(lens, B, what):
+    if lens.dtype != torch.int32 or lens.numel() != B or not lens.is_contiguous():
+        raise ValueError(f"{what}: the lengths must be a contiguous int32 [{B}] on the device, got {lens.dtype} {tuple(lens.shape)}")
+    return lens.data_ptr()
+
+
+def gst_conv2d_fwd(x, w, bias, act=ACT_NONE, rows=None):
+    """x [Cin, B, H, W], w [Cout, Cin, 3, 3] -> y [Cout, B, OH, OW]; act: ACT_NONE or ACT_RELU (inference: folded BatchNorm + ReLU).
+    ``rows`` (int32 [B] on the device): item b has rows[b] valid input rows; later ones are not read and its output rows beyond
+    gst_conv_out(rows[b]) are zero."""
     cin, B, H, W = x.shape
     cout = w.shape[0]
     y = torch.empty(cout, B, gst_conv_out(H), gst_conv_out(W), device=x.device, dtype=torch.float32)
-    _chk(_lib.load().evmi_gst_conv2d_fwd_f32(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), y.data_ptr(), cin, cout, B, H, W, act, _s(x)),
-         "evmi_gst_conv2d_fwd_f32")
+    if rows is not None:
+        _chk(_lib.load().evmi_gst_conv2d_fwd_rows_f32(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), y.data_ptr(), _lens_arg(rows, B, "gst_conv2d_fwd"), cin,
+                                                      cout, B, H, W, act, _s(x)), "evmi_gst_conv2d_fwd_rows_f32")
+    else:
+        _chk(_lib.load().evmi_gst_conv2d_fwd_f32(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), y.data_ptr(), cin, cout, B, H, W, act, _s(x)),
+             "evmi_gst_conv2d_fwd_f32")
     _FLOPS[0] += 2.0 * y.numel() * cin * 9
     return y
 
@@ -1429,26 +1469,37 @@ def gst_conv2d_wgrad(x, dy, dw, db, accumulate=True):
     _FLOPS[0] += 2.0 * dy.numel() * cin * 9
 
 
-def gst_gru_fwd(gi, whh, bhh, save=True):
-    """gi [3H, B, T] (x W_ih^T + b_ih of every step) -> (last hidden state [H, B], what the backward needs or None)."""
+def gst_gru_fwd(gi, whh, bhh, save=True, steps=None):
+    """gi [3H, B, T] (x W_ih^T + b_ih of every step) -> (last hidden state [H, B], what the backward needs or None).  ``steps`` (int32 [B]
+    on the device): item b runs steps[b] steps; the saved tensors are zero beyond them."""
     H3, B, T = gi.shape
     H = H3 // 3
     dev = gi.device
     hlast = torch.empty(H, B, device=dev, dtype=torch.float32)
     saved = (torch.empty(H3, B, T, device=dev, dtype=torch.float32), torch.empty(H, B, T, device=dev, dtype=torch.float32),
              torch.empty(H, B, T, device=dev, dtype=torch.float32)) if save else None
-    _chk(_lib.load().evmi_gst_gru_fwd_f32(gi.data_ptr(), whh.data_ptr(), bhh.data_ptr(), *([t.data_ptr() for t in saved] if save else [0, 0, 0]),
-                                          hlast.data_ptr(), B, T, H, _s(gi)), "evmi_gst_gru_fwd_f32")
+    ptrs = [t.data_ptr() for t in saved] if save else [0, 0, 0]
+    if steps is not None:
+        _chk(_lib.load().evmi_gst_gru_fwd_steps_f32(gi.data_ptr(), whh.data_ptr(), bhh.data_ptr(), *ptrs, hlast.data_ptr(), _lens_arg(steps, B, "gst_gru_fwd"),
+                                                    B, T, H, _s(gi)), "evmi_gst_gru_fwd_steps_f32")
+    else:
+        _chk(_lib.load().evmi_gst_gru_fwd_f32(gi.data_ptr(), whh.data_ptr(), bhh.data_ptr(), *ptrs, hlast.data_ptr(), B, T, H, _s(gi)),
+             "evmi_gst_gru_fwd_f32")
     return hlast, saved
 
 
-def gst_gru_bwd(saved, whh, dhlast):
-    """-> (dgi [3H, B, T], dgh [3H, B, T]); saved[2] is hprev [H, B, T]: dW_hh = dgh . hprev^T, db_hh = row sums of dgh."""
+def gst_gru_bwd(saved, whh, dhlast, steps=None):
+    """-> (dgi [3H, B, T], dgh [3H, B, T]); saved[2] is hprev [H, B, T]: dW_hh = dgh . hprev^T, db_hh = row sums of dgh.  ``steps``: as
+    given to the forward; dgi / dgh are zero beyond them."""
     rzn, hn, hprev = saved
     H3, B, T = rzn.shape
     dgi, dgh = torch.empty_like(rzn), torch.empty_like(rzn)
-    _chk(_lib.load().evmi_gst_gru_bwd_f32(rzn.data_ptr(), hn.data_ptr(), hprev.data_ptr(), whh.data_ptr(), dhlast.data_ptr(), dgi.data_ptr(),
-                                          dgh.data_ptr(), B, T, H3 // 3, _s(rzn)), "evmi_gst_gru_bwd_f32")
+    if steps is not None:
+        _chk(_lib.load().evmi_gst_gru_bwd_steps_f32(rzn.data_ptr(), hn.data_ptr(), hprev.data_ptr(), whh.data_ptr(), dhlast.data_ptr(), dgi.data_ptr(),
+                                                    dgh.data_ptr(), _lens_arg(steps, B, "gst_gru_bwd"), B, T, H3 // 3, _s(rzn)), "evmi_gst_gru_bwd_steps_f32")
+    else:
+        _chk(_lib.load().evmi_gst_gru_bwd_f32(rzn.data_ptr(), hn.data_ptr(), hprev.data_ptr(), whh.data_ptr(), dhlast.data_ptr(), dgi.data_ptr(),
+                                              dgh.data_ptr(), B, T, H3 // 3, _s(rzn)), "evmi_gst_gru_bwd_f32")
     return dgi, dgh
 
 

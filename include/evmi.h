@@ -893,6 +893,18 @@ int evmi_batchnorm_fwd_cbt_f32(const float* x_dev, const float* gamma_dev, const
 int evmi_batchnorm_bwd_cbt_f32(const float* x_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev,
                                const float* rstd_dev, const float* dy_dev, float* dx_dev, float* dgamma_dev,
                                float* dbeta_dev, int C, long long n_cols, int act, void* stream);
+/* The pair above over the valid prefix of every item: n_cols = B * T, item b owns columns b T .. b T + T - 1 of every channel row and
+ * its first valid[b] (int32 [B] in device memory, clamped to [0, T]) columns count.  Statistics, running statistics (unbiased over the
+ * valid count) and gradient sums run over the valid columns only; invalid columns of x and dy are never read and y / dx there are
+ * written as zero.  One workgroup per channel, fixed-order sums. */
+int evmi_batchnorm_fwd_valid_cbt_f32(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev,
+                                     float* mean_dev, float* rstd_dev, float* running_mean_dev, float* running_var_dev,
+                                     int C, long long n_cols, float eps, float momentum, int act, const int* valid_dev, int B,
+                                     int T, void* stream);
+int evmi_batchnorm_bwd_valid_cbt_f32(const float* x_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev,
+                                     const float* rstd_dev, const float* dy_dev, float* dx_dev, float* dgamma_dev,
+                                     float* dbeta_dev, int C, long long n_cols, int act, const int* valid_dev, int B, int T,
+                                     void* stream);
 /* Depthwise convolution backward: dx (NULL = skip), dw [C][k] += ..., db [C] += ... (dw NULL = skip both; otherwise
  * ws: evmi_dwconv1d_bwd_cbt_f32_ws_elems floats of per-(channel, item) partial sums, reduced in a fixed order). */
 long long evmi_dwconv1d_bwd_cbt_f32_ws_elems(int C, int B, int k);
@@ -1000,6 +1012,11 @@ int evmi_align_qk_grad_f32(const float* x_dev, const float* sums_dev, float* m_d
  * BatchNorm + ReLU of inference).  H, W are the INPUT sizes in all three entry points. */
 int evmi_gst_conv2d_fwd_f32(const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, int Cin, int Cout,
                             int B, int H, int W, int act, void* stream);
+/* The forward with per-item frame counts rows_in [B] (int32, device memory, clamped to [0, H]): input rows at or beyond rows_in[b] are
+ * absent (never read, whatever they hold), output rows at or beyond (rows_in[b] - 1) / 2 + 1 are written as zero.  With
+ * rows_in[b] == H for every item the result is bit-equal to evmi_gst_conv2d_fwd_f32. */
+int evmi_gst_conv2d_fwd_rows_f32(const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev,
+                                 const int* rows_in_dev, int Cin, int Cout, int B, int H, int W, int act, void* stream);
 /* dx [Cin][B][H][W] = the input gradient of dy [Cout][B][OH][OW] (written, not accumulated). */
 int evmi_gst_conv2d_dgrad_f32(const float* dy_dev, const float* w_dev, float* dx_dev, int Cin, int Cout, int B, int H, int W,
                               void* stream);
@@ -1017,6 +1034,14 @@ int evmi_gst_gru_fwd_f32(const float* gi_dev, const float* whh_dev, const float*
  * (gradient of W_hh h + b_hh: dW_hh = dgh . hprev^T and db_hh = its row sums, a dense layer's weight gradient). */
 int evmi_gst_gru_bwd_f32(const float* rzn_dev, const float* hn_dev, const float* hprev_dev, const float* whh_dev,
                          const float* dhlast_dev, float* dgi_dev, float* dgh_dev, int B, int T, int H, void* stream);
+/* The recurrence and its backward with per-item step counts steps [B] (int32, device memory, clamped to [1, T]): item b runs steps[b]
+ * steps, hlast is its state after the last of them, gi beyond is never read, and rzn / hn / hprev / dgi / dgh are zero at later steps.
+ * With steps[b] == T for every item the results are bit-equal to the pair above. */
+int evmi_gst_gru_fwd_steps_f32(const float* gi_dev, const float* whh_dev, const float* bhh_dev, float* rzn_dev, float* hn_dev,
+                               float* hprev_dev, float* hlast_dev, const int* steps_dev, int B, int T, int H, void* stream);
+int evmi_gst_gru_bwd_steps_f32(const float* rzn_dev, const float* hn_dev, const float* hprev_dev, const float* whh_dev,
+                               const float* dhlast_dev, float* dgi_dev, float* dgh_dev, const int* steps_dev, int B, int T, int H,
+                               void* stream);
 /* Style-token attention: one query per item q [E][B] against keys / values [E][N] (N <= 16 tokens), `heads` heads of E / heads,
  * scores q.k / sqrt(E / heads), softmax over the tokens -> style [B][E]; probs [B][heads][N] (or NULL) is saved for the backward. */
 int evmi_gst_attention_fwd_f32(const float* q_dev, const float* keys_dev, const float* values_dev, float* style_dev,
