@@ -379,12 +379,7 @@ static int prepare_tc(evmi_generator* g) {
           warena.resize(warena.size() + 2 * (size_t)cc * cc * k);
           for (int which = 1; which <= 2; ++which) {
             const float* w = g->host_w[rb_name(c, n, which, m, "weight")].data();
-            uint16_t* dst = &warena[off + (size_t)(which - 1) * cc * cc * k];
-            for (int mo = 0; mo < cc; ++mo)
-              for (int ci = 0; ci < cc; ++ci)
-                for (int jt = 0; jt < k; ++jt)
-                  dst[((((size_t)(ci / pl->kc)) * k + jt) * cc + mo) * pl->kc + ci % pl->kc] =
-                      f32_to_bf16_bits(w[((size_t)mo * cc + ci) * k + jt]);  // [chunk][tap][C][kc]
+            relayout_resblock_pair(w, cc, k, pl->kc, &warena[off + (size_t)(which - 1) * cc * cc * k]);  // [chunk][tap][C][kc]
           }
         }
         pair_w.push_back(off);

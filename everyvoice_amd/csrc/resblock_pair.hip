@@ -47,6 +47,13 @@ const PairLaunch* find_resblock_pair(int c, int ks, int dil) {
   return nullptr;
 }
 
+void relayout_resblock_pair(const float* w, int c, int ks, int kc, uint16_t* dst) {
+  for (int mo = 0; mo < c; ++mo)
+    for (int ci = 0; ci < c; ++ci)
+      for (int jt = 0; jt < ks; ++jt)
+        dst[((((size_t)(ci / kc)) * ks + jt) * c + mo) * kc + ci % kc] = f32_to_bf16_bits(w[((size_t)mo * c + ci) * ks + jt]);
+}
+
 int launch_resblock_pair(const PairLaunch* L, PairArgs a, int B, int n_cu, hipStream_t stream) {
   a.tiles_per_item = (a.T + L->tt - 1) / L->tt;
   a.n_tiles = a.tiles_per_item * B;
@@ -115,3 +122,108 @@ int launch_resblock_branch(const BranchLaunch* L, BranchArgs a, int B, int n_cu,
 }
 
 }  // namespace evmi
+
+// ---- one pair, one branch alone (include/evmi.h) -------------------------------------------------------------------------------------------
+using namespace evmi;
+
+namespace {
+
+// n_cu of the entry points: 0 = the current device's compute units, a positive value as given
+int resolve_n_cu(int n_cu, int* out) {
+  if (n_cu > 0) { *out = n_cu; return EVMI_OK; }
+  int dev = 0, cu = 0;
+  EVMI_HIP_CHECK(hipGetDevice(&dev));
+  EVMI_HIP_CHECK(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
+  *out = cu > 0 ? cu : 256;
+  return EVMI_OK;
+}
+
+// what both entry points refuse before any launch
+int fused_refusal(const char* who, const void* x, const void* out, int B, int T, int C, int n_cu) {
+  if (B <= 0 || T <= 0 || n_cu < 0) return fail(EVMI_ERR_INVALID_ARG, std::string(who) + ": B and T must be positive, n_cu >= 0");
+  if ((long long)T * C >= (1LL << 30)) return fail(EVMI_ERR_UNSUPPORTED, std::string(who) + ": an item of 2^30 elements or more");
+  const char* xb = static_cast<const char*>(x);
+  const char* ob = static_cast<const char*>(out);
+  const long long bytes = 2LL * B * T * C;
+  if (xb < ob + bytes && ob < xb + bytes) return fail(EVMI_ERR_INVALID_ARG, std::string(who) + ": x and out overlap (a tile reads the halo rows of its neighbours)");
+  return EVMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int evmi_resblock_pair_plan(int C, int ks, int dil, int* tt, int* bn, int* kc, long long* weight_elems) {
+  const PairLaunch* L = (C > 0 && ks > 0 && dil >= 1) ? find_resblock_pair(C, ks, dil) : nullptr;
+  if (tt) *tt = L ? L->tt : 0;
+  if (bn) *bn = L ? L->bn : 0;
+  if (kc) *kc = L ? L->kc : 0;
+  if (weight_elems) *weight_elems = L ? (long long)C * C * ks : 0;
+  return L ? 1 : 0;
+}
+
+int evmi_resblock_branch_plan(int C, int ks, int np, const int* dil, int* tt, int* bn) {
+  const BranchLaunch* L = (C > 0 && ks > 0 && dil) ? find_resblock_branch(C, ks, np, dil) : nullptr;
+  if (tt) *tt = L ? branch_valid_rows(*L, np, dil) : 0;
+  if (bn) *bn = L ? L->bn : 0;
+  return L ? 1 : 0;
+}
+
+int evmi_resblock_pair_relayout_f32(const float* w_host, void* dst_bf16_host, int C, int ks, int kc) {
+  if (!w_host || !dst_bf16_host) return fail(EVMI_ERR_INVALID_ARG, "resblock_pair_relayout: null pointer");
+  if (C <= 0 || ks <= 0 || kc <= 0 || C % kc) return fail(EVMI_ERR_INVALID_ARG, "resblock_pair_relayout: kc must divide C");
+  relayout_resblock_pair(w_host, C, ks, kc, static_cast<uint16_t*>(dst_bf16_host));
+  return EVMI_OK;
+}
+
+int evmi_resblock_pair_bf16(const void* x, const void* w1_laid, const float* b1_dev, const void* w2_laid, const float* b2_dev, void* out, int B,
+                            int T, int C, int ks, int dil, float slope, float post_slope, float out_scale, int accumulate, int n_cu, void* stream) {
+  if (!x || !w1_laid || !b1_dev || !w2_laid || !b2_dev || !out) return fail(EVMI_ERR_INVALID_ARG, "resblock_pair: null pointer");
+  const PairLaunch* L = (C > 0 && ks > 0 && dil >= 1) ? find_resblock_pair(C, ks, dil) : nullptr;
+  if (!L) return fail(EVMI_ERR_UNSUPPORTED, "resblock_pair: no fused kernel for c=" + std::to_string(C) + " k=" + std::to_string(ks) + " dil=" + std::to_string(dil));
+  if (int rc = fused_refusal("resblock_pair", x, out, B, T, C, n_cu)) return rc;
+  if (int rc = resolve_n_cu(n_cu, &n_cu)) return rc;
+  PairArgs pa;
+  pa.x = reinterpret_cast<const bf16_t*>(x);
+  pa.w1 = reinterpret_cast<const bf16_t*>(w1_laid);
+  pa.w2 = reinterpret_cast<const bf16_t*>(w2_laid);
+  pa.b1 = b1_dev;
+  pa.b2 = b2_dev;
+  pa.out = reinterpret_cast<bf16_t*>(out);
+  pa.T = T;
+  pa.dil1 = dil;
+  pa.slope = slope;
+  pa.post_slope = post_slope;
+  pa.out_scale = out_scale;
+  pa.accumulate = accumulate ? 1 : 0;
+  pa.timeline = nullptr;
+  return launch_resblock_pair(L, pa, B, n_cu, (hipStream_t)stream);
+}
+
+int evmi_resblock_branch_bf16(const void* x, const void* const* w_laid, const float* const* bias_dev, void* out, int B, int T, int C, int ks, int np,
+                              const int* dil, float slope, float post_slope, float out_scale, int accumulate, int n_cu, void* stream) {
+  if (!x || !w_laid || !bias_dev || !out || !dil) return fail(EVMI_ERR_INVALID_ARG, "resblock_branch: null pointer");
+  const BranchLaunch* L = (C > 0 && ks > 0) ? find_resblock_branch(C, ks, np, dil) : nullptr;
+  if (!L) return fail(EVMI_ERR_UNSUPPORTED, "resblock_branch: no fused kernel for c=" + std::to_string(C) + " k=" + std::to_string(ks) + " np=" + std::to_string(np) + " with these dilations");
+  for (int i = 0; i < 2 * np; ++i)
+    if (!w_laid[i] || !bias_dev[i]) return fail(EVMI_ERR_INVALID_ARG, "resblock_branch: null pointer");
+  if (int rc = fused_refusal("resblock_branch", x, out, B, T, C, n_cu)) return rc;
+  if (int rc = resolve_n_cu(n_cu, &n_cu)) return rc;
+  BranchArgs ba;
+  ba.x = reinterpret_cast<const bf16_t*>(x);
+  ba.out = reinterpret_cast<bf16_t*>(out);
+  for (int i = 0; i < 6; ++i) {
+    ba.w[i] = reinterpret_cast<const bf16_t*>(w_laid[i]);
+    ba.b[i] = bias_dev[i];
+  }
+  for (int p = 0; p < 3; ++p) ba.dil[p] = dil[p];
+  ba.T = T;
+  ba.np = np;
+  ba.slope = slope;
+  ba.post_slope = post_slope;
+  ba.out_scale = out_scale;
+  ba.accumulate = accumulate ? 1 : 0;
+  return launch_resblock_branch(L, ba, B, n_cu, (hipStream_t)stream);
+}
+
+}  // extern "C"

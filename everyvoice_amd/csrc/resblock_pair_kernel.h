@@ -347,6 +347,9 @@ static PairLaunch make_pair_launch(const char* name) {
 }
 
 const PairLaunch* find_resblock_pair(int c, int ks, int dil);
+// w fp32 [c][c][ks] (torch: [out][in][tap]) -> the bf16 image [chunk][tap][c][kc] both pair kernels and the branch kernel stream
+// (kc = PairLaunch::kc; kc == c: the plain tap-major [ks][c][c]).  Host memory on both sides; dst holds c * c * ks elements.
+void relayout_resblock_pair(const float* w, int c, int ks, int kc, uint16_t* dst);
 int launch_resblock_pair(const PairLaunch* L, PairArgs a, int B, int n_cu, hipStream_t stream);
 
 }  // namespace evmi

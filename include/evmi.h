@@ -475,6 +475,35 @@ int evmi_conv_generic_relayout_f32(const float* w_dev, void* dst_bf16_dev, int c
 int evmi_conv_generic_bf16(const void* x, const void* w_laid, const float* bias_dev, const void* res, void* out, int B, int t_in, int n_rows,
                            int c_in, int c_out, int ks, int dil, int pad, long long out_row_stride, long long out_shift, long long out_limit,
                            float pre_slope, float post_slope, float out_scale, int accumulate, void* stream);
+/* ---- The fused residual kernels alone (csrc/resblock_pair.hip): one pair, or one whole branch, of a HiFiGAN ResBlock1 (upstream
+ * jik876 hifi-gan models.py ResBlock1) as evmi_generator_forward launches them in bf16, for layer-level tests.
+ *   pair:    out = post( [accumulate ? out : 0] + out_scale * ( x + b2 + conv2( lrelu( b1 + conv1_dil( lrelu(x) ) ) ) ) )
+ *   branch:  y0 = x;  y(p+1) = y(p) + b2p + conv2p( lrelu( b1p + conv1p_dil(dp)( lrelu(y(p)) ) ) );  out = post( [out +] out_scale * y(3) )
+ * x, out: bf16 [B][T][C], distinct and not overlapping (a tile reads its neighbours' halo rows of x after they may have been stored).
+ * Both convolutions are C -> C with ks taps and "same" zero padding: every stage reads zero outside [0, T).  lrelu uses `slope`, post
+ * is a leaky ReLU with post_slope (1 = none).  The intermediate, y(p) between two pairs and out are rounded to bf16; sums are fp32.
+ *   evmi_resblock_pair_plan          1 when a fused kernel takes (C, ks, dil), else 0.  *tt: output rows a tile stores, *bn: rows a
+ *                                    tile computes, *kc: channel chunk of the weight image, *weight_elems: bf16 elements of one
+ *                                    convolution's image (all 0 when not taken; any output pointer may be NULL).  Host arithmetic.
+ *   evmi_resblock_branch_plan        the same for a branch of np pairs with dilations dil[0 .. np): only np = 3, and only where the
+ *                                    recomputed halo stays within 25 % of the tile (4 * tt >= 3 * bn).  Host arithmetic.
+ *   evmi_resblock_pair_relayout_f32  w fp32 [C][C][ks] (torch: [out][in][tap]) -> the bf16 image [chunk][tap][C][kc] the kernels stream
+ *                                    (kc from the pair plan; the branch kernels take kc = C).  HOST memory on both sides, no GPU call:
+ *                                    the function evmi_generator_finalize itself calls.
+ *   evmi_resblock_pair_bf16          one pair.  w1_laid / w2_laid: device copies of that image (16-byte aligned), b1 / b2: fp32 [C].
+ *   evmi_resblock_branch_bf16        one branch.  w_laid[6], bias_dev[6]: conv1, conv2 of pair 0, 1, 2 (host arrays of device pointers).
+ *   n_cu: workgroups of the persistent grid (rounded up to a multiple of 8, at most one per tile); 0 = the device's compute units.
+ * Refused before any launch -- EVMI_ERR_INVALID_ARG: a null pointer, B < 1, T < 1, n_cu < 0, x and out overlapping;
+ * EVMI_ERR_UNSUPPORTED: a shape the kernel tables do not hold (evmi_*_plan returns 0), T * C >= 2^30.
+ * The process-wide A/B switches EVMI_PAIR_C128=0 and EVMI_BRANCH=0 are read once, inside the table lookups: under them the plans
+ * return 0 and the entry points answer EVMI_ERR_UNSUPPORTED for the 128-channel pair / for every branch. */
+int evmi_resblock_pair_plan(int C, int ks, int dil, int* tt, int* bn, int* kc, long long* weight_elems);
+int evmi_resblock_branch_plan(int C, int ks, int np, const int* dil, int* tt, int* bn);
+int evmi_resblock_pair_relayout_f32(const float* w_host, void* dst_bf16_host, int C, int ks, int kc);
+int evmi_resblock_pair_bf16(const void* x, const void* w1_laid, const float* b1_dev, const void* w2_laid, const float* b2_dev, void* out, int B,
+                            int T, int C, int ks, int dil, float slope, float post_slope, float out_scale, int accumulate, int n_cu, void* stream);
+int evmi_resblock_branch_bf16(const void* x, const void* const* w_laid, const float* const* bias_dev, void* out, int B, int T, int C, int ks, int np,
+                              const int* dil, float slope, float post_slope, float out_scale, int accumulate, int n_cu, void* stream);
 /* ---- The iSTFTNet output head alone (csrc/istft_head.hip: the specialised kernel; csrc/istft_head_generic.hip: any size):
  * reflection pad (1, 0) -> conv_post (C -> n_fft + 2, k 7) -> exp / sin -> torch.istft(mag * e^{i phi}, n_fft, hop, n_fft, periodic
  * hann, center = True).  The logits stay fp32 from the MFMA accumulators to the waveform.
