@@ -222,7 +222,11 @@ def test_generic_dropout_matches_torch_with_the_same_mask(cuda_device):
     dev = cuda_device
     qkv = torch.randn(B, 3 * D, T, generator=g, requires_grad=True)
     lens = torch.tensor([T, T - 7])
-    keep = _keep_mask(dev, B, H, T, p, seed)
+    import dropout_ref
+
+    keep = torch.from_numpy(dropout_ref.attention_keep(seed, B, H, T, p)).to(torch.float32)  # the generator restated on the host
+    read_back = _keep_mask(dev, B, H, T, p, seed)
+    assert keep.shape == read_back.shape and torch.equal(keep, read_back.to(torch.float32))  # ... is evmi_dropout_f32's stream, bit for bit
     assert abs(float(keep.mean()) - (1 - p)) < 0.03
     o = _attention_ref(qkv, lens, H, keep, p)
     do = torch.randn(B, D, T, generator=g)

@@ -198,8 +198,12 @@ def test_attention_dropout_matches_torch_with_the_same_mask(cuda_device):
     dev = cuda_device
     qkv = torch.randn(B, 3 * D, T, generator=g, requires_grad=True)
     lens = torch.tensor([T, T - 7])
+    import dropout_ref
+
+    keep = torch.from_numpy(dropout_ref.attention_keep(seed, B, H, T, p)).float()  # [B, H, Tq, Tk]: the generator restated on the host
     ones = torch.ones(B * T * T, device=dev)
-    keep = torch.stack([(ops.dropout(ones, p, seed + h) > 0).float().view(B, T, T) for h in range(H)], dim=1).cpu()  # [B, H, Tq, Tk]
+    read_back = torch.stack([(ops.dropout(ones, p, seed + h) > 0).float().view(B, T, T) for h in range(H)], dim=1).cpu()
+    assert torch.equal(keep, read_back)  # ... is the stream evmi_dropout_f32 draws from, bit for bit
     assert abs(float(keep.mean()) - (1 - p)) < 0.03
     o = _attention_ref(qkv, lens, H, keep, p)
     do = torch.randn(B, D, T, generator=g)
@@ -230,6 +234,9 @@ def test_glu_silu_relu_dropout(cuda_device):
     x = torch.randn(100000, generator=g).to(dev)
     y = ops.dropout(x, 0.25, 7)
     kept = y != 0
+    import dropout_ref
+
+    assert torch.equal(kept.cpu(), torch.from_numpy(dropout_ref.keep_mask(7, x.numel(), 0.25)) & (x.cpu() != 0))  # the generator restated on the host
     assert abs(float(kept.float().mean()) - 0.75) < 0.01
     _close(y[kept].cpu(), (x[kept] / 0.75).cpu(), 1e-6)
     assert torch.equal(y, ops.dropout(x, 0.25, 7)) and not torch.equal(y, ops.dropout(x, 0.25, 8))
