@@ -14,6 +14,8 @@ _HERE = Path(__file__).resolve().parent
 LIB_NAME = "libevmi_hip.so"
 
 EVMI_OK = 0
+EVMI_ERR_INVALID_ARG = 1
+EVMI_ERR_NOT_READY = 3
 EVMI_ERR_UNSUPPORTED = 4
 EVMI_PREC_BF16 = 0
 EVMI_PREC_F32 = 1
@@ -319,6 +321,11 @@ SYMBOLS = {
     "evmi_generator_forward_profiled": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(LaunchRecord), C.c_int, C.POINTER(C.c_int)],
+    ),
+    "evmi_generator_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "evmi_generator_forward_lens_profiled": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(LaunchRecord), C.c_int, C.POINTER(C.c_int)],
     ),
     "evmi_generator_macs_per_sample": (C.c_double, [C.c_void_p]),
 }

@@ -94,6 +94,22 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// Ragged batches.  The launch-wide extent of a layer stays the item stride and the upper bound; the VALID extent of item b is
+// rows_per_frame * clamp(frames[b], 0, frames_max) rows, read from device memory (a captured graph follows each batch).  The clamp is
+// part of the kernel: no value in frames[] makes a kernel address memory outside its item.  frames == nullptr: every item has the
+// launch-wide extent and the kernels do what they did before the field existed.
+struct ItemLens {
+  const int* frames = nullptr;  // [B] mel frames per item
+  int frames_max = 0;           // T of the forward
+  int rows_per_frame = 0;       // rows of this layer's sequence per mel frame
+};
+// valid rows of item b (b wave-uniform: one scalar load per tile, the result lives in an SGPR); full: the launch-wide extent
+__device__ __forceinline__ int item_rows(const ItemLens& l, int b, int full) {
+  if (!l.frames) return full;
+  const int f = l.frames[b];
+  return __builtin_amdgcn_readfirstlane(min(max(f, 0), l.frames_max) * l.rows_per_frame);
+}
+
 // Accumulator layout <-> 16 contiguous bytes per lane.  After a 32 x 32 MFMA chain lane (n, h) holds, for every register quad q,
 // channels 8q + 4h .. + 3 of row n.  With d = (two packed-bf16 dwords of quad 2p | two of quad 2p + 1), one v_permlane32_swap per
 // dword pair leaves lane (n, 0) with channels 16p .. 16p + 7 and lane (n, 1) with 16p + 8 .. 16p + 15 of the row.  The exchange is

@@ -85,6 +85,9 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
   const int b = blockIdx.y;
   const int mtile = blockIdx.z;
   const int m0 = mtile * C::BM;
+  int t_in, n_rows;  // of this item (ragged batch: its own, conv_tc_mfma.h)
+  long long out_limit;
+  if (!conv_item_extents(a, b, r0, t_in, n_rows, out_limit)) return;
 
   const bf16_t* __restrict__ xb = a.x + (long long)b * a.x_batch_stride;
   // pre-swizzled LDS images [mtile][chunk][tap][BM rows][8 slots] (relayout_conv, layout 1)
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
   auto vec_index = [&](int nt, int co) -> long long {
     const int r = r0 + wn * (C::NT * 32) + nt * 32 + (lane & 31);
     const long long f = (long long)r * a.out_row_stride + m0 + wm * (C::MT * 32) + 8 * h + a.out_shift + co;
-    return (r < a.n_rows && f >= 0 && f + 8 <= a.out_limit) ? f : -1;
+    return (r < n_rows && f >= 0 && f + 8 <= out_limit) ? f : -1;
   };
   auto swap_quads = [](u32x4 d) -> u32x4 { return M16 ? swap_quads16_bf16(d) : swap_quads_bf16(d); };
 
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
       const int row = p * 8 + (lane >> 3);
       const int rr = r0 - a.pad + row;
       const int c8 = slot ^ (M16 ? mfma16::x_swizzle(row) : (row >> 1) & 7);  // the swizzle belongs to the shape that reads the tile
-      const bf16_t* src = (row < rows_needed && rr >= 0 && rr < a.t_in) ? xb + (long long)rr * C::CIN + chunk * C::KC + c8 * 8
+      const bf16_t* src = (row < rows_needed && rr >= 0 && rr < t_in) ? xb + (long long)rr * C::CIN + chunk * C::KC + c8 * 8
                                                                         : g_conv_dma_zero_row + slot * 8;
       lds_dma_b128(src, Xs + p * 1024);
     }
@@ -353,7 +356,7 @@ __global__ __launch_bounds__(C::NTHREADS, 4) void conv_tc_dma_kernel(ConvTcArgs 
       const int n = v / VPR, c8 = v % VPR;
       const int r = r0 + n;
       const long long flat = (long long)r * a.out_row_stride + m0 + c8 * 8 + a.out_shift;
-      return (r >= a.n_rows || flat < 0 || flat >= a.out_limit) ? -1 : flat;
+      return (r >= n_rows || flat < 0 || flat >= out_limit) ? -1 : flat;
     };
     // residual / running-sum rows of a batch are requested before the first is consumed; unconditional loads and separate
     // straight-line bodies per case (conditions around the loads make the compiler drain the memory counter at every join)

@@ -41,6 +41,9 @@ __global__ __launch_bounds__(G::NTHREADS, 2) void conv_tc_generic_kernel(ConvTcA
   const int b = blockIdx.y;
   const int mtile = blockIdx.z;
   const int m0 = mtile * G::BM;
+  int t_in, n_rows;  // of this item (ragged batch: its own, conv_tc_mfma.h)
+  long long out_limit;
+  if (!conv_item_extents(a, b, r0, t_in, n_rows, out_limit)) return;
   const int nchunk = (c_in + G::KC - 1) / G::KC;
   const int ngroup = (ks + G::TAPS - 1) / G::TAPS;
   const int nstep = nchunk * ngroup;
@@ -97,7 +100,7 @@ __global__ __launch_bounds__(G::NTHREADS, 2) void conv_tc_generic_kernel(ConvTcA
         bf16x8 val;
 #pragma unroll
         for (int e = 0; e < 8; ++e) val[e] = (bf16_t)0.f;
-        if (v < x_nvec && c < c_in && rr >= 0 && rr < a.t_in) val = *reinterpret_cast<const bf16x8*>(xb + (long long)rr * c_in + c);
+        if (v < x_nvec && c < c_in && rr >= 0 && rr < t_in) val = *reinterpret_cast<const bf16x8*>(xb + (long long)rr * c_in + c);
         xv[i] = val;
       }
 #pragma unroll
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(G::NTHREADS, 2) void conv_tc_generic_kernel(ConvTcA
       const int n = v / VPR, c8 = v % VPR;
       const int r = r0 + n;
       const long long flat = (long long)r * a.out_row_stride + m0 + c8 * 8 + a.out_shift;
-      return (r >= a.n_rows || m0 + c8 * 8 >= a.c_out || flat < 0 || flat >= a.out_limit) ? -1 : flat;
+      return (r >= n_rows || m0 + c8 * 8 >= a.c_out || flat < 0 || flat >= out_limit) ? -1 : flat;
     };
     const float mslope = a.mask_slope;
     auto body = [&](auto has_res, auto has_acc, auto has_mask) {

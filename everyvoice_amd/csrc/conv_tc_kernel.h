@@ -64,6 +64,9 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void conv_tc_kernel(ConvTcArgs
   const int b = blockIdx.y;
   const int mtile = blockIdx.z;
   const int m0 = mtile * C::BM;
+  int t_in, n_rows;  // of this item (ragged batch: its own, conv_tc_mfma.h)
+  long long out_limit;
+  if (!conv_item_extents(a, b, r0, t_in, n_rows, out_limit)) return;
 
   const bf16_t* __restrict__ xb = a.x + (long long)b * a.x_batch_stride;
   // weights pre-laid-out by the host as [mtile][chunk][tap][BM][KC] (see relayout_conv_tc_weights)
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void conv_tc_kernel(ConvTcArgs
       bf16x8 val;
 #pragma unroll
       for (int e = 0; e < 8; ++e) val[e] = (bf16_t)0.f;
-      if (v < x_nvec && rr >= 0 && rr < a.t_in) val = *reinterpret_cast<const bf16x8*>(xb + (long long)rr * C::CIN + chunk * C::KC + c8 * 8);
+      if (v < x_nvec && rr >= 0 && rr < t_in) val = *reinterpret_cast<const bf16x8*>(xb + (long long)rr * C::CIN + chunk * C::KC + c8 * 8);
       xreg[i] = val;
     }
   };
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void conv_tc_kernel(ConvTcArgs
         bf16x8 val;
 #pragma unroll
         for (int e = 0; e < 8; ++e) val[e] = (bf16_t)0.f;
-        if (v < x_nvec && rr >= 0 && rr < a.t_in) val = *reinterpret_cast<const bf16x8*>(xb + (long long)rr * C::CIN + chunk * C::KC + c8 * 8);
+        if (v < x_nvec && rr >= 0 && rr < t_in) val = *reinterpret_cast<const bf16x8*>(xb + (long long)rr * C::CIN + chunk * C::KC + c8 * 8);
         xv[i] = val;
       }
 #pragma unroll
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void conv_tc_kernel(ConvTcArgs
       const int n = v / VPR, c8 = v % VPR;
       const int r = r0 + n;
       const long long flat = (long long)r * a.out_row_stride + m0 + c8 * 8 + a.out_shift;
-      return (v >= C::BN * VPR || r >= a.n_rows || flat < 0 || flat >= a.out_limit) ? -1 : flat;
+      return (v >= C::BN * VPR || r >= n_rows || flat < 0 || flat >= out_limit) ? -1 : flat;
     };
     // the (residual, running sum) cases are separate straight-line bodies: with the conditions inside, the compiler joins the
     // paths with s_waitcnt vmcnt(0) after every store

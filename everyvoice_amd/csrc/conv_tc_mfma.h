@@ -45,7 +45,25 @@ struct ConvTcArgs {
   float mask_slope = 1.f;
   long long* timeline = nullptr;  // debug instantiations only (ABL bit 128): s_memtime stamps of wave 0 of workgroup (5, 1, 0)
   int n_items = 0;                // batch items (persistent kernels walk (item, row tile, m-tile) themselves; set by launch_conv_tc)
+  // ragged batch (inference): lens.rows_per_frame = t_in per mel frame.  t_in, n_rows and out_limit stay the item strides and the
+  // upper bounds; item b computes with its own (conv_item_extents).  Value-initialised: no lengths.
+  ItemLens lens;
 };
+
+// The extents of item b, wave-uniform: t_in_b = rows_per_frame * frames_b, n_rows_b = t_in_b + (n_rows - t_in) and
+// out_limit_b = out_limit / t_in * t_in_b (the launch-wide difference and quotient are constants of the layer: 0 or 1 extra polyphase
+// row, out elements per input row).  False: the tile at row r0 lies wholly at or beyond the item's rows (an item of length 0: every
+// tile) and the workgroup exits before its first load.
+__device__ __forceinline__ bool conv_item_extents(const ConvTcArgs& a, int b, int r0, int& t_in, int& n_rows, long long& out_limit) {
+  t_in = a.t_in;
+  n_rows = a.n_rows;
+  out_limit = a.out_limit;
+  if (!a.lens.frames) return true;
+  t_in = item_rows(a.lens, b, a.t_in);
+  n_rows = t_in + (a.n_rows - a.t_in);
+  out_limit = a.out_limit / a.t_in * t_in;
+  return t_in > 0 && r0 < n_rows;
+}
 
 // One launch description, so the runtime can size LDS / grid without instantiating templates.
 struct ConvTcLaunch {

@@ -41,8 +41,8 @@ int launch_conv_transpose1d_f32(const float*, const float*, const float*, float*
                                 int, int, float, hipStream_t);
 int launch_tanh_f32(float*, long long, hipStream_t);
 int launch_nct_f32_to_tc_bf16(const float*, bf16_t*, int, int, int, int, hipStream_t);
-int launch_conv_post_tanh(const bf16_t*, const float*, float, float*, int, int, int, int, float, hipStream_t);
-int launch_istft_head(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, hipStream_t);
+int launch_conv_post_tanh(const bf16_t*, const float*, float, float*, int, int, int, int, float, ItemLens, hipStream_t);
+int launch_istft_head(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, ItemLens, hipStream_t);
 int launch_reflect_pad_left1_f32(const float*, float*, long long, int, float, hipStream_t);
 int launch_istft_f32(const float*, float*, int, int, int, int, hipStream_t);
 
@@ -510,8 +510,11 @@ static size_t stage_elems_max(const evmi_generator* g, int B, int T, bool f32) {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, int T, hipStream_t s, Recorder& rec) {
+// item_frames: mel frames per item in device memory (a ragged batch: every launch bounds item b by its own length, ItemLens in
+// common.h, and samples at or beyond item_frames[b] * hop of wav row b are left untouched), or nullptr
+static int forward_tc(evmi_generator* g, const float* mel, const int* item_frames, float* wav, int B, int T, hipStream_t s, Recorder& rec) {
   const auto& c = g->cfg;
+  auto lens_of = [&](int rows) { return ItemLens{item_frames, T, rows / T}; };  // rows: the layer's launch-wide extent, a multiple of T
   if (!g->tc_ok) return fail(EVMI_ERR_UNSUPPORTED, "bf16 MFMA path unavailable: " + g->tc_why);
   const size_t se = align_up(stage_elems_max(g, B, T, false), 64);
   const size_t in_e = align_up((size_t)B * T * round_up8(c.n_mels), 64);
@@ -533,6 +536,7 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
     a.out_batch_stride = limit;
     a.out_row_stride = row_stride; a.out_shift = shift; a.out_limit = limit;
     a.pre_slope = pre; a.post_slope = post; a.out_scale = scale; a.accumulate = accumulate;
+    a.lens = lens_of(t_in);
     EVMI_TRY(rec.begin());
     EVMI_TRY(t.launch ? launch_conv_tc(t.launch, a, B, s) : launch_conv_generic(a, t.c_in, t.ks, B, s));
     const double flops = 2.0 * B * (double)n_rows * t.c_out * t.ks * t.c_in;
@@ -595,6 +599,7 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
           ba.post_slope = (j == c.num_kernels - 1) ? (last_stage ? c.post_lrelu_slope : c.lrelu_slope) : 1.f;
           ba.out_scale = 1.f / c.num_kernels;
           ba.accumulate = j > 0;
+          ba.lens = lens_of(len_out);
           EVMI_TRY(rec.begin());
           EVMI_TRY(launch_resblock_branch(bl, ba, B, g->n_cu, s));
           EVMI_TRY(rec.end(bl->name, convs[0].layer + "+" + std::to_string(2 * nd), 4.0 * nd * B * (double)len_out * cout * cout * convs[0].ks,
@@ -624,6 +629,7 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
           pa.out_scale = scale;
           pa.accumulate = accum;
           pa.timeline = nullptr;
+          pa.lens = lens_of(len_out);
           EVMI_TRY(rec.begin());
           EVMI_TRY(launch_resblock_pair(pl, pa, B, g->n_cu, s));
           EVMI_TRY(rec.end(pl->name, convs[2 * m].layer + "+2", 4.0 * B * (double)len_out * cout * cout * convs[2 * m].ks,
@@ -645,13 +651,13 @@ static int forward_tc(evmi_generator* g, const float* mel, float* wav, int B, in
   EVMI_TRY(rec.begin());
   if (c.istft_layer) {
     if (g->istft_generic)
-      EVMI_TRY(launch_istft_head_generic(A, warena + g->istft_w_off, barena + g->istft_b_off, wav, B, len, cl, c.istft_n_fft, c.istft_hop, s));
+      EVMI_TRY(launch_istft_head_generic(A, warena + g->istft_w_off, barena + g->istft_b_off, wav, B, len, cl, c.istft_n_fft, c.istft_hop, lens_of(len), s));
     else
-      EVMI_TRY(launch_istft_head(A, warena + g->istft_w_off, barena + g->istft_b_off, wav, B, len, cl, s));
+      EVMI_TRY(launch_istft_head(A, warena + g->istft_w_off, barena + g->istft_b_off, wav, B, len, cl, lens_of(len), s));
     EVMI_TRY(rec.end(g->istft_kernel.c_str(), "conv_post+istft", 2.0 * B * (double)(len + 1) * cl * 7 * (c.istft_n_fft + 2),
                      (double)B * len * (2.0 * cl + 4.0 * c.istft_hop)));
   } else {
-    EVMI_TRY(launch_conv_post_tanh(A, (const float*)g->post_w.p, g->post_bias, wav, B, len, cl, 7, 1.f, s));
+    EVMI_TRY(launch_conv_post_tanh(A, (const float*)g->post_w.p, g->post_bias, wav, B, len, cl, 7, 1.f, lens_of(len), s));
     EVMI_TRY(rec.end("conv_post_tanh", "conv_post", 2.0 * B * (double)len * cl * 7, (double)B * len * (2.0 * cl + 4)));
   }
   return EVMI_OK;
@@ -857,9 +863,10 @@ double evmi_generator_macs_per_sample(const evmi_generator* g) {
   return per_frame / (double)g->hop();
 }
 
-static int forward_common(evmi_generator* g, const float* mel, float* wav, int B, int T, int precision, void* stream,
-                          evmi_launch_record* recs, int cap, int* n_out) {
-  if (!g || !mel || !wav) return fail(EVMI_ERR_INVALID_ARG, "forward: null argument");
+static int forward_common(evmi_generator* g, const float* mel, const int* item_frames, bool ragged, float* wav, int B, int T, int precision,
+                          void* stream, evmi_launch_record* recs, int cap, int* n_out) {
+  if (!g || !mel || !wav || (ragged && !item_frames)) return fail(EVMI_ERR_INVALID_ARG, "forward: null argument");
+  if (ragged && precision != EVMI_PREC_BF16) return fail(EVMI_ERR_UNSUPPORTED, "forward_lens: per-item lengths run in EVMI_PREC_BF16 only");
   if (!g->finalized) return fail(EVMI_ERR_NOT_READY, "forward: call evmi_generator_finalize first");
   if (B <= 0 || T <= 0) return fail(EVMI_ERR_INVALID_ARG, "forward: B and T must be positive");
   Recorder rec;
@@ -868,7 +875,7 @@ static int forward_common(evmi_generator* g, const float* mel, float* wav, int B
   rec.stream = (hipStream_t)stream;
   int rc;
   if (precision == EVMI_PREC_BF16)
-    rc = forward_tc(g, mel, wav, B, T, (hipStream_t)stream, rec);
+    rc = forward_tc(g, mel, ragged ? item_frames : nullptr, wav, B, T, (hipStream_t)stream, rec);
   else if (precision == EVMI_PREC_F32)
     rc = forward_f32(g, mel, wav, B, T, (hipStream_t)stream, rec);
   else
@@ -880,13 +887,24 @@ static int forward_common(evmi_generator* g, const float* mel, float* wav, int B
 }
 
 int evmi_generator_forward(evmi_generator* g, const float* mel, float* wav, int B, int T, int precision, void* stream) {
-  return forward_common(g, mel, wav, B, T, precision, stream, nullptr, 0, nullptr);
+  return forward_common(g, mel, nullptr, false, wav, B, T, precision, stream, nullptr, 0, nullptr);
+}
+
+int evmi_generator_forward_lens(evmi_generator* g, const float* mel, const int* item_frames, float* wav, int B, int T, int precision,
+                                void* stream) {
+  return forward_common(g, mel, item_frames, true, wav, B, T, precision, stream, nullptr, 0, nullptr);
+}
+
+int evmi_generator_forward_lens_profiled(evmi_generator* g, const float* mel, const int* item_frames, float* wav, int B, int T,
+                                         int precision, void* stream, evmi_launch_record* records, int cap, int* n_out) {
+  if (!records || cap <= 0) return fail(EVMI_ERR_INVALID_ARG, "forward_lens_profiled: records/cap");
+  return forward_common(g, mel, item_frames, true, wav, B, T, precision, stream, records, cap, n_out);
 }
 
 int evmi_generator_forward_profiled(evmi_generator* g, const float* mel, float* wav, int B, int T, int precision,
                                     void* stream, evmi_launch_record* records, int cap, int* n_out) {
   if (!records || cap <= 0) return fail(EVMI_ERR_INVALID_ARG, "forward_profiled: records/cap");
-  return forward_common(g, mel, wav, B, T, precision, stream, records, cap, n_out);
+  return forward_common(g, mel, nullptr, false, wav, B, T, precision, stream, records, cap, n_out);
 }
 
 }  // extern "C"

@@ -22,7 +22,8 @@ __global__ __launch_bounds__(512) void istft_head_kernel(const bf16_t* __restric
                                                          const bf16_t* __restrict__ w,   // [7][32][C], rows >= 18 zero
                                                          const float* __restrict__ bias, // [32]
                                                          float* __restrict__ wav,        // [B][4 L]
-                                                         int L) {
+                                                         int Ls,                         // frames per item: the stride
+                                                         ItemLens lens) {                // ragged batch: item b holds item_rows(lens, b, Ls) frames
   constexpr int S = C + 8;
   constexpr int XROWS = IS_FRAMES + IS_KS - 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -32,9 +33,11 @@ __global__ __launch_bounds__(512) void istft_head_kernel(const bf16_t* __restric
   float* Ys = Zs + IS_FRAMES * 20;                         // [IS_FRAMES][17] windowed time frames
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wn = tid >> 6;
   const int T0 = blockIdx.x * IS_SAMPLES;  // first output sample of this workgroup
+  const int L = item_rows(lens, b, Ls);     // this item's frames: L + 1 spectral frames, the envelope of a sequence of L
+  if (T0 >= IS_HOP * L) return;             // wholly at or beyond the item: before the first load
   const int F0 = T0 / IS_HOP - 1;          // first frame it needs
   const int n_frames = L + 1;
-  const bf16_t* xb = x + (long long)b * L * C;
+  const bf16_t* xb = x + (long long)b * Ls * C;
 
   for (int v = tid; v < XROWS * (C / 8); v += 512) {
     const int i = v / (C / 8), c8 = v % (C / 8);
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(512) void istft_head_kernel(const bf16_t* __restric
         env += wk * wk;
       }
     }
-    wav[(long long)b * n_out + t] = s / env;
+    wav[(long long)b * (IS_HOP * Ls) + t] = s / env;
   }
 }
 
@@ -186,7 +189,7 @@ __global__ void istft_f32_kernel(const float* __restrict__ z, float* __restrict_
   wav[(long long)b * n_out + t] = s / env;
 }
 
-int launch_istft_head(const bf16_t* x, const bf16_t* w, const float* bias, float* wav, int B, int L, int c_in,
+int launch_istft_head(const bf16_t* x, const bf16_t* w, const float* bias, float* wav, int B, int L, int c_in, ItemLens lens,
                       hipStream_t s) {
   const int n_out = IS_HOP * L;
   dim3 grid((n_out + IS_SAMPLES - 1) / IS_SAMPLES, B);
@@ -194,7 +197,7 @@ int launch_istft_head(const bf16_t* x, const bf16_t* w, const float* bias, float
   if (c_in != 32 && c_in != 64 && c_in != 128) return fail(EVMI_ERR_UNSUPPORTED, "istft_head: unsupported channel count");
   const size_t lds = lds_of(c_in) > (size_t)IS_FRAMES * 40 * 4 ? lds_of(c_in) : (size_t)IS_FRAMES * 40 * 4;
   const auto kernel = c_in == 32 ? istft_head_kernel<32> : c_in == 64 ? istft_head_kernel<64> : istft_head_kernel<128>;
-  if (int rc = launch_with_lds(kernel, grid, dim3(512), lds, s, x, w, bias, wav, L)) return rc;
+  if (int rc = launch_with_lds(kernel, grid, dim3(512), lds, s, x, w, bias, wav, L, lens)) return rc;
   EVMI_LAUNCH_CHECK("istft_head");
   return EVMI_OK;
 }

@@ -35,6 +35,6 @@ inline int istft_head_frame_tile(int n_fft, int hop) {
 }
 
 int launch_istft_head_generic(const bf16_t* x, const bf16_t* w_img, const float* bias, float* wav, int B, int L, int C, int n_fft, int hop,
-                              hipStream_t s);
+                              ItemLens lens, hipStream_t s);  // lens: ragged batch (common.h), ItemLens{} = none
 
 }  // namespace evmi

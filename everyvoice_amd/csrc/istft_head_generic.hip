@@ -40,7 +40,8 @@ __global__ __launch_bounds__(H::NTHREADS) void istft_head_generic_kernel(const b
                                                                          const bf16_t* __restrict__ w,     // conv_tc_generic image
                                                                          const float* __restrict__ bias,   // [n_fft + 2]
                                                                          float* __restrict__ wav,          // [B][hop L]
-                                                                         int L, int C, int n_fft, int hop) {
+                                                                         int Ls, int C, int n_fft, int hop,  // Ls: frames per item, the stride
+                                                                         ItemLens lens) {  // ragged batch: item b holds item_rows(lens, b, Ls) frames
   constexpr int F = 64 * NT;
   constexpr int XROWS = F + H::KS - 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -57,10 +58,12 @@ __global__ __launch_bounds__(H::NTHREADS) void istft_head_generic_kernel(const b
   const int G = F - 2 * lo - 1;
   const int F0 = blockIdx.x * G - lo;   // first frame of the tile
   const int T0 = blockIdx.x * G * hop;  // first output sample
+  const int L = item_rows(lens, b, Ls);  // this item's frames: L + 1 spectral frames, the envelope of a sequence of L
+  if (T0 >= hop * L) return;             // wholly at or beyond the item: before the first load
   const int n_frames = L + 1;
   const int nchunk = (C + H::KC - 1) / H::KC;
   const int ngroups = (co + H::BM - 1) / H::BM;
-  const bf16_t* __restrict__ xb = x + (long long)b * L * C;
+  const bf16_t* __restrict__ xb = x + (long long)b * Ls * C;
 
 #pragma unroll 1
   for (int grp = 0; grp < ngroups; ++grp) {
@@ -191,12 +194,12 @@ __global__ __launch_bounds__(H::NTHREADS) void istft_head_generic_kernel(const b
       s += (a0 + a1) * wk * inv_n;
       env += wk * wk;
     }
-    wav[(long long)b * n_out + t] = s / env;
+    wav[(long long)b * hop * Ls + t] = s / env;
   }
 }
 
 int launch_istft_head_generic(const bf16_t* x, const bf16_t* w_img, const float* bias, float* wav, int B, int L, int C, int n_fft, int hop,
-                              hipStream_t s) {
+                              ItemLens lens, hipStream_t s) {
   if (!istft_head_channels_ok(C)) return fail(EVMI_ERR_UNSUPPORTED, "istft_head_generic: C must be a multiple of 8 in [8, 512]");
   if (!istft_head_nfft_ok(n_fft)) return fail(EVMI_ERR_UNSUPPORTED, "istft_head_generic: n_fft must be even in [4, 128]");
   if (!istft_head_hop_ok(n_fft, hop)) return fail(EVMI_ERR_UNSUPPORTED, "istft_head_generic: hop must be in [1, n_fft / 2]");
@@ -209,12 +212,12 @@ int launch_istft_head_generic(const bf16_t* x, const bf16_t* w_img, const float*
   if (G < 1 || lds > 160 * 1024) return fail(EVMI_ERR_UNSUPPORTED, "istft_head_generic: tile does not fit");
   dim3 grid((unsigned)((L + G - 1) / G), B);
   const auto kernel = F == 64 ? istft_head_generic_kernel<1> : F == 128 ? istft_head_generic_kernel<2> : istft_head_generic_kernel<3>;
-  if (int rc = launch_with_lds(kernel, grid, dim3(H::NTHREADS), lds, s, x, w_img, bias, wav, L, C, n_fft, hop)) return rc;
+  if (int rc = launch_with_lds(kernel, grid, dim3(H::NTHREADS), lds, s, x, w_img, bias, wav, L, C, n_fft, hop, lens)) return rc;
   EVMI_LAUNCH_CHECK("istft_head_generic");
   return EVMI_OK;
 }
 
-int launch_istft_head(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, hipStream_t);  // istft_head.hip
+int launch_istft_head(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, ItemLens, hipStream_t);  // istft_head.hip
 
 namespace {
 
@@ -283,12 +286,12 @@ int evmi_istft_head_bf16(const void* x_dev, const float* w_dev, const float* bia
     const int n = H::KS * 32 * C;
     hipLaunchKernelGGL(istft_relayout_specialised_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w_dev, bias_dev, img, bias32, C);
     EVMI_LAUNCH_CHECK("istft_relayout_specialised");
-    return launch_istft_head(x, img, bias32, wav_dev, B, L, C, s);
+    return launch_istft_head(x, img, bias32, wav_dev, B, L, C, ItemLens{}, s);
   }
   const long long n = conv_generic_weight_elems(C, n_fft + 2, H::KS);
   hipLaunchKernelGGL(istft_relayout_generic_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w_dev, img, n_fft + 2, C, n);
   EVMI_LAUNCH_CHECK("istft_relayout_generic");
-  return launch_istft_head_generic(x, img, bias_dev, wav_dev, B, L, C, n_fft, hop, s);
+  return launch_istft_head_generic(x, img, bias_dev, wav_dev, B, L, C, n_fft, hop, ItemLens{}, s);
 }
 
 }  // extern "C"

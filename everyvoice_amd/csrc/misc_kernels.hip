@@ -29,12 +29,15 @@ template <int CIN, int KS>
 __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const bf16_t* __restrict__ x,
                                                              const float* __restrict__ w,  // [KS][CIN]
                                                              float bias, float* __restrict__ wav,
-                                                             int T, float pre_slope) {
+                                                             int Ts, float pre_slope,  // Ts: rows per item, the stride
+                                                             ItemLens lens) {  // ragged batch: item b holds item_rows(lens, b, Ts) rows
   constexpr int BN = 256, HALO = KS / 2, R = BN + KS - 1, XS = CIN + 8;
   __shared__ __attribute__((aligned(16))) bf16_t Xs[R * XS];
   __shared__ float Ws[KS * CIN];
   const int b = blockIdx.y, t0 = blockIdx.x * BN, tid = threadIdx.x;
-  const bf16_t* xb = x + (long long)b * T * CIN;
+  const int T = item_rows(lens, b, Ts);
+  if (t0 >= T) return;  // wholly at or beyond the item: before the first load
+  const bf16_t* xb = x + (long long)b * Ts * CIN;
   for (int v = tid; v < R * (CIN / 8); v += 256) {
     const int i = v / (CIN / 8), c8 = v % (CIN / 8);
     const int rr = t0 - HALO + i;
@@ -65,18 +68,21 @@ __global__ __launch_bounds__(256) void conv_post_tanh_kernel(const bf16_t* __res
       for (int e = 0; e < 8; ++e) acc = fmaf(Ws[j * CIN + c8 * 8 + e], (float)v[e], acc);
     }
   }
-  wav[(long long)b * T + t] = tanhf(acc);
+  wav[(long long)b * Ts + t] = tanhf(acc);
 }
 
 // ... for any channel count that is a multiple of 8: the same sum walked in chunks of up to 64 channels through a fixed LDS tile
 // (per output: chunk, tap, channel -- the instantiations above keep their own order and bits)
 __global__ __launch_bounds__(256) void conv_post_tanh_any_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w,  // [KS][c_in]
-                                                                 float bias, float* __restrict__ wav, int T, int c_in, float pre_slope) {
+                                                                 float bias, float* __restrict__ wav, int Ts, int c_in, float pre_slope,
+                                                                 ItemLens lens) {  // Ts, lens: as above
   constexpr int KS = 7, BN = 256, HALO = KS / 2, R = BN + KS - 1, CK = 64, XS = CK + 8;
   __shared__ __attribute__((aligned(16))) bf16_t Xs[R * XS];
   __shared__ float Ws[KS * CK];
   const int b = blockIdx.y, t0 = blockIdx.x * BN, tid = threadIdx.x;
-  const bf16_t* xb = x + (long long)b * T * c_in;
+  const int T = item_rows(lens, b, Ts);
+  if (t0 >= T) return;
+  const bf16_t* xb = x + (long long)b * Ts * c_in;
   float acc = bias;
   for (int c0 = 0; c0 < c_in; c0 += CK) {
     const int cw = c_in - c0 < CK ? c_in - c0 : CK;  // channels of this chunk (a multiple of 8)
@@ -107,7 +113,7 @@ __global__ __launch_bounds__(256) void conv_post_tanh_any_kernel(const bf16_t* _
       }
   }
   const int t = t0 + tid;
-  if (t < T) wav[(long long)b * T + t] = tanhf(acc);
+  if (t < T) wav[(long long)b * Ts + t] = tanhf(acc);
 }
 
 int launch_nct_f32_to_tc_bf16(const float* in, bf16_t* out, int B, int C, int Cp, int T, hipStream_t s) {
@@ -120,18 +126,18 @@ int launch_nct_f32_to_tc_bf16(const float* in, bf16_t* out, int B, int C, int Cp
 }
 
 int launch_conv_post_tanh(const bf16_t* x, const float* w_kc, float bias, float* wav, int B, int T,
-                          int c_in, int ks, float pre_slope, hipStream_t s) {
+                          int c_in, int ks, float pre_slope, ItemLens lens, hipStream_t s) {
   dim3 grid((T + 255) / 256, B);
   if (ks == 7 && c_in == 32) {
-    hipLaunchKernelGGL((conv_post_tanh_kernel<32, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope);
+    hipLaunchKernelGGL((conv_post_tanh_kernel<32, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope, lens);
   } else if (ks == 7 && c_in == 64) {
-    hipLaunchKernelGGL((conv_post_tanh_kernel<64, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope);
+    hipLaunchKernelGGL((conv_post_tanh_kernel<64, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope, lens);
   } else if (ks == 7 && c_in == 16) {
-    hipLaunchKernelGGL((conv_post_tanh_kernel<16, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope);
+    hipLaunchKernelGGL((conv_post_tanh_kernel<16, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope, lens);
   } else if (ks == 7 && c_in == 128) {
-    hipLaunchKernelGGL((conv_post_tanh_kernel<128, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope);
+    hipLaunchKernelGGL((conv_post_tanh_kernel<128, 7>), grid, dim3(256), 0, s, x, w_kc, bias, wav, T, pre_slope, lens);
   } else if (ks == 7 && c_in > 0 && c_in % 8 == 0) {
-    hipLaunchKernelGGL(conv_post_tanh_any_kernel, grid, dim3(256), 0, s, x, w_kc, bias, wav, T, c_in, pre_slope);
+    hipLaunchKernelGGL(conv_post_tanh_any_kernel, grid, dim3(256), 0, s, x, w_kc, bias, wav, T, c_in, pre_slope, lens);
   } else {
     return fail(EVMI_ERR_UNSUPPORTED, "conv_post_tanh: unsupported (c_in, k): k = 7 and a multiple of 8 channels");
   }

@@ -36,10 +36,12 @@ struct BranchArgs {
   int n_tiles;
   float slope, post_slope, out_scale;
   int accumulate;
+  ItemLens lens = {};  // ragged batch: as PairArgs::lens
 };
 
 struct BranchLaunch {
   void (*kernel)(BranchArgs);
+  void (*kernel_ragged)(BranchArgs) = nullptr;  // as PairLaunch::kernel_ragged
   int c, ks, bn, rb, threads;
   size_t lds_bytes;
   const char* name;
@@ -75,7 +77,7 @@ struct BranchCfg {
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-template <class P>
+template <class P, bool RAGGED = false>  // RAGGED: as in resblock_pair_kernel
 __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* XA = reinterpret_cast<bf16_t*>(smem) + P::OFF_XA;
@@ -108,6 +110,8 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int g0 = rt * a.tt - mtot;
     const bf16_t* xb = a.x + (long long)item * a.T * C;
+    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;
+    if (RAGGED && rt * a.tt >= Tb) return;  // a tile at or beyond its item's length is skipped: nothing to load
 #pragma unroll
     for (int i = 0; i < P::X_PER_THREAD; ++i) {
       const int v = tid + i * P::NTHREADS;
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
       bf16x8 val;
 #pragma unroll
       for (int e = 0; e < 8; ++e) val[e] = (bf16_t)0.f;
-      if (v < x_nvec && g >= 0 && g < a.T) val = *reinterpret_cast<const bf16x8*>(xb + (long long)g * C + c8 * 8);
+      if (v < x_nvec && g >= 0 && g < Tb) val = *reinterpret_cast<const bf16x8*>(xb + (long long)g * C + c8 * 8);
       xreg[i] = val;
     }
   };
@@ -184,8 +188,13 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int r0 = rt * a.tt;       // first output row of this tile
     const int g0 = r0 - mtot;       // global row of LDS row 0
-    const bool edge = g0 < 0 || g0 + P::RB > a.T;  // (wave-uniform) the tile holds rows outside the sequence
     const int next = tile + per_xcd_wg;
+    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;  // valid rows of this item (wave-uniform)
+    if (RAGGED && r0 >= Tb) {  // this slot of the walk lies at or beyond its item's length: no load, no store
+      if (next < tile_hi) x_issue(next);
+      continue;
+    }
+    const bool edge = g0 < 0 || g0 + P::RB > Tb;  // (wave-uniform) the tile holds rows outside the sequence
     x_commit();
 
     f32x16 acc[P::MT][P::NT];
@@ -243,7 +252,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
                 bf16x4 pk = lrelu4_bf16(f32x4{acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]}, sl);
                 if (edge) {
                   const int g = g0 + row;
-                  if (g < 0 || g >= a.T) {
+                  if (g < 0 || g >= Tb) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)0.f;
                   }
@@ -274,7 +283,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
               for (int i = 0; i < 4; ++i) raw[i] = (bf16_t)(acc[mt][nt][4 * q + i] + (float)rv[i]);
               if (edge) {
                 const int g = g0 + row;
-                if (g < 0 || g >= a.T) {
+                if (g < 0 || g >= Tb) {
 #pragma unroll
                   for (int i = 0; i < 4; ++i) raw[i] = (bf16_t)0.f;
                 }
@@ -294,7 +303,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
         for (int nt = 0; nt < P::NT; ++nt) {
           const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
           const int r = r0 + n;
-          const bool ok = n < a.tt && r < a.T;
+          const bool ok = n < a.tt && r < Tb;
           bf16_t* dst = ob + (long long)(ok ? r : 0) * C + 8 * hh;
           u32x4 pv[P::MT][2];
           if (a.accumulate) {
@@ -345,6 +354,7 @@ template <class P>
 static BranchLaunch make_branch_launch(const char* name) {
   BranchLaunch l;
   l.kernel = resblock_branch_kernel<P>;
+  l.kernel_ragged = resblock_branch_kernel<P, true>;
   l.c = P::C;
   l.ks = P::KS;
   l.bn = P::BN;

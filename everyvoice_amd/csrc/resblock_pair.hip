@@ -63,7 +63,7 @@ int launch_resblock_pair(const PairLaunch* L, PairArgs a, int B, int n_cu, hipSt
   grid = (grid + 7) / 8 * 8;
   const int needed = (a.n_tiles + 7) / 8 * 8;
   if (grid > needed) grid = needed;
-  if (int rc = launch_with_lds(L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
+  if (int rc = launch_with_lds(a.lens.frames ? L->kernel_ragged : L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
   EVMI_LAUNCH_CHECK(L->name);
   return EVMI_OK;
 }
@@ -116,7 +116,7 @@ int launch_resblock_branch(const BranchLaunch* L, BranchArgs a, int B, int n_cu,
   grid = (grid + 7) / 8 * 8;
   const int needed = (a.n_tiles + 7) / 8 * 8;
   if (grid > needed) grid = needed;
-  if (int rc = launch_with_lds(L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
+  if (int rc = launch_with_lds(a.lens.frames ? L->kernel_ragged : L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
   EVMI_LAUNCH_CHECK(L->name);
   return EVMI_OK;
 }

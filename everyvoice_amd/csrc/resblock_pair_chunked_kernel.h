@@ -35,7 +35,7 @@ struct PairChunkedCfg {
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-template <class P>
+template <class P, bool RAGGED = false>  // RAGGED: as in resblock_pair_kernel
 // (one workgroup per CU by its LDS: the register budget is the full 256 per wave at two waves per SIMD)
 __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(PairArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -68,14 +68,16 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
   auto x_issue = [&](int t, int chunk) {
     const int item = t / a.tiles_per_item, rt = t % a.tiles_per_item;
     const int g0 = rt * P::TT - H2 - h1;
+    // the descriptor holds the item's own byte extent (ragged batch: item_rows); none at all for a tile at or beyond it, which is skipped
+    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x + (long long)item * a.T * C), 0,
-                                                        a.T * C * 2, 0x00020000);
+                                                        (!RAGGED || rt * P::TT < Tb) ? Tb * C * 2 : 0, 0x00020000);
 #pragma unroll
     for (int i = 0; i < P::XV; ++i) {
       const int v = tid + i * P::NTHREADS;
       const int row = v / (KC / 8), c8 = v % (KC / 8);
       const int g = g0 + row;
-      // rows outside [0, T) fall outside the descriptor and read as zero (the convolution's zero padding)
+      // rows outside [0, T_item) fall outside the descriptor and read as zero (the convolution's zero padding)
       const unsigned voff = g < 0 ? 0xfffffff0u : (unsigned)((g * C + chunk * KC + c8 * 8) * 2);
       xreg[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 0));
     }
@@ -114,11 +116,11 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
       *reinterpret_cast<bf16x8*>(dst + (v / (KC / 8)) * P::SW + (v % (KC / 8)) * 8) = wreg[slot][i];
     }
   };
-  auto out_offset = [&](int r0, int i) -> unsigned {
+  auto out_offset = [&](int r0, int Tb, int i) -> unsigned {
     const int v = tid + i * P::NTHREADS;
     const int n = v / (C / 8), c8 = v % (C / 8);
     const int r = r0 + n;
-    return (n < P::TT && r < a.T) ? (unsigned)((r * C + c8 * 8) * 2) : 0xfffffff0u;
+    return (n < P::TT && r < Tb) ? (unsigned)((r * C + c8 * 8) * 2) : 0xfffffff0u;
   };
 
   x_issue(tile, 0);
@@ -130,6 +132,11 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int r0 = rt * P::TT;
     const int next = tile + per_xcd_wg < tile_hi ? tile + per_xcd_wg : tile;  // last tile: a harmless repeat
+    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;  // valid rows of this item (wave-uniform)
+    if (RAGGED && r0 >= Tb) {  // this slot of the walk lies at or beyond its item's length: no load, no store (the weight ring keeps its place)
+      if (next != tile) x_issue(next, 0);
+      continue;
+    }
 
     f32x16 acc[P::MT][P::NT];
     auto zero_acc = [&]() {
@@ -175,7 +182,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
           for (int nt = 0; nt < P::NT; ++nt) {
             const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
             const int g = r0 - H2 + n;
-            const float mask = (g >= 0 && g < a.T) ? 1.f : 0.f;
+            const float mask = (g >= 0 && g < Tb) ? 1.f : 0.f;
             bf16x4 pk;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -209,11 +216,11 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
     }
     // ---------------- epilogue ----------------
     const auto xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x + (long long)item * a.T * C), 0,
-                                                         a.T * C * 2, 0x00020000);
-    const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + (long long)item * a.T * C, 0, a.T * C * 2, 0x00020000);
+                                                         Tb * C * 2, 0x00020000);
+    const auto orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + (long long)item * a.T * C, 0, Tb * C * 2, 0x00020000);
 #pragma unroll
     for (int i = 0; i < P::RV; ++i)  // residual rows (raw x): L2-resident, issued before the staging pass
-      rreg[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, out_offset(r0, i), 0, 0));
+      rreg[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, out_offset(r0, Tb, i), 0, 0));
     lds_barrier();  // every wave is done reading T1: it becomes the staging tile
 #pragma unroll
     for (int mt = 0; mt < P::MT; ++mt)
@@ -236,7 +243,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
 #pragma unroll
       for (int i = 0; i < P::RV; ++i) {
         const int v = tid + i * P::NTHREADS;
-        const unsigned off = out_offset(r0, i);
+        const unsigned off = out_offset(r0, Tb, i);
         const bf16x8 o = *reinterpret_cast<const bf16x8*>(OS + (v / (C / 8)) * P::ST + (v % (C / 8)) * 8);
         float f[8];
 #pragma unroll
@@ -260,6 +267,7 @@ template <class P>
 static PairLaunch make_pair_chunked_launch(const char* name) {
   PairLaunch l;
   l.kernel = resblock_pair_chunked_kernel<P>;
+  l.kernel_ragged = resblock_pair_chunked_kernel<P, true>;
   l.c = P::C;
   l.ks = P::KS;
   l.bn = P::BN;

@@ -37,10 +37,13 @@ struct PairArgs {
   float out_scale;
   int accumulate;
   long long* timeline;  // debug builds only (PairCfg::DBG): cycle stamps of workgroup 0, else nullptr
+  // ragged batch: T stays the item stride and the upper bound, item b is valid for item_rows(lens, b, T) rows (common.h)
+  ItemLens lens = {};
 };
 
 struct PairLaunch {
   void (*kernel)(PairArgs);
+  void (*kernel_ragged)(PairArgs) = nullptr;  // the same kernel reading PairArgs::lens: an instantiation of its own, so the uniform one keeps its registers
   int c, ks, bn, tt, threads, max_dil;
   int wg_per_cu = 1;  // persistent workgroups per CU (LDS-bound residency)
   int kc;  // channel chunk of the weight layout [chunk][tap][C][kc] (== c when the layer is not chunked)
@@ -87,7 +90,8 @@ struct PairCfg {
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-template <class P>
+// RAGGED: item lengths from a.lens (item_rows); false: a.lens is not looked at and every item holds a.T rows
+template <class P, bool RAGGED = false>
 __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* XA = reinterpret_cast<bf16_t*>(smem) + P::OFF_XA;
@@ -117,6 +121,8 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) 
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int g0 = rt * P::TT - H2 - h1;  // global row of XA row 0
     const bf16_t* xb = a.x + (long long)item * a.T * C;
+    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;
+    if (RAGGED && rt * P::TT >= Tb) return;  // a tile at or beyond its item's length is skipped: nothing to load
 #pragma unroll
     for (int i = 0; i < P::X_PER_THREAD; ++i) {
       const int v = tid + i * P::NTHREADS;
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) 
       bf16x8 val;
 #pragma unroll
       for (int e = 0; e < 8; ++e) val[e] = (bf16_t)0.f;
-      if (v < x_nvec && g >= 0 && g < a.T) val = *reinterpret_cast<const bf16x8*>(xb + (long long)g * C + c8 * 8);
+      if (v < x_nvec && g >= 0 && g < Tb) val = *reinterpret_cast<const bf16x8*>(xb + (long long)g * C + c8 * 8);
       xreg[i] = val;
     }
   };
@@ -197,6 +203,11 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) 
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int r0 = rt * P::TT;  // first output row of this tile
     const int next = tile + per_xcd_wg;
+    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;  // valid rows of this item (wave-uniform)
+    if (RAGGED && r0 >= Tb) {  // this slot of the walk lies at or beyond its item's length: no load, no store
+      if (next < tile_hi) x_issue(next);
+      continue;
+    }
     stamp();  // tile start
     x_commit();
     stamp();  // x committed
@@ -240,7 +251,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) 
       if (conv == 0) {
         // T1[n] = lrelu(conv1 + b1) for global row r0 - H2 + n, zero outside the sequence
         const float sl = a.slope;
-        const bool edge = r0 - H2 < 0 || r0 - H2 + P::BN > a.T;  // (wave-uniform) rows outside the sequence in this tile
+        const bool edge = r0 - H2 < 0 || r0 - H2 + P::BN > Tb;  // (wave-uniform) rows outside the sequence in this tile
 #pragma unroll
         for (int mt = 0; mt < P::MT; ++mt) {
 #pragma unroll
@@ -252,7 +263,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) 
               bf16x4 pk = lrelu4_bf16(f32x4{acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]}, sl);
               if (edge) {
                 const int g = r0 - H2 + n;
-                if (g < 0 || g >= a.T) {
+                if (g < 0 || g >= Tb) {
 #pragma unroll
                   for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)0.f;
                 }
@@ -283,7 +294,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) 
       for (int nt = 0; nt < P::NT; ++nt) {
         const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
         const int r = r0 + n;
-        const bool ok = n < P::TT && r < a.T;
+        const bool ok = n < P::TT && r < Tb;
         bf16_t* dst = ob + (long long)(ok ? r : 0) * C + 8 * hh;
         u32x4 pv[P::MT][2];
         if (a.accumulate) {  // wave-uniform; all of the lane's vectors are requested before the first is consumed
@@ -333,6 +344,7 @@ template <class P>
 static PairLaunch make_pair_launch(const char* name) {
   PairLaunch l;
   l.kernel = resblock_pair_kernel<P>;
+  l.kernel_ragged = resblock_pair_kernel<P, true>;
   l.c = P::C;
   l.ks = P::KS;
   l.bn = P::BN;

@@ -703,7 +703,8 @@ def style_reference_batch(references, cfg: AudioConfig | None = None, device="cu
 def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, out_dir, basenames: list[str], speaker: str = "default",
                          language: str = "default", output_types=("wav", "spec"), sr: int = 22050, hop: int = 256,
                          duration_control: float = 1.0, global_step: int | None = None, style_reference=None,
-                         audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None) -> list[dict]:
+                         audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None,
+                         mask_vocoder_padding: bool = False) -> list[dict]:
     """The device part of ``everyvoice synthesize from-text`` (``fs2.cli.synthesize.synthesize_helper``,
     ``everyvoice/demo/app.py:84-106``): token ids -> FastSpeech2 (postnet mel) -> HiFiGAN -> files named as the reference's
     prediction writers name them (``everyvoice/base_cli/prediction_writing_callback.py:35-41``):
@@ -711,7 +712,9 @@ def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, ou
     holding ``[n_mels, T]``.  Text normalisation / g2p (CPU string work) stays with the caller: ``ids`` are symbol ids, 0 pads.
     ``style_reference`` (a wav path, or a 1-D waveform at ``style_reference_sampling_rate``; ``audio_config``: the model's
     ``preprocessing.audio``, default as in ``synthesize_helper``): a model with the Global Style Token module needs it, any other refuses it.
-    A list of references gives every item its own (``style_reference_batch``: padded together, passed with their lengths)."""
+    A list of references gives every item its own (``style_reference_batch``: padded together, passed with their lengths).
+    ``mask_vocoder_padding``: the vocoder gets the mel lengths (``vocoder(mel, lens=mel_lens)``), so every item's waveform is the one
+    it gets alone, whatever else is in the batch, and the padding frames are not computed.  Off: the batch runs as a rectangle."""
     kw = {}
     if style_reference is not None:
         if not _has_style_tokens(fs2):
@@ -724,7 +727,10 @@ def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, ou
         else:
             kw["style_mel"] = style_reference_mel(style_reference, cfg, fs2.device, style_reference_sampling_rate)
     mel, post, durations, _, _, mel_lens = fs2(ids, lens, duration_control=duration_control, **kw)
-    wav = vocoder(post.transpose(1, 2).contiguous()) if "wav" in output_types else None
+    wav = None
+    if "wav" in output_types:
+        vmel = post.transpose(1, 2).contiguous()
+        wav = vocoder(vmel, lens=mel_lens) if mask_vocoder_padding else vocoder(vmel)
     results = []
     for i, base in enumerate(basenames):
         T = int(mel_lens[i])
@@ -768,7 +774,8 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                       text_representation=None, accelerator: str = "auto", devices: str = "1", device=None, batch_size: int = 16, num_workers: int = 0,
                       filelist=None, filelist_data=None, output_dir: Path = Path("synthesis_output"), teacher_forcing_directory: Path | None = None,
                       vocoder_model=None, vocoder_config=None, vocoder_global_step: int | None = None, style_reference=None, return_scores: bool = False,
-                      text_to_ids=None, audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None):
+                      text_to_ids=None, audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None,
+                      mask_vocoder_padding: bool = False):
     """``fs2.cli.synthesize.synthesize_helper`` (call site ``everyvoice/demo/app.py:84-106``, same keyword names) for the path this
     library accelerates: texts -> symbol ids -> FastSpeech2 -> (vocoder) -> files through per-format writers.
     Returns ``(config, device, predictions, callbacks)`` with ``callbacks`` keyed by output format ("wav", "spec").
@@ -780,7 +787,10 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
     ``style_reference``: the path of a wav file (the demo's ``gr.Audio(type="filepath")``) or a 1-D float waveform (at
     ``style_reference_sampling_rate``, default the front end's input rate), for a model with the Global Style Token module: it goes through
     the front end the training mels were made with (``audio_config``; default: the model's own ``audio_config`` /
-    ``config.preprocessing.audio``, else the vocoder configuration's, else the defaults) and ONE style embedding serves every text of the call.  A model without the module refuses it; a model with the module refuses a call without it."""
+    ``config.preprocessing.audio``, else the vocoder configuration's, else the defaults) and ONE style embedding serves every text of the call.  A model without the module refuses it; a model with the module refuses a call without it.
+    ``mask_vocoder_padding``: the vocoder gets each batch's mel lengths (``vocoder_model(mel, lens=mel_lens)``): an utterance's audio no
+    longer depends on ``batch_size`` or on its neighbours, and the padding frames are not computed.  A keyword, not a configuration
+    field (the vocoder's model configuration mirrors the reference's schema).  Off (the default): the batch runs as a rectangle."""
     if style_reference is not None and not _has_style_tokens(model):
         raise ValueError("style_reference given, but this model has no Global Style Token module (model.use_global_style_token_module)")
     formats = [getattr(f, "value", f) for f in (output_type if isinstance(output_type, (list, tuple)) else [output_type])]
@@ -835,7 +845,10 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
         if style_mel is not None:
             kw["style_mel"] = style_mel
         _, post, durations, _, _, mel_lens = model(ids, lens, duration_control=1.0 if duration_control is None else duration_control, **kw)
-        wav = vocoder_model(post.transpose(1, 2).contiguous()) if "wav" in formats else None
+        wav = None
+        if "wav" in formats:
+            vmel = post.transpose(1, 2).contiguous()
+            wav = vocoder_model(vmel, lens=mel_lens) if mask_vocoder_padding else vocoder_model(vmel)
         for j, r in enumerate(chunk):
             T = int(mel_lens[j])
             rec = {"basename": r["basename"], "speaker": spk[j], "language": lang[j], "frames": T, "durations": durations[j, : int(lens[j])].cpu()}

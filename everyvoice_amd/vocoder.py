@@ -30,6 +30,20 @@ from .config import ACTIVATION_SLOPES, HiFiGANConfig
 PRECISIONS = {"bf16": _lib.EVMI_PREC_BF16, "f32": _lib.EVMI_PREC_F32, "f32-direct": _lib.EVMI_PREC_F32}
 
 
+def check_lens(lens, B: int, T: int, what: str = "lens"):
+    """Host-side refusals for the per-item mel lengths of a ragged vocoder batch: ``lens`` must be an integer [B].  Lengths that
+    live on the host are checked to lie in [1, T] and returned as they are (the caller uploads them); a device tensor is taken as
+    it is, as int32 and contiguous, without a synchronisation -- the kernels clamp what they read to [0, T], so a captured graph
+    can be replayed on new lengths written into the same tensor."""
+    if not isinstance(lens, torch.Tensor):
+        lens = torch.as_tensor(lens)
+    if lens.dim() != 1 or lens.shape[0] != B or lens.dtype.is_floating_point or lens.dtype == torch.bool or lens.dtype.is_complex:
+        raise ValueError(f"{what}: expected {B} integer lengths (one per row of the mel batch), got {lens.dtype} {tuple(lens.shape)}")
+    if lens.device.type == "cpu" and B and (int(lens.min()) < 1 or int(lens.max()) > T):
+        raise ValueError(f"{what}: lengths must be between 1 and T = {T}, got {lens.tolist()}")
+    return lens.to(torch.int32).contiguous()
+
+
 class _ConvParams(nn.Module):
     """weight + bias of one convolution (no forward: the arithmetic lives in the HIP library)."""
 
@@ -279,9 +293,65 @@ class Generator(nn.Module):
                 x = ops.tanh(ops.conv1d_fwd(x, self.conv_post.weight, self.conv_post.bias, 1, 3, 1, 1))
         return x.view(B, 1, -1)  # [1, B, T'] and [B, 1, T'] are the same bytes
 
+    def _lens_arg(self, lens, mel: torch.Tensor) -> torch.Tensor:
+        """``lens`` checked (check_lens) and on the mel's device as int32."""
+        lens = check_lens(lens, mel.shape[0], mel.shape[2])
+        return lens if lens.device == mel.device else lens.to(mel.device)
+
     @torch.no_grad()
-    def forward(self, mel: torch.Tensor) -> torch.Tensor:
+    def _forward_lens(self, mel: torch.Tensor, lens, profiled: bool = False):
+        """A ragged batch: item i holds ``lens[i]`` mel frames and its waveform equals, bit for bit, the one the item gets alone at
+        that length; ``wav[i, 0, lens[i] * hop:]`` is zero.
+
+        bf16: every kernel reads the lengths from device memory (evmi_generator_forward_lens) -- no host round trip, so the call
+        can be captured in a graph and replayed on other lengths.  "f32" / "f32-direct": each item runs alone at its own length
+        through the forward without lengths and is copied into the zeroed output; exact by construction, but the lengths are read
+        on the host, so these precisions cannot be captured."""
+        B, _, T = mel.shape
+        wav = torch.zeros(B, 1, T * self.hop, device=mel.device, dtype=torch.float32)
+        if self.precision != "bf16":
+            host = check_lens(lens, B, T).cpu()
+            if B and (int(host.min()) < 0 or int(host.max()) > T):
+                raise ValueError(f"lens: lengths must be between 0 and T = {T}, got {host.tolist()}")
+            recs = []
+            for i, n in enumerate(host.tolist()):
+                if n == 0:
+                    continue
+                item = mel[i : i + 1, :, :n].contiguous()
+                if profiled:
+                    solo, r = self.forward_profiled(item)
+                    recs += r
+                else:
+                    solo = self.forward(item)
+                wav[i, 0, : n * self.hop] = solo[0, 0]
+            return (wav, recs) if profiled else wav
+        dev_lens = self._lens_arg(lens, mel)
+        lib = self._ensure_native(mel.device)
+        stream = _lib.current_stream_ptr(mel.device)
+        with torch.cuda.device(mel.device):
+            if not profiled:
+                _lib.check(
+                    lib.evmi_generator_forward_lens(self._handle, mel.data_ptr(), dev_lens.data_ptr(), wav.data_ptr(), B, T,
+                                                    PRECISIONS[self.precision], stream),
+                    "evmi_generator_forward_lens",
+                )
+                return wav
+            cap = 512
+            recs = (_lib.LaunchRecord * cap)()
+            n = C.c_int(0)
+            _lib.check(
+                lib.evmi_generator_forward_lens_profiled(self._handle, mel.data_ptr(), dev_lens.data_ptr(), wav.data_ptr(), B, T,
+                                                         PRECISIONS[self.precision], stream, recs, cap, C.byref(n)),
+                "evmi_generator_forward_lens_profiled",
+            )
+        return wav, _records(recs, n.value, cap)
+
+    @torch.no_grad()
+    def forward(self, mel: torch.Tensor, lens=None) -> torch.Tensor:
+        """``lens`` (integer [B], mel frames per item): a ragged batch, see ``_forward_lens``.  None: the whole rectangle."""
         mel = self._check_input(mel)
+        if lens is not None:
+            return self._forward_lens(mel, lens)
         if self.precision == "f32":
             return self._forward_f32_mfma(mel)
         lib = self._ensure_native(mel.device)
@@ -296,10 +366,12 @@ class Generator(nn.Module):
         return wav
 
     @torch.no_grad()
-    def forward_profiled(self, mel: torch.Tensor):
+    def forward_profiled(self, mel: torch.Tensor, lens=None):
         """One forward with every launch bracketed by HIP events on the current stream.
-        Returns (wav, [dict(kernel, layer, ms, flops, bytes)])."""
+        Returns (wav, [dict(kernel, layer, ms, flops, bytes)]).  ``lens``: as in ``forward``."""
         mel = self._check_input(mel)
+        if lens is not None:
+            return self._forward_lens(mel, lens, profiled=True)
         lib = self._ensure_native(mel.device)
         B, _, T = mel.shape
         wav = torch.empty(B, 1, T * self.hop, device=mel.device, dtype=torch.float32)
@@ -313,11 +385,14 @@ class Generator(nn.Module):
                                                     recs, cap, C.byref(n)),
                 "evmi_generator_forward_profiled",
             )
-        out = [
-            dict(kernel=r.kernel.decode(), layer=r.layer.decode(), ms=float(r.ms), flops=float(r.flops), bytes=float(r.bytes))
-            for r in recs[: min(n.value, cap)]
-        ]
-        return wav, out
+        return wav, _records(recs, n.value, cap)
+
+
+def _records(recs, n: int, cap: int) -> list:
+    return [
+        dict(kernel=r.kernel.decode(), layer=r.layer.decode(), ms=float(r.ms), flops=float(r.flops), bytes=float(r.bytes))
+        for r in recs[: min(n, cap)]
+    ]
 
 
 def fold_weight_norm_(state_dict: dict, prefix: str = "") -> None:
@@ -345,8 +420,8 @@ class HiFiGANGenerator(nn.Module):
         self.config = config
         self.generator = Generator(config, precision=precision)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.generator(x)
+    def forward(self, x: torch.Tensor, lens=None) -> torch.Tensor:
+        return self.generator(x) if lens is None else self.generator(x, lens)
 
     def on_save_checkpoint(self, checkpoint: dict) -> None:
         """Checkpoint conventions of the reference (everyvoice/tests/test_model.py:85-151,302-313):

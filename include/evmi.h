@@ -218,6 +218,16 @@ int64_t evmi_generator_workspace_bytes(const evmi_generator* g, int B, int T, in
 int evmi_generator_forward(evmi_generator* g, const float* mel_dev, float* wav_dev, int B, int T,
                            int precision, void* stream);
 
+/* The same forward on a ragged batch: item_frames_dev [B] int32 in device memory holds the mel frames of each item.  Item b is
+ * computed as if it were alone at its own length, bit for bit: every kernel bounds its loads, stores and zero padding by
+ * clamp(item_frames[b], 0, T) frames, and tiles that lie wholly beyond an item are not computed.  Samples at or beyond
+ * item_frames[b] * hop of row b of wav_dev are left untouched.  The lengths are read on the device only (no host round trip, no
+ * extra workspace), so a captured graph follows whatever the tensor holds at replay.  Same contract as evmi_generator_forward
+ * otherwise; EVMI_ERR_INVALID_ARG for a null pointer, EVMI_ERR_UNSUPPORTED for any precision but EVMI_PREC_BF16,
+ * EVMI_ERR_NOT_READY before finalize. */
+int evmi_generator_forward_lens(evmi_generator* g, const float* mel_dev, const int* item_frames_dev, float* wav_dev, int B, int T,
+                                int precision, void* stream);
+
 /* Same forward with every kernel launch bracketed by HIP events on `stream` (synchronises).
  * Fills up to `cap` records; returns the number of launches through *n_out. */
 typedef struct evmi_launch_record {
@@ -230,6 +240,9 @@ typedef struct evmi_launch_record {
 int evmi_generator_forward_profiled(evmi_generator* g, const float* mel_dev, float* wav_dev, int B,
                                     int T, int precision, void* stream, evmi_launch_record* records,
                                     int cap, int* n_out);
+/* ... of evmi_generator_forward_lens (the records' flops / bytes stay those of the full rectangle). */
+int evmi_generator_forward_lens_profiled(evmi_generator* g, const float* mel_dev, const int* item_frames_dev, float* wav_dev, int B,
+                                         int T, int precision, void* stream, evmi_launch_record* records, int cap, int* n_out);
 
 /* Algorithmic MACs per output sample of this configuration (V1: 1,199,424). */
 double evmi_generator_macs_per_sample(const evmi_generator* g);
