@@ -102,6 +102,11 @@ class FastSpeech2ModelConfig:
     gst_mask_padding: bool = False
     gst_num_tokens: int = 10
     gst_ref_enc_filters: tuple = (32, 32, 64, 64, 128, 128)
+    # not in the reference's schema: every layer that looks beyond its own column (the Conformers' depthwise convolutions and, in
+    # training, their BatchNorms; the variance predictors' k > 1 convolutions; the postnet) treats the columns at or beyond an item's
+    # length as absent: what the model writes for an utterance then does not depend on the padding or on what
+    # else is in its batch.  False = the padded columns are computed and seen, as in the reference's Conformer
+    mask_padding: bool = False
 
     def __post_init__(self):
         self.gst_ref_enc_filters = tuple(int(v) for v in self.gst_ref_enc_filters)  # (a list after a JSON round trip)
@@ -150,9 +155,21 @@ def _ln_conv(x, g, b, w, bias, act=ops.ACT_NONE):
     return _conv(_layernorm(x, g, b), w, bias, act=act)
 
 
-def _dwconv(x, w, b, k, act):
+def _mask_cols_(x, lens):
+    """x [C, B, T]: zero at the columns t >= lens[b], in place."""
+    C, B, T = x.shape
+    _chk(_lib.load().evmi_mask_cols_f32(x.data_ptr(), lens.data_ptr(), C, B, T, _s(x)), "evmi_mask_cols_f32")
+    return x
+
+
+def _dwconv(x, w, b, k, act, lens=None):
+    """``lens`` (int32 [B] on the device; ``mask_padding``): the columns at or beyond lens[b] are absent -- read as zero, written as zero."""
     y = torch.empty_like(x)
     C, B, T = x.shape
+    if lens is not None:
+        _chk(_lib.load().evmi_dwconv1d_cbt_lens_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), lens.data_ptr(), y.data_ptr(), C, B, T, k, (k - 1) // 2,
+                                                    act, _s(x)), "evmi_dwconv1d_cbt_lens_f32")
+        return y
     _chk(_lib.load().evmi_dwconv1d_cbt_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), C, B, T, k, (k - 1) // 2, act, _s(x)),
          "evmi_dwconv1d_cbt_f32")
     return y
@@ -316,8 +333,8 @@ def check_style_lens(style_lens, style_mel_shape, what="style_lens"):
 
 
 class _Conformer:
-    def __init__(self, cfg: ConformerConfig, sd: dict, prefix: str, dev):
-        self.cfg = cfg
+    def __init__(self, cfg: ConformerConfig, sd: dict, prefix: str, dev, mask_padding: bool = False):
+        self.cfg, self.mask_padding = cfg, mask_padding
         self.layers = []
         d = cfg.input_dim
         put = lambda t: t.to(dev, torch.float32).contiguous()
@@ -353,7 +370,9 @@ class _Conformer:
         return _conv_add(h, P["w2"], P["b2"], x)
 
     def forward(self, x, lens):
-        """x [D, B, T] (padded positions are computed, not masked: the convolution module sees them, as in the reference)."""
+        """x [D, B, T] (padded positions are computed, not masked: the convolution module sees them, as in the reference).  With
+        ``mask_padding`` the depthwise convolution takes the columns at or beyond lens[b] as absent; attention masks its keys by length
+        already and everything else is position-wise, so a valid column then depends on its own item's valid columns only."""
         lib = _lib.load()
         D, B, T = x.shape
         for L in self.layers:
@@ -367,7 +386,7 @@ class _Conformer:
             Cm = L["conv"]
             p = _ln_conv(x, Cm["ln_g"], Cm["ln_b"], Cm["w_pw1"], Cm["b_pw1"])
             g = ops.elementwise(15, p[:D], p[D:])  # GLU over the channel halves
-            h = _dwconv(g, Cm["w_dw"], Cm["b_dw"], self.cfg.conv_kernel_size, 1)  # depthwise + folded BatchNorm + SiLU
+            h = _dwconv(g, Cm["w_dw"], Cm["b_dw"], self.cfg.conv_kernel_size, 1, lens if self.mask_padding else None)  # depthwise + folded BatchNorm + SiLU
             x = _conv_add(h, Cm["w_pw2"], Cm["b_pw2"], x)
             x = self._ffn(x, L["ffn2"])
             x = _layernorm(x, L["final"]["g"], L["final"]["b"])
@@ -375,8 +394,8 @@ class _Conformer:
 
 
 class _VariancePredictor:
-    def __init__(self, cfg: VariancePredictorConfig, sd: dict, prefix: str, dev):
-        self.cfg = cfg
+    def __init__(self, cfg: VariancePredictorConfig, sd: dict, prefix: str, dev, mask_padding: bool = False):
+        self.cfg, self.mask_padding = cfg, mask_padding
         put = lambda t: t.to(dev, torch.float32).contiguous()
         self.layers = []
         d = cfg.input_dim
@@ -392,15 +411,20 @@ class _VariancePredictor:
         self.w_lin, self.b_lin = put(sd[prefix + ".linear.weight"].unsqueeze(-1)), put(sd[prefix + ".linear.bias"])
 
     def forward(self, x, lens):
-        """x [D, B, L] -> [B, L] (zero at padded positions)."""
+        """x [D, B, L] -> [B, L] (zero at padded positions).  With ``mask_padding`` every layer's k > 1 convolution reads the columns at
+        or beyond lens[b] as zero (layer 0 too: the caller's tensor holds bucket embeddings there); x itself is left as it is."""
         k = self.cfg.kernel_size
+        mlens = lens if self.mask_padding else None
         for P in self.layers:
-            h = (_conv(_dwconv(x, P["w_dw"], P["b_dw"], k, 0), P["w_pw"], P["b_pw"], act=ops.ACT_RELU) if self.cfg.depthwise
-                 else _conv(x, P["w"], P["b"], k, act=ops.ACT_RELU))
+            if self.cfg.depthwise:
+                h = _conv(_dwconv(x, P["w_dw"], P["b_dw"], k, 0, mlens), P["w_pw"], P["b_pw"], act=ops.ACT_RELU)
+            else:
+                if mlens is not None and k > 1:  # (a copy at layer 0: the tensor is the caller's; the LayerNorm outputs are this function's)
+                    x = _mask_cols_(x.clone() if P is self.layers[0] else x, mlens)
+                h = _conv(x, P["w"], P["b"], k, act=ops.ACT_RELU)
             x = _layernorm(h, P["ln_g"], P["ln_b"])
         y = _conv(x, self.w_lin, self.b_lin)  # [1, B, L]
-        _chk(_lib.load().evmi_mask_cols_f32(y.data_ptr(), lens.data_ptr(), 1, y.shape[1], y.shape[2], _s(y)), "evmi_mask_cols_f32")
-        return y[0]
+        return _mask_cols_(y, lens)[0]
 
 
 class FastSpeech2:
@@ -435,15 +459,15 @@ class FastSpeech2:
         put = lambda t: t.to(dev, torch.float32).contiguous()
         self.table = put(sd["text_input_layer.weight"])
         self.inv_freq = put(sd["position_embedding.inv_freq"])
-        self.encoder = _Conformer(c.encoder, sd, "encoder", dev)
-        self.decoder = _Conformer(c.decoder, sd, "decoder", dev)
+        self.encoder = _Conformer(c.encoder, sd, "encoder", dev, c.mask_padding)
+        self.decoder = _Conformer(c.decoder, sd, "decoder", dev, c.mask_padding)
         self.speaker_table = put(sd["speaker_embedding.weight"]) if c.multispeaker else None
         self.language_table = put(sd["language_embedding.weight"]) if c.multilingual else None
         self.gst = StyleTokens(c, sd, dev) if c.use_global_style_token_module else None
         vp = c.variance_predictors
-        self.duration_predictor = _VariancePredictor(vp.duration, sd, "duration_predictor", dev)
-        self.pitch_predictor = _VariancePredictor(vp.pitch, sd, "pitch_predictor", dev)
-        self.energy_predictor = _VariancePredictor(vp.energy, sd, "energy_predictor", dev)
+        self.duration_predictor = _VariancePredictor(vp.duration, sd, "duration_predictor", dev, c.mask_padding)
+        self.pitch_predictor = _VariancePredictor(vp.pitch, sd, "pitch_predictor", dev, c.mask_padding)
+        self.energy_predictor = _VariancePredictor(vp.energy, sd, "energy_predictor", dev, c.mask_padding)
         lin = lambda st, n: torch.linspace(st.norm_min, st.norm_max, n - 1)
         self.pitch_bins = put(sd["pitch_bins"] if "pitch_bins" in sd else lin(self.stats.pitch, vp.pitch.n_bins))
         self.energy_bins = put(sd["energy_bins"] if "energy_bins" in sd else lin(self.stats.energy, vp.energy.n_bins))
@@ -657,6 +681,8 @@ class FastSpeech2:
         if self.postnet:
             h = mel
             for i, (w, b) in enumerate(self.postnet):
+                if c.mask_padding and i > 0:  # tanh(bias) beyond the length (layer 0 reads the masked mel): postnet_layers - 1 launches
+                    _mask_cols_(h, mel_lens)
                 h = _conv(h, w, b, c.postnet_kernel, act=ops.ACT_TANH if i < len(self.postnet) - 1 else ops.ACT_NONE)
             post = ops.axpby(1.0, mel, 1.0, h)
             _chk(lib.evmi_mask_cols_f32(post.data_ptr(), mel_lens.data_ptr(), c.n_mels, B, T, _s(x)), "evmi_mask_cols_f32")

@@ -284,16 +284,17 @@ def batchnorm(tape: Tape, x: Var, bn: Affine, act=ops.ACT_NONE, valid=None, item
     return y
 
 
-def dwconv(tape: Tape, x: Var, layer) -> Var:
-    """Depthwise convolution; ``layer``: Dense or WNConv with wshape (C, 1, k)."""
+def dwconv(tape: Tape, x: Var, layer, lens=None) -> Var:
+    """Depthwise convolution; ``layer``: Dense or WNConv with wshape (C, 1, k).  ``lens`` (int32 [B] on the device; ``model.mask_padding``):
+    the columns at or beyond lens[b] are absent in both directions -- read as zero, written as zero."""
     w, dw_sink = layer.effective(True)
     k = layer.k
-    y = Var(ops.dwconv_fwd(x.data, w, layer.bias_data(), k))
+    y = Var(ops.dwconv_fwd(x.data, w, layer.bias_data(), k, lens))
 
     def bwd():
         if y.grad is None:
             return
-        dx = ops.dwconv_bwd(x.data, w, y.grad, dw_sink, layer.db_sink(), k, need_dx=x.needs_grad)
+        dx = ops.dwconv_bwd(x.data, w, y.grad, dw_sink, layer.db_sink(), k, need_dx=x.needs_grad, lens=lens)
         if dx is not None:
             x.accumulate(dx)
 
@@ -651,15 +652,21 @@ class _ConformerT:
     def batchnorms(self):
         return [L["bn"] for L in self.layers]
 
-    def forward(self, tape: Tape, x: Var, lens32, seeds) -> Var:
+    def forward(self, tape: Tape, x: Var, lens32, seeds, mask: bool = False) -> Var:
+        """``mask`` (``model.mask_padding``): the depthwise convolution takes the columns at or beyond lens32[b] as
+        absent and the BatchNorm behind it runs over the valid columns only (statistics, output zero beyond, gradient ignored there)."""
         p = 0.0 if _EVAL[0] else self.cfg.dropout
+        B = x.data.shape[1]
         for L in self.layers:
             x = self._ffn_fwd(tape, x, L["ffn1"], p, seeds)
             h = ln_dense(tape, x, L["attn_ln"], L["in_proj"])
             h = attention(tape, h, lens32, self.cfg.heads, p, seeds(self.cfg.heads))
             x = dense_residual_dropout(tape, x, h, L["out_proj"], p, seeds())
             h = glu(tape, ln_dense(tape, x, L["conv_ln"], L["pw1"]))
-            h = batchnorm(tape, dwconv(tape, h, L["dw"]), L["bn"], ops.ACT_SILU)
+            if mask:
+                h = batchnorm(tape, dwconv(tape, h, L["dw"], lens32), L["bn"], ops.ACT_SILU, valid=lens32, items=B)
+            else:
+                h = batchnorm(tape, dwconv(tape, h, L["dw"]), L["bn"], ops.ACT_SILU)
             x = dense_residual_dropout(tape, x, h, L["pw2"], p, seeds())
             x = self._ffn_fwd(tape, x, L["ffn2"], p, seeds)
             x = layernorm(tape, x, L["final_ln"])
@@ -688,10 +695,15 @@ class _VariancePredictorT:
     def convs(self):
         return [c for conv, _ in self.layers for c in conv]
 
-    def forward(self, tape: Tape, x: Var, lens32, seeds) -> Var:
-        """x [D, B, L] -> [1, B, L], zero at the padded positions."""
+    def forward(self, tape: Tape, x: Var, lens32, seeds, mask: bool = False) -> Var:
+        """x [D, B, L] -> [1, B, L], zero at the padded positions.  ``mask`` (``model.mask_padding``): every layer's k > 1 convolution reads
+        the columns at or beyond lens32[b] as zero, layer 0 included (x holds bucket embeddings there)."""
+        mlens = lens32 if mask else None
         for conv, ln in self.layers:
-            h = dense(tape, dwconv(tape, x, conv[0]), conv[1], ops.ACT_RELU) if self.cfg.depthwise else dense(tape, x, conv[0], ops.ACT_RELU)
+            if self.cfg.depthwise:
+                h = dense(tape, dwconv(tape, x, conv[0], mlens), conv[1], ops.ACT_RELU)
+            else:
+                h = dense(tape, masked(tape, x, lens32) if mask and conv[0].k > 1 else x, conv[0], ops.ACT_RELU)
             x = dropout(tape, layernorm(tape, h, ln), 0.0 if _EVAL[0] else self.cfg.dropout, seeds())
         return masked(tape, dense(tape, x, self.linear), lens32)
 
@@ -1255,7 +1267,7 @@ class FastSpeech2Trainer(CapturedStep):
             align_join = self.aligner.forward(st.align.tape, ta, Var(b["mel_t"], needs_grad=False), b.get("attn_prior"), lens, b["mel_lens"], self._scal[2:3],
                                               tr.attn_ctc_loss_weight, self._bin_weight() > 0.0, self._scal[4:5], self._scal[5:6])
         x0 = embed_text(tape, text, lens, layer, self.inv_freq)
-        return self.encoder.forward(tape, x0, lens, st.seeds), align_join
+        return self.encoder.forward(tape, x0, lens, st.seeds, self.config.mask_padding), align_join
 
     def _durations_and_targets(self, st: _Step, align_join):
         """-> (cumulated durations [B, L] int32, log(1 + durations), variance targets: [B, L] for a phone-level predictor, the per-frame
@@ -1289,7 +1301,7 @@ class FastSpeech2Trainer(CapturedStep):
                 "energy": (self.energy_predictor, self.energy_bins, self.energy_table, tr.energy_loss_weight)}[key]
 
     def _predict(self, st: _Step, tape: Tape, name: str, predictor, x: Var, want, lens, count_dev, weight: float) -> None:
-        st.losses[name] = _LOSS[self.loss_kinds[name]](tape, predictor.forward(tape, x, lens, st.seeds), want.view(1, *want.shape), count_dev, weight)
+        st.losses[name] = _LOSS[self.loss_kinds[name]](tape, predictor.forward(tape, x, lens, st.seeds, self.config.mask_padding), want.view(1, *want.shape), count_dev, weight)
 
     def _run_predictors(self, st: _Step, jobs: list) -> None:
         for name, predictor, x, want, weight in jobs:
@@ -1347,13 +1359,16 @@ class FastSpeech2Trainer(CapturedStep):
         """Decoder, mel projection and postnet, with their losses."""
         tape, tr, mel_lens, mel_t = st.tape, self.training, st.batch["mel_lens"], st.batch["mel_t"]
         loss, n_el = _LOSS[self.loss_kinds["mel"]], self._scal[3:4]
-        y = self.decoder.forward(tape, f, mel_lens, st.seeds)
+        y = self.decoder.forward(tape, f, mel_lens, st.seeds, self.config.mask_padding)
         mel = masked(tape, dense(tape, y, self.mel_linear), mel_lens)
         st.losses["mel"] = loss(tape, mel, mel_t, n_el, tr.mel_loss_weight)
         if self.postnet:
             h = mel
+            # model.mask_padding: the BatchNorms over the valid frames only; their output is zero beyond the length, which is what the next
+            # k = 5 convolution has to read there (layer 0 reads the masked mel)
+            valid = dict(valid=mel_lens, items=st.meta["B"]) if self.config.mask_padding else {}
             for i, (conv, bn) in enumerate(self.postnet):
-                h = batchnorm(tape, dense(tape, h, conv), bn, ops.ACT_TANH if i < len(self.postnet) - 1 else ops.ACT_NONE)
+                h = batchnorm(tape, dense(tape, h, conv), bn, ops.ACT_TANH if i < len(self.postnet) - 1 else ops.ACT_NONE, **valid)
             post = masked(tape, residual(tape, mel, h), mel_lens)
             st.losses["postnet"] = loss(tape, post, mel_t, n_el, tr.postnet_loss_weight)
 

@@ -1261,26 +1261,35 @@ def batchnorm_bwd(x, gamma, beta, mean, rstd, dy, dgamma, dbeta, act=ACT_NONE, v
     return dx
 
 
-def dwconv_fwd(x, w, bias, k):
+def dwconv_fwd(x, w, bias, k, lens=None):
+    """``lens`` (int32 [B] on the device; ``model.mask_padding``): columns at or beyond lens[b] are read as zero
+    and written as zero."""
     y = torch.empty_like(x)
     C, B, T = x.shape
+    if lens is not None:
+        _chk(_lib.load().evmi_dwconv1d_cbt_lens_f32(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), lens.data_ptr(), y.data_ptr(), C, B, T, k, (k - 1) // 2, 0,
+                                                    _s(x)), "evmi_dwconv1d_cbt_lens_f32")
+        return y
     _chk(_lib.load().evmi_dwconv1d_cbt_f32(x.data_ptr(), w.data_ptr(), _lib.ptr(bias), y.data_ptr(), C, B, T, k, (k - 1) // 2, 0, _s(x)), "evmi_dwconv1d_cbt_f32")
     return y
 
 
-def dwconv_bwd(x, w, dy, dw, db, k, need_dx=True):
+def dwconv_bwd(x, w, dy, dw, db, k, need_dx=True, lens=None):
+    """``lens``: the backward of ``dwconv_fwd(..., lens)`` -- dy and x count as zero at or beyond lens[b], dx is zero there."""
     C, B, T = x.shape
     dx = torch.empty_like(x) if need_dx else None
     lib = _lib.load()
     n = lib.evmi_dwconv1d_bwd_cbt_f32_ws_elems(C, B, k)
+    if lens is None:
+        entry = lambda *a: _chk(lib.evmi_dwconv1d_bwd_cbt_f32(x.data_ptr(), w.data_ptr(), dy.data_ptr(), *a), "evmi_dwconv1d_bwd_cbt_f32")
+    else:
+        entry = lambda *a: _chk(lib.evmi_dwconv1d_bwd_cbt_lens_f32(x.data_ptr(), w.data_ptr(), dy.data_ptr(), lens.data_ptr(), *a), "evmi_dwconv1d_bwd_cbt_lens_f32")
     side = side_wgrad(x, dy, dw, db).mark()
     if need_dx:
-        _chk(lib.evmi_dwconv1d_bwd_cbt_f32(x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), 0, 0, 0, 0, C, B, T, k, (k - 1) // 2, _s(x)),
-             "evmi_dwconv1d_bwd_cbt_f32")
+        entry(dx.data_ptr(), 0, 0, 0, 0, C, B, T, k, (k - 1) // 2, _s(x))
     def launch():  # the filter / bias gradient (partial sums per item, then the reduction) beside the chain, issued behind dx
         ws = WS.get("dw_bwd", n, x.device)
-        _chk(lib.evmi_dwconv1d_bwd_cbt_f32(x.data_ptr(), w.data_ptr(), dy.data_ptr(), 0, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, C, B, T, k,
-                                           (k - 1) // 2, _s(x)), "evmi_dwconv1d_bwd_cbt_f32")
+        entry(0, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), n, C, B, T, k, (k - 1) // 2, _s(x))
     side.run(launch)
     return dx
 

@@ -953,6 +953,16 @@ long long evmi_dwconv1d_bwd_cbt_f32_ws_elems(int C, int B, int k);
 int evmi_dwconv1d_bwd_cbt_f32(const float* x_dev, const float* w_dev, const float* dy_dev, float* dx_dev, float* dw_dev,
                               float* db_dev, float* ws_dev, long long ws_elems, int C, int B, int T, int k, int pad,
                               void* stream);
+/* The depthwise convolution and its backward with per-item lengths (csrc/fs2_lens_ops.hip; model.mask_padding, DESIGN.md
+ * section 29).  lens_dev: int32 [B] on the device, clamped to [0, T] in the kernels.  Columns t >= lens[b] are absent: read as zero
+ * whatever they hold (NaN included) and written as zero (y, dx); dw / db sum over the valid columns.  Otherwise the contracts, the
+ * accumulation order and the activation formulas of evmi_dwconv1d_cbt_f32 / evmi_dwconv1d_bwd_cbt_f32: with every length equal to T
+ * y and dx carry their bits.  bias_dev may be NULL; the backward takes the workspace of evmi_dwconv1d_bwd_cbt_f32_ws_elems. */
+int evmi_dwconv1d_cbt_lens_f32(const float* x_dev, const float* w_dev, const float* bias_dev, const int* lens_dev, float* y_dev,
+                               int C, int B, int T, int k, int pad, int act, void* stream);
+int evmi_dwconv1d_bwd_cbt_lens_f32(const float* x_dev, const float* w_dev, const float* dy_dev, const int* lens_dev, float* dx_dev,
+                                   float* dw_dev, float* db_dev, float* ws_dev, long long ws_elems, int C, int B, int T, int k,
+                                   int pad, void* stream);
 /* Multi-head self-attention in TRAINING mode (csrc/attention_train.hip; the reference reaches torch.nn.MultiheadAttention
  * through torchaudio's Conformer inside the absent submodule FastSpeech2_lightning; SURVEY.md 8b names evmi_mha_{fwd,bwd}).
  * qkv [3D][B][T] channel-major, lens [B] = key padding mask.  Forward: out [D][B][T] and the per-query log-sum-exp
