@@ -1,45 +1,142 @@
-"""ctypes binding of libevmi_hip.so (the C ABI declared in include/evmi.h).
+"""ctypes binding of libevmi_hip.so, derived from include/evmi.h: the header is the one description of the C ABI.
 
-There is NO fallback: if the shared library is missing or a symbol is absent, importing the
-compute modules fails loudly — the product never silently runs a CPU or eager-PyTorch path.
+Importing this module reads the header once: its constants become module attributes (EVMI_OK, EVMI_ERR_*, EVMI_PREC_*, EVMI_MAX_*,
+EVMI_ABI_VERSION) and every function it declares gets its restype / argtypes in SYMBOLS.  Only the six structs that Python fills or
+reads field by field are mirrored by hand (tests/test_header_binding.py holds them to the header).
+
+There is NO fallback: if the header or the shared library is missing or a symbol is absent, importing the compute modules fails
+loudly -- the product never silently runs a CPU or eager-PyTorch path, and never binds from a table of its own.
 """
 
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from pathlib import Path
+from typing import NamedTuple
 
 _HERE = Path(__file__).resolve().parent
 LIB_NAME = "libevmi_hip.so"
-
-EVMI_OK = 0
-EVMI_ERR_INVALID_ARG = 1
-EVMI_ERR_NOT_READY = 3
-EVMI_ERR_UNSUPPORTED = 4
-EVMI_PREC_BF16 = 0
-EVMI_PREC_F32 = 1
-EVMI_MAX_UPSAMPLES = 8
-EVMI_MAX_RESBLOCK_KERNELS = 8
-EVMI_MAX_DILATIONS = 8
+HEADER = _HERE.parent / "include" / "evmi.h"
 
 
 class EvmiError(RuntimeError):
     """A libevmi_hip call returned a non-zero status."""
 
 
+# ---- the header ----------------------------------------------------------------------------------------------------------------------
+class Header(NamedTuple):
+    constants: dict     # name -> int: the members of the enums and the integer #defines
+    structs: dict       # name -> [(C type, member, [extents])] of every struct defined with a body
+    declarations: list  # [(name, return C type, [(parameter C type, parameter name)])] in the header's order
+
+
+_FUNCTION = re.compile(r"([\w\s*]+?)\b(\w+)\s*\(([^()]*)\)\s*;")
+_STRUCT = re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_DECLARATOR = re.compile(r"(\w+)((?:\s*\[\s*\w+\s*\])*)")
+
+
+def _c_type(text: str) -> str:
+    """'const  float *const *' -> 'const float* const*'."""
+    return re.sub(r"\s+\*", "*", " ".join(text.replace("*", "* ").split()))
+
+
+def _typed_name(text: str, where: str):
+    """'const float* x_dev' -> ('const float*', 'x_dev', ''); a struct member may carry extents: 'char kernel[48]'."""
+    m = re.fullmatch(r"(.*[\s*])" + _DECLARATOR.pattern, text.strip(), flags=re.S)
+    if not m:
+        raise ValueError(f"{where}: cannot read {' '.join(text.split())!r} as a type and a name")
+    return _c_type(m.group(1)), m.group(2), m.group(3)
+
+
+def parse_header(text: str) -> Header:
+    """Reads the subset of C that include/evmi.h is written in.  Anything else raises: the parser never guesses and never skips."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {name: int(value) for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+
+    def enum(m):
+        for item in filter(None, (" ".join(i.split()) for i in m.group(1).split(","))):
+            im = re.fullmatch(r"(\w+) = (-?\d+)", item)
+            if not im:
+                raise ValueError(f"enum member {item!r}: only `NAME = integer` is read")
+            constants[im.group(1)] = int(im.group(2))
+        return " "
+
+    text = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, text)
+
+    def extent(e, where):
+        if not (e.isdigit() or e in constants):
+            raise ValueError(f"{where}: unknown array extent {e!r}")
+        return int(e) if e.isdigit() else constants[e]
+
+    structs = {}
+
+    def struct(m):
+        members, name = [], m.group(2)
+        for line in filter(None, (s.strip() for s in m.group(1).split(";"))):
+            ctype = None
+            for d in line.split(","):  # `int c_in, c_out;`: the later declarators repeat the first one's type
+                if ctype and "*" in ctype:
+                    raise ValueError(f"struct {name}: {line!r}: one pointer member per declaration")
+                ctype, member, extents = _typed_name(f"{ctype} {d}" if ctype else d, f"struct {name}")
+                members.append((ctype, member, [extent(e, f"{name}.{member}") for e in re.findall(r"\w+", extents)]))
+        structs[name] = members
+        return " "
+
+    text = _STRUCT.sub(struct, text)
+    text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", " ", text)  # opaque handles
+    declarations = []
+
+    def function(m):
+        name = m.group(2)
+        params = [] if m.group(3).strip() in ("", "void") else [_typed_name(p, name) for p in m.group(3).split(",")]
+        if any(extents for _, _, extents in params):
+            raise ValueError(f"{name}: array parameters are not read")
+        declarations.append((name, _c_type(m.group(1)), [p[:2] for p in params]))
+        return " "
+
+    rest = re.sub(r'extern\s+"C"\s*\{', " ", _FUNCTION.sub(function, text)).split()
+    if rest not in ([], ["}"]):
+        raise ValueError(f"not read as a declaration: {' '.join(rest)[:200]!r}")
+    return Header(constants, structs, declarations)
+
+
+def _read_header() -> Header:
+    if not HEADER.exists():
+        raise ImportError(f"{HEADER} not found: the ctypes binding is derived from it and there is no built-in table.")
+    return parse_header(HEADER.read_text())
+
+
+_HEADER = _read_header()  # once per process
+_K = _HEADER.constants
+globals().update(_K)  # EVMI_OK, EVMI_ERR_*, EVMI_PREC_*, EVMI_MAX_*, EVMI_ABI_VERSION as module attributes
+
+
+def declarations() -> list:
+    """Every function include/evmi.h declares: [(name, return C type, [(parameter C type, parameter name)])]."""
+    return _HEADER.declarations
+
+
+def struct_members() -> dict:
+    """Every struct include/evmi.h defines: name -> [(C type, member, [array extents])]."""
+    return _HEADER.structs
+
+
+# ---- the structs Python fills or reads by field -----------------------------------------------------------------------------------
 class GeneratorConfig(C.Structure):
     _fields_ = [
         ("n_mels", C.c_int),
         ("upsample_initial_channel", C.c_int),
         ("num_upsamples", C.c_int),
-        ("upsample_rates", C.c_int * EVMI_MAX_UPSAMPLES),
-        ("upsample_kernel_sizes", C.c_int * EVMI_MAX_UPSAMPLES),
+        ("upsample_rates", C.c_int * _K["EVMI_MAX_UPSAMPLES"]),
+        ("upsample_kernel_sizes", C.c_int * _K["EVMI_MAX_UPSAMPLES"]),
         ("resblock_type", C.c_int),
         ("num_kernels", C.c_int),
-        ("resblock_kernel_sizes", C.c_int * EVMI_MAX_RESBLOCK_KERNELS),
-        ("num_dilations", C.c_int * EVMI_MAX_RESBLOCK_KERNELS),
-        ("resblock_dilations", (C.c_int * EVMI_MAX_DILATIONS) * EVMI_MAX_RESBLOCK_KERNELS),
+        ("resblock_kernel_sizes", C.c_int * _K["EVMI_MAX_RESBLOCK_KERNELS"]),
+        ("num_dilations", C.c_int * _K["EVMI_MAX_RESBLOCK_KERNELS"]),
+        ("resblock_dilations", (C.c_int * _K["EVMI_MAX_DILATIONS"]) * _K["EVMI_MAX_RESBLOCK_KERNELS"]),
         ("lrelu_slope", C.c_float),
         ("post_lrelu_slope", C.c_float),
         ("istft_layer", C.c_int),
@@ -75,262 +172,35 @@ class LnPartials(C.Structure):  # evmi_ln_partials
     _fields_ = [("ws", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("C", C.c_int), ("n_cols", C.c_longlong)]
 
 
-# name -> (restype, argtypes); every symbol include/evmi.h declares
-SYMBOLS = {
-    "evmi_tm_colsum_batch_bf16": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_conv_pkflat_ws_elems": (C.c_longlong, [C.c_int] * 10),
-    "evmi_conv_pkflat_plan": (C.c_int, [C.c_int] * 10),
-    "evmi_conv_pkflat_tab": (C.c_int, [C.c_int] * 10 + [C.c_void_p, C.c_longlong, C.c_void_p]),
-    "evmi_conv_pkflat_frag_elems": (C.c_longlong, [C.c_int] * 6),
-    "evmi_conv_pkflat_fragments": (C.c_int, [C.c_int, C.POINTER(PkFlatJob), C.c_void_p]),
-    "evmi_conv_pkflat_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
-                             + [C.c_int] * 12 + [C.c_float, C.c_void_p]),
-    "evmi_conv_pkflat_dgrad": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_int] * 11
-                               + [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_void_p]),
-    "evmi_conv_pkflat_wgrad_ws_elems": (C.c_longlong, [C.c_int] * 8),
-    "evmi_conv_pkflat_wgrad": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 10
-                               + [C.c_void_p]),
-    "evmi_pkflat_zero": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
-    "evmi_disc_first_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 6
-                            + [C.c_float, C.c_void_p]),
-    "evmi_disc_first_wgrad_ws_elems": (C.c_longlong, [C.c_int] * 4),
-    "evmi_disc_first_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_longlong] + [C.c_int] * 5 + [C.c_void_p]),
-    "evmi_disc_first_dgrad": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_disc_post_fwd_ws_elems": (C.c_longlong, [C.c_int] * 3),
-    "evmi_disc_post_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
-                                     C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_disc_post_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 6
-                             + [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_void_p]),
-    "evmi_disc_post_wgrad_ws_elems": (C.c_longlong, [C.c_int] * 4),
-    "evmi_disc_post_wgrad": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
-                             + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_pkflat_absdiff_ws_elems": (C.c_longlong, [C.c_int]),
-    "evmi_pkflat_absdiff": (C.c_int, [C.c_int, C.POINTER(PkFlatPair), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
-    "evmi_pkflat_rowsum_ws_elems": (C.c_longlong, [C.c_int, C.POINTER(PkFlatRows)]),
-    "evmi_pkflat_rowsum": (C.c_int, [C.c_int, C.POINTER(PkFlatRows), C.c_void_p, C.c_longlong, C.c_void_p]),
-    "evmi_abi_version": (C.c_int, []),
-    "evmi_last_error": (C.c_char_p, []),
-    "evmi_device_info": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
-    "evmi_length_regulate": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
-    ),
-    "evmi_length_regulate_bwd_f32": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
-    ),
-    "evmi_conv1d_f32": (
-        C.c_int,
-        [C.c_void_p] * 5 + [C.c_int] * 9 + [C.c_float, C.c_float, C.c_int, C.c_void_p],
-    ),
-    "evmi_conv_transpose1d_f32": (
-        C.c_int,
-        [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_float, C.c_void_p],
-    ),
-    "evmi_mel_spectrogram_f32": (
-        C.c_int,
-        [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p],
-    ),
-    "evmi_mel_spectrogram_ragged_f32": (
-        C.c_int,
-        [C.c_void_p] * 7 + [C.c_int] * 7 + [C.c_void_p],
-    ),
-    "evmi_mel_spectrogram_win_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 8 + [C.c_void_p]),
-    "evmi_mel_spectrogram_plan": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_longlong)]),
-    "evmi_spectrogram_layout_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_gemm_f32": (C.c_int, [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
-    "evmi_conv1d_cbt_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong] + [C.c_int] * 15 + [C.c_float, C.c_void_p]),
-    "evmi_conv1d_cbt_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong] + [C.c_int] * 15 + [C.c_float, C.c_void_p]),
-    "evmi_conv1d_cbt_bf16pk": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong] + [C.c_int] * 15 + [C.c_float, C.c_void_p]),
-    "evmi_conv1d_cbt_bf16pk_ws_elems": (C.c_longlong, [C.c_int] * 10),
-    "evmi_conv1d_cbt_bf16pk_plan": (C.c_int, [C.c_int] * 10),
-    "evmi_conv1d_cbt_bf16_rounds": (C.c_int, [C.c_int] * 10),
-    "evmi_conv1d_dgrad_cbt_bf16pk_plan": (C.c_int, [C.c_int] * 10),
-    "evmi_conv1d_wgrad_cbt_bf16pk_plan": (C.c_int, [C.c_int] * 10),
-    "evmi_conv1d_dgrad_cbt_bf16pk": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 10 + [C.c_void_p]),
-    "evmi_conv1d_dgrad_cbt_bf16pk_ws_elems": (C.c_longlong, [C.c_int] * 10),
-    "evmi_conv1d_cbt_f32_ws_elems": (C.c_longlong, [C.c_int] * 6),
-    "evmi_conv1d_cbt_f32_supported": (C.c_int, [C.c_int] * 9),
-    "evmi_conv1d_dgrad_cbt_f32_ws_elems": (C.c_longlong, [C.c_int] * 10),
-    "evmi_conv1d_dgrad_cbt_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 10 + [C.c_void_p]),
-    "evmi_conv1d_dgrad_cbt_bf16": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 10 + [C.c_void_p]),
-    "evmi_weight_norm_fwd_batched_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]),
-    "evmi_weight_norm_bwd_batched_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]),
-    "evmi_istft_polar_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p]),
-    "evmi_istft_polar_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p]),
-    "evmi_reflect_pad_left1_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_conv1d_wgrad_cbt_bf16pk_ws_elems": (C.c_longlong, [C.c_int] * 10),
-    "evmi_conv1d_wgrad_cbt_bf16pk": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 11 + [C.c_void_p]),
-    "evmi_conv1d_cbt_bf16pk_fused": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong] + [C.c_int] * 12 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
-    "evmi_conv1d_dgrad_cbt_bf16pk_fused": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 10 + [C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
-    "evmi_conv1d_dgrad_cbt_bf16pk_staged": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 10 + [C.c_void_p]),
-    "evmi_layernorm_pack_bf16pk": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
-    "evmi_layernorm_pack_bf16pk_w": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
-                                                                                                   C.c_int, C.c_void_p]),
-    "evmi_conv1d_cbt_bf16pk_prepacked": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p]),
-    "evmi_conv1d_cbt_bf16pk_silu_dropout": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong] + [C.c_int] * 6 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_conv1d_cbt_bf16pk_resdrop": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_longlong] + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_float, C.c_ulonglong,
-                                                  C.c_float, C.c_void_p, C.c_void_p]),
-    "evmi_conv1d_dgrad_cbt_bf16pk_staged_dropout": (C.c_int, [C.c_int, C.c_void_p, C.c_float, C.c_ulonglong, C.c_void_p, C.c_float] + [C.c_void_p] * 3
-                                                    + [C.c_longlong] + [C.c_int] * 10 + [C.c_void_p]),
-    "evmi_conv1d_dgrad_cbt_bf16pk_staged_silu_dropout": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_ulonglong, C.c_void_p] + [C.c_void_p] * 3
-                                                         + [C.c_longlong] + [C.c_int] * 10 + [C.c_void_p]),
-    "evmi_conv1d_cbt_bf16pk_ffn_up": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 5
-                                      + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_int, C.c_void_p]),
-    "evmi_conv1d_dgrad_cbt_bf16pk_ffn_down": (C.c_int, [C.c_void_p] * 2 + [C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 5
-                                              + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_conv1d_wgrad_cbt_bf16pk_prepacked": (C.c_int, [C.c_void_p] * 6 + [C.c_longlong] + [C.c_int] * 11 + [C.c_void_p]),
-    "evmi_conv1d_bf16pk_shares_packed": (C.c_int, [C.c_int] * 7),
-    "evmi_conv1d_wgrad_cbt_bf16pk_fused": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 11 + [C.c_float, C.c_void_p, C.c_float, C.c_void_p]),
-    "evmi_conv1d_wgrad_cbt_f32_ws_elems": (C.c_longlong, [C.c_int] * 10),
-    "evmi_conv1d_wgrad_cbt_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 11 + [C.c_void_p]),
-    "evmi_fs2_embed_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_fs2_add_posemb_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_mask_cols_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_layernorm_cbt_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
-    "evmi_dwconv1d_cbt_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_fs2_bucket_embed_add_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
-    "evmi_fs2_durations_i32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_float, C.c_void_p]),
-    "evmi_length_regulate_cbt_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_attention_cbt_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_attention_cbt_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_fs2_add_item_embedding_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_attention_prior_f64": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_align_attention_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
-    "evmi_forward_sum_loss_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
-    "evmi_binarization_partials_f64": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_longlong, C.c_void_p]),
-    "evmi_monotonic_align_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_layernorm_bwd_cbt_f32_ws_elems": (C.c_longlong, [C.c_int, C.c_longlong]),
-    "evmi_layernorm_bwd_cbt_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_longlong, C.c_int, C.c_longlong, C.c_float, C.c_int, C.c_void_p]),
-    "evmi_layernorm_bwd_partials_reduce": (C.c_int, [C.c_int, C.POINTER(LnPartials), C.c_void_p]),
-    "evmi_batchnorm_fwd_cbt_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_longlong, C.c_float, C.c_float, C.c_int, C.c_void_p]),
-    "evmi_batchnorm_bwd_cbt_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
-    "evmi_batchnorm_fwd_valid_cbt_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_longlong, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                   C.c_void_p]),
-    "evmi_batchnorm_bwd_valid_cbt_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_dwconv1d_bwd_cbt_f32_ws_elems": (C.c_longlong, [C.c_int] * 3),
-    "evmi_dwconv1d_bwd_cbt_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_longlong] + [C.c_int] * 5 + [C.c_void_p]),
-    "evmi_dwconv1d_cbt_lens_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_dwconv1d_bwd_cbt_lens_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_longlong] + [C.c_int] * 5 + [C.c_void_p]),
-    "evmi_mha_fwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_mha_fwd_bf16": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_mha_bwd_bf16": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_mha_bwd_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    # any head dimension up to 256 (csrc/attention_generic.hip): the argument lists of the six entry points above
-    "evmi_attention_generic_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_attention_generic_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_mha_generic_fwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_mha_generic_fwd_bf16": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_mha_generic_bwd_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_mha_generic_bwd_bf16": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_softmax_rows_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float, C.c_ulonglong, C.c_void_p]),
-    "evmi_softmax_bwd_rows_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_ulonglong, C.c_void_p]),
-    "evmi_glu_bwd_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_void_p]),
-    "evmi_dropout_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_longlong, C.c_float, C.c_ulonglong, C.c_void_p, C.c_void_p]),
-    "evmi_dropout_fused_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_longlong, C.c_float, C.c_ulonglong, C.c_void_p, C.c_float, C.c_void_p]),
-    "evmi_fs2_embed_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
-    "evmi_fs2_bucket_embed_bwd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
-    "evmi_fs2_item_embedding_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_length_regulate_bwd_cbt_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_forward_sum_grad_f32_ws_elems": (C.c_longlong, [C.c_int] * 3),
-    "evmi_forward_sum_grad_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_longlong] + [C.c_int] * 3 + [C.c_float, C.c_float, C.c_void_p]),
-    "evmi_align_attention_bwd_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 3 + [C.c_float, C.c_void_p, C.c_void_p]),
-    "evmi_align_qk_grad_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
-    "evmi_dgrad_weights_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_gemm_batched_f32": (C.c_int, [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
-    "evmi_unfold_cbt_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
-    "evmi_fold_cbt_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
-    "evmi_bias_add_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p]),
-    "evmi_lrelu_bwd_rowsum_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_float, C.c_int, C.c_void_p]),
-    "evmi_row_reduce_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_int, C.c_void_p]),
-    "evmi_elementwise_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_void_p]),
-    "evmi_scalar_reduce_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_int, C.c_void_p]),
-    "evmi_avgpool4s2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_period_view_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_stft_frames_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_weight_norm_fwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
-    "evmi_weight_norm_bwd_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
-    "evmi_normalize_vec_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
-    "evmi_generator_bf16_check": (C.c_int, [C.POINTER(GeneratorConfig)]),
-    "evmi_conv_generic_weight_elems": (C.c_longlong, [C.c_int] * 3),
-    "evmi_conv_generic_relayout_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_conv_generic_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_longlong] * 3 + [C.c_float] * 3 + [C.c_int, C.c_void_p]),
-    "evmi_istft_head_weight_elems": (C.c_longlong, [C.c_int] * 2),
-    "evmi_istft_head_frame_tile": (C.c_int, [C.c_int] * 2),
-    "evmi_istft_head_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_conv_tc_supported": (C.c_int, [C.c_int] * 4),
-    "evmi_conv_tc_relayout_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
-    "evmi_conv_tc_tile_layout": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3),
-    "evmi_conv_tc_relayout_batched_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_resblock_pair_plan": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_longlong)]),
-    "evmi_resblock_branch_plan": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int)] * 3),
-    "evmi_resblock_pair_relayout_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3),
-    "evmi_resblock_pair_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_float] * 3 + [C.c_int, C.c_int, C.c_void_p]),
-    "evmi_resblock_branch_bf16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p] + [C.c_int] * 5
-                                  + [C.POINTER(C.c_int)] + [C.c_float] * 3 + [C.c_int, C.c_int, C.c_void_p]),
-    "evmi_conv_tc_tm_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 8 + [C.c_float] * 4 + [C.c_void_p]),
-    "evmi_conv1d_wgrad_tm_bf16_ws_elems": (C.c_longlong, [C.c_longlong] + [C.c_int] * 4),
-    "evmi_conv1d_wgrad_tm_bf16": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong, C.c_longlong] + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_tm_colsum_bf16_ws_elems": (C.c_longlong, [C.c_longlong, C.c_int]),
-    "evmi_tm_colsum_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_cbt_f32_to_tm_bf16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_void_p]),
-    "evmi_tm_bf16_to_cbt_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
-    "evmi_tm_lrelu_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p]),
-    "evmi_optimizer_step_lrdev_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p, C.c_float, C.c_void_p]),
-    "evmi_store_f32": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
-    "evmi_store_u64": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_void_p]),
-    "evmi_optimizer_step_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_longlong] + [C.c_float] * 5 + [C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
-    "evmi_comm_unique_id": (C.c_int, [C.c_void_p]),
-    "evmi_comm_init_rank": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int]),
-    "evmi_comm_destroy": (C.c_int, [C.c_void_p]),
-    "evmi_allreduce_bucket": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p]),
-    "evmi_loudness_lkfs_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_loudness_scratch_elems": (C.c_longlong, [C.c_int] * 4),
-    "evmi_pitch_acf_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p]),
-    "evmi_pitch_world_ws_elems": (C.c_longlong, [C.c_int] * 5 + [C.c_float] * 3),
-    "evmi_pitch_world_f64": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 5 + [C.c_float] * 4 + [C.c_void_p]),
-    "evmi_pitch_world_decimator": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
-    "evmi_peak_normalize_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
-    "evmi_sox_silence_ws_bytes": (C.c_longlong, [C.c_int] * 4),
-    "evmi_sox_silence_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_int] * 5 + [C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
-    "evmi_sox_reverse_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p]),
-    "evmi_transpose_bct_cbt_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_counter_add_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "evmi_spectral_norm_grad_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
-    "evmi_ratio_accumulate_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
-    "evmi_adamw_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
-    "evmi_gst_conv2d_fwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_gst_conv2d_fwd_rows_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_gst_conv2d_dgrad_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
-    "evmi_gst_conv2d_wgrad_ws_elems": (C.c_longlong, [C.c_int] * 5),
-    "evmi_gst_conv2d_wgrad_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_longlong] + [C.c_int] * 6 + [C.c_void_p]),
-    "evmi_gst_gru_fwd_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_gst_gru_bwd_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_gst_gru_fwd_steps_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_gst_gru_bwd_steps_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 3 + [C.c_void_p]),
-    "evmi_gst_attention_fwd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_gst_attention_bwd_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p]),
-    "evmi_generator_create": (C.c_int, [C.POINTER(GeneratorConfig), C.c_int, C.POINTER(C.c_void_p)]),
-    "evmi_generator_destroy": (None, [C.c_void_p]),
-    "evmi_generator_set_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
-    "evmi_generator_num_weights": (C.c_int, [C.c_void_p]),
-    "evmi_generator_weight_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
-    "evmi_generator_finalize": (C.c_int, [C.c_void_p]),
-    "evmi_generator_hop": (C.c_int, [C.c_void_p]),
-    "evmi_generator_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "evmi_generator_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_generator_forward_profiled": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(LaunchRecord), C.c_int, C.POINTER(C.c_int)],
-    ),
-    "evmi_generator_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "evmi_generator_forward_lens_profiled": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(LaunchRecord), C.c_int, C.POINTER(C.c_int)],
-    ),
-    "evmi_generator_macs_per_sample": (C.c_double, [C.c_void_p]),
-}
+MIRRORS = {"evmi_generator_config": GeneratorConfig, "evmi_launch_record": LaunchRecord, "evmi_pkflat_job": PkFlatJob,
+           "evmi_pkflat_pair": PkFlatPair, "evmi_pkflat_rows": PkFlatRows, "evmi_ln_partials": LnPartials}
+
+# ---- C types -> ctypes ------------------------------------------------------------------------------------------------------------
+# A single pointer to a mirrored struct is POINTER(mirror); every other pointer is c_void_p, pointers to pointers and the opaque
+# evmi_generator* included: the header cannot say whether an int* is a host out-parameter or a device buffer, so none is typed
+# (c_void_p takes an address, None, byref(...) and a ctypes array alike).
+C_TYPES = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
+           "int64_t": C.c_int64, "char*": C.c_char_p}
+
+
+def _ctypes_of(c_type: str, where: str, returned: bool = False):
+    bare = " ".join(w for w in c_type.replace("*", " * ").split() if w != "const").replace(" *", "*")
+    if bare in C_TYPES:
+        return C_TYPES[bare]
+    if bare == "void" and returned:
+        return None
+    if bare.endswith("*"):
+        return C.POINTER(MIRRORS[bare[:-1]]) if bare[:-1] in MIRRORS else C.c_void_p
+    raise TypeError(f"{where}: no ctypes type is given for the C type {c_type!r}")
+
+
+def bind_types(decls) -> dict:
+    """name -> (restype, argtypes) of the given declarations; a C type outside the table above raises, naming symbol and parameter."""
+    return {name: (_ctypes_of(ret, f"{name}: return type", returned=True), [_ctypes_of(t, f"{name}: parameter {p}") for t, p in params])
+            for name, ret, params in decls}
+
+
+SYMBOLS = bind_types(declarations())  # name -> (restype, argtypes); every symbol include/evmi.h declares
 
 _lib = None
 
@@ -356,14 +226,14 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.evmi_abi_version() != 2:
-        raise ImportError(f"{path}: ABI version {lib.evmi_abi_version()} != 2")
+    if lib.evmi_abi_version() != _K["EVMI_ABI_VERSION"]:
+        raise ImportError(f"{path}: ABI version {lib.evmi_abi_version()} != {_K['EVMI_ABI_VERSION']} of {HEADER}")
     _lib = lib
     return lib
 
 
 def check(rc: int, what: str = "") -> None:
-    if rc != EVMI_OK:
+    if rc != _K["EVMI_OK"]:
         msg = load().evmi_last_error()
         raise EvmiError(f"{what or 'libevmi_hip'} failed (code {rc}): {msg.decode() if msg else '?'}")
 

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .train import ops
+from .train.ops import _chk, _s
 
 
 @dataclass
@@ -116,14 +117,6 @@ N_PHONOLOGICAL_FEATURES = 43  # everyvoice/text/features.py:7
 
 _LN_EPS = 1e-5
 _BN_EPS = 1e-5
-
-
-def _chk(rc, what):
-    _lib.check(rc, what)
-
-
-def _s(t):
-    return _lib.current_stream_ptr(t.device)
 
 
 def _conv(x, w, b, k=1, act=ops.ACT_NONE):

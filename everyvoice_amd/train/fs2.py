@@ -37,6 +37,7 @@ from ..fs2 import N_PHONOLOGICAL_FEATURES, FastSpeech2ModelConfig, Stats, apply_
 from . import ops
 from .autograd import _ACTIVATION_ELEMS, Tape, Var, alias
 from .layers import ParamGroup, WNBatch, WNConv
+from .ops import _chk, _s
 from .step import EAGER, BucketReducer, CapturedStep, SideBranch, _held_tensors, on_own_stream, step_scope  # noqa: F401 (_held_tensors: its old home)
 
 
@@ -119,14 +120,6 @@ class FastSpeech2TrainingConfig:
             else:
                 out[k] = v
         return out
-
-
-def _s(t):
-    return _lib.current_stream_ptr(t.device)
-
-
-def _chk(rc, what):
-    _lib.check(rc, what)
 
 
 # ---- parameter holders (names = the reference state dict) ---------------------------------------------------------------

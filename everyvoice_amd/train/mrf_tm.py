@@ -46,10 +46,6 @@ class TMBuf:
         return body[:, self.PL: self.PL + self.T]
 
 
-def _s(device):
-    return _lib.current_stream_ptr(device)
-
-
 def stage_supported(C: int, kernel_sizes, dilations) -> bool:
     lib = _lib.load()
     if C % 8 or C < 32 or C > 256:
@@ -135,7 +131,7 @@ class MRFStageTM:
             self._table_base, self._base_w = base, min(ws, key=lambda w: w.data_ptr())
             self._ks_max = max(c.k for c in layers)
         _lib.check(lib.evmi_conv_tc_relayout_batched_f32(base, self._arena.data_ptr(), self._table.data_ptr(), self._table.shape[0], self.C, self._ks_max,
-                                                         _s(self.device)), "evmi_conv_tc_relayout_batched_f32")
+                                                         _lib.current_stream_ptr(self.device)), "evmi_conv_tc_relayout_batched_f32")
 
     def _laid_ptr(self, layer, transpose: bool) -> int:
         return self._arena.data_ptr() + 2 * self._w_off[(id(layer), transpose)]
@@ -145,7 +141,7 @@ class MRFStageTM:
         ops._count_conv(x.B, x.T, self.C, self.C, k)
         _lib.check(_lib.load().evmi_conv_tc_tm_bf16(x.ptr, w_laid, bias.data_ptr(), res.ptr if res is not None else 0,
                                                     mask.ptr if mask is not None else 0, out.ptr, x.B, x.T, x.Tp, x.PL, self.C, self.C, k, dil,
-                                                    float(pre), float(post), float(mask_slope), 1.0, _s(self.device)), "evmi_conv_tc_tm_bf16")
+                                                    float(pre), float(post), float(mask_slope), 1.0, _lib.current_stream_ptr(self.device)), "evmi_conv_tc_tm_bf16")
 
     def _wgrad(self, x: TMBuf, dy: TMBuf, dw: torch.Tensor, k, dil):
         lib = _lib.load()
@@ -153,13 +149,13 @@ class MRFStageTM:
         n = lib.evmi_conv1d_wgrad_tm_bf16_ws_elems(x.rows, self.C, self.C, k, dil)
         ws = ops.WS.get("tm_wgrad", n, self.device)
         _lib.check(lib.evmi_conv1d_wgrad_tm_bf16(x.ptr, dy.ptr, dw.data_ptr(), ws.data_ptr(), n, x.rows, self.C, self.C, k, dil * (k - 1) // 2, dil, 1,
-                                                 _s(self.device)), "evmi_conv1d_wgrad_tm_bf16")
+                                                 _lib.current_stream_ptr(self.device)), "evmi_conv1d_wgrad_tm_bf16")
 
     def _colsum(self, dy: TMBuf, db: torch.Tensor):
         lib = _lib.load()
         n = lib.evmi_tm_colsum_bf16_ws_elems(dy.rows, self.C)
         ws = ops.WS.get("tm_colsum", n, self.device)
-        _lib.check(lib.evmi_tm_colsum_bf16(dy.ptr, db.data_ptr(), ws.data_ptr(), n, dy.rows, self.C, 1, _s(self.device)), "evmi_tm_colsum_bf16")
+        _lib.check(lib.evmi_tm_colsum_bf16(dy.ptr, db.data_ptr(), ws.data_ptr(), n, dy.rows, self.C, 1, _lib.current_stream_ptr(self.device)), "evmi_tm_colsum_bf16")
 
     def _colsum_batch(self, jobs):
         """jobs: (TMBuf, bias-gradient sink) of one shape: db += column sums, 24 tensors per launch pair."""
@@ -174,20 +170,20 @@ class MRFStageTM:
             dbs = (C.c_void_p * n)(*[d.data_ptr() for _, d in part])
             ne = n * lib.evmi_tm_colsum_bf16_ws_elems(rows, self.C)
             ws = ops.WS.get("tm_colsum_b", ne, self.device)
-            _lib.check(lib.evmi_tm_colsum_batch_bf16(n, dys, dbs, ws.data_ptr(), ne, rows, self.C, 1, _s(self.device)), "evmi_tm_colsum_batch_bf16")
+            _lib.check(lib.evmi_tm_colsum_batch_bf16(n, dys, dbs, ws.data_ptr(), ne, rows, self.C, 1, _lib.current_stream_ptr(self.device)), "evmi_tm_colsum_batch_bf16")
 
     def _lrelu(self, x: TMBuf, y: TMBuf):
-        _lib.check(_lib.load().evmi_tm_lrelu_bf16(x.ptr, y.ptr, x.numel_body, self.slope, _s(self.device)), "evmi_tm_lrelu_bf16")
+        _lib.check(_lib.load().evmi_tm_lrelu_bf16(x.ptr, y.ptr, x.numel_body, self.slope, _lib.current_stream_ptr(self.device)), "evmi_tm_lrelu_bf16")
 
     def _to_tm(self, x_cbt: torch.Tensor, out: TMBuf, scale=1.0):
-        _lib.check(_lib.load().evmi_cbt_f32_to_tm_bf16(x_cbt.data_ptr(), out.ptr, self.C, out.B, out.T, out.Tp, out.PL, 1.0, float(scale), _s(self.device)),
+        _lib.check(_lib.load().evmi_cbt_f32_to_tm_bf16(x_cbt.data_ptr(), out.ptr, self.C, out.B, out.T, out.Tp, out.PL, 1.0, float(scale), _lib.current_stream_ptr(self.device)),
                    "evmi_cbt_f32_to_tm_bf16")
 
     def _to_cbt(self, parts, scale=1.0) -> torch.Tensor:
         a = parts[0]
         out = torch.empty(self.C, a.B, a.T, device=self.device, dtype=torch.float32)
         ptrs = [p.ptr for p in parts] + [0, 0]
-        _lib.check(_lib.load().evmi_tm_bf16_to_cbt_f32(ptrs[0], ptrs[1], ptrs[2], out.data_ptr(), self.C, a.B, a.T, a.Tp, a.PL, float(scale), _s(self.device)),
+        _lib.check(_lib.load().evmi_tm_bf16_to_cbt_f32(ptrs[0], ptrs[1], ptrs[2], out.data_ptr(), self.C, a.B, a.T, a.Tp, a.PL, float(scale), _lib.current_stream_ptr(self.device)),
                    "evmi_tm_bf16_to_cbt_f32")
         return out
 

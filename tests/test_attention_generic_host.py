@@ -68,15 +68,13 @@ def test_generic_entry_points_refuse_before_any_launch(name):
 def test_generic_entry_points_are_declared_with_their_counterparts_arguments():
     """include/evmi.h declares the six symbols; parameter by parameter they match _lib.py's ctypes table, which gives each the argument
     list of the specialised entry point it generalises."""
-    text = (ROOT / "include" / "evmi.h").read_text()
+    header = {n: (ret, params) for n, ret, params in _lib.declarations()}
     ctype = {"int": ctypes.c_int, "float": ctypes.c_float, "unsigned long long": ctypes.c_ulonglong}
     for name, other in COUNTERPART.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/evmi.h"
-        declared = []
-        for param in m.group(1).split(","):
-            param = " ".join(param.split())
-            declared.append(ctypes.c_void_p if "*" in param else ctype[param.rsplit(" ", 1)[0]])
+        assert name in header, f"{name} is not declared in include/evmi.h"
+        ret, params = header[name]
+        assert ret == "int"
+        declared = [ctypes.c_void_p if "*" in t else ctype[t] for t, _ in params]
         restype, argtypes = _signature(name)
         assert restype is ctypes.c_int and list(argtypes) == declared, (name, argtypes, declared)
         assert list(_signature(other)[1]) == list(argtypes), (name, other)

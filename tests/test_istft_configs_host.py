@@ -180,14 +180,15 @@ def test_f32_workspace_covers_the_logits_of_a_wide_head():
 
 
 def test_declarations_match_the_ctypes_table():
-    text = (ROOT / "include" / "evmi.h").read_text()
+    header = {n: (ret, params) for n, ret, params in _lib.declarations()}
     for name in ("evmi_istft_head_bf16", "evmi_istft_head_weight_elems", "evmi_istft_head_frame_tile"):
-        m = re.search(r"\b(int|long long)\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/evmi.h"
-        declared = [C.c_void_p if "*" in p else C.c_int for p in m.group(2).split(",")]
+        assert name in header, f"{name} is not declared in include/evmi.h"
+        ret, params = header[name]
+        assert all("*" in t or t == "int" for t, _ in params), (name, params)
+        declared = [C.c_void_p if "*" in t else C.c_int for t, _ in params]
         fn = getattr(_lib.load(), name)
         assert list(fn.argtypes) == declared, (name, fn.argtypes, declared)
-        assert fn.restype is (C.c_int if m.group(1) == "int" else C.c_longlong)
+        assert fn.restype is {"int": C.c_int, "long long": C.c_longlong}[ret]
 
 
 # ---- static rule on the compiled kernels ------------------------------------------------------------------------------------

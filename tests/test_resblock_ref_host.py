@@ -247,7 +247,9 @@ def test_refused_on_the_host_with_the_documented_code(name):
 def test_the_header_states_the_preconditions():
     from pathlib import Path
 
-    text = " ".join((Path(__file__).resolve().parents[1] / "include" / "evmi.h").read_text().split())
+    declared = {name for name, _, _ in _lib.declarations()}
+    assert {fn for fn, _, _ in REFUSALS.values()} <= declared
+    text = " ".join((Path(__file__).resolve().parents[1] / "include" / "evmi.h").read_text().split())  # the comments: the raw text
     for phrase in ("evmi_resblock_pair_bf16", "evmi_resblock_branch_bf16", "x and out overlapping", "EVMI_PAIR_C128=0", "EVMI_BRANCH=0",
                    "0 = the device's compute units"):
         assert phrase in text, phrase

@@ -34,6 +34,7 @@ from everyvoice_amd.train.autograd import Tape, Var  # noqa: E402
 from everyvoice_amd.train.layers import ParamGroup  # noqa: E402
 
 STREAM = 0x5EED0
+_BYREF = type(C.byref(C.c_int()))
 QUERY_SUFFIXES = ("_ws_elems", "_plan", "_supported", "_rounds", "_shares_packed", "_frag_elems")
 
 # scenario -> [(substring of the query's name, answer)], first match wins; names no pattern matches answer 64
@@ -72,12 +73,18 @@ class Recorder:
         return "PTR"
 
     def _canon(self, v, ctype):
-        if ctype is C.c_void_p:
-            return self._pointer(v)
+        # what the value is decides first: the header types every pointer parameter but those to the mirrored structs as void*
+        if isinstance(v, _BYREF):  # byref(x) stands for x
+            v = v._obj
+            ctype = type(v)
         if isinstance(v, C.Array):  # jobs (structs), pointer tables, small value arrays
             return [self._canon(e, v._type_) for e in v]
         if isinstance(v, C.Structure):
             return {f: self._canon(getattr(v, f), t) for f, t in v._fields_}
+        if ctype is C.c_void_p:
+            return self._pointer(v)
+        if isinstance(v, C._SimpleCData):
+            v = v.value
         if v is None:
             return "NULL"
         if ctype in (C.c_float, C.c_double):
