@@ -17,6 +17,7 @@
 // sequence are forced to zero at every stage (each convolution of the unfused chain zero-pads ITS input).
 //   XA [RB][C+8]  lrelu(y(p))      RS [RB][C+8]  y(p) (the residual; updated in place)      T1 [RB][C+8]  lrelu(conv1 + b1)
 //   RB = BN + 16 H rows (the reach of pair 2 of a (1, 3, 5) branch); WS / BIAS as in the pair kernel.
+// Every block but the update of y between two pairs is the pair kernel's own, from resblock_tiles.h.
 #pragma once
 
 #include "resblock_pair_kernel.h"
@@ -62,6 +63,7 @@ struct BranchCfg {
   static constexpr int RB = BN + 16 * H;
   static constexpr int NG = (KS + TAPS - 1) / TAPS;
   static constexpr int LAST_TAPS = KS - (NG - 1) * TAPS;
+  static constexpr int NSTEP = 2 * NP * NG;  // weight steps per tile: convolution s / NG (conv1, conv2 of pair 0, conv1 of pair 1, ...)
   static constexpr int W_TILE = TAPS * C * S;
   static constexpr int W_VECS = TAPS * C * (C / 8);
   static constexpr int W_PER_THREAD = (W_VECS + NTHREADS - 1) / NTHREADS;
@@ -86,116 +88,43 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
   bf16_t* WS = reinterpret_cast<bf16_t*>(smem) + P::OFF_WS;
   float* BIAS = reinterpret_cast<float*>(reinterpret_cast<bf16_t*>(smem) + P::OFF_BIAS);
 
-  constexpr int C = P::C, S = P::S, KS = P::KS, H = P::H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / P::WN, wn = wave % P::WN;
-  const int cb = wm * P::MT * 32;  // first output channel of this wave
+  constexpr int C = P::C, S = P::S, H = P::H;
+  const Lane ln = lane_coords<P>();
+  const int tid = ln.tid, lane = ln.lane;
   constexpr int np = P::NP;
   int mtot = 0;
 #pragma unroll
   for (int p = 0; p < np; ++p) mtot += a.dil[p] * H + H;
-  const int r_in = P::BN + 2 * a.dil[0] * H;  // rows of x a tile loads
-  const int x_nvec = r_in * (C / 8);
-  constexpr int nstep = 2 * np * P::NG;
+  // LDS row 0 is global row r0 - Mtot; a tile loads BN + 2 h1_0 rows of x
+  const XLoad xl = {a.x, a.lens, a.T, a.tiles_per_item, a.tt, mtot, (P::BN + 2 * a.dil[0] * H) * (C / 8)};
+  const TileWalk walk = tile_walk(a.n_tiles);
 
-  const int nwg = gridDim.x;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd_wg = (nwg + 7) >> 3;
-  const int tiles_per_xcd = (a.n_tiles + 7) >> 3;
-  const int tile_lo = xcd * tiles_per_xcd;
-  const int tile_hi = min(a.n_tiles, tile_lo + tiles_per_xcd);
+  u32x4 xreg[P::X_PER_THREAD];
+  u32x4 wreg[P::WRES ? P::NSTEP : 1][P::W_PER_THREAD];
 
-  bf16x8 xreg[P::X_PER_THREAD];
-  bf16x8 wreg[P::WRES ? nstep : 1][P::W_PER_THREAD];
-
-  auto x_issue = [&](int tile) {
-    const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
-    const int g0 = rt * a.tt - mtot;
-    const bf16_t* xb = a.x + (long long)item * a.T * C;
-    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;
-    if (RAGGED && rt * a.tt >= Tb) return;  // a tile at or beyond its item's length is skipped: nothing to load
-#pragma unroll
-    for (int i = 0; i < P::X_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      const int row = v / (C / 8), c8 = v % (C / 8);
-      const int g = g0 + row;
-      bf16x8 val;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) val[e] = (bf16_t)0.f;
-      if (v < x_nvec && g >= 0 && g < Tb) val = *reinterpret_cast<const bf16x8*>(xb + (long long)g * C + c8 * 8);
-      xreg[i] = val;
-    }
-  };
-  auto x_commit = [&]() {
-    const float sl = a.slope;
-#pragma unroll
-    for (int i = 0; i < P::X_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      if (v < x_nvec) {
-        const int row = v / (C / 8), c8 = v % (C / 8);
-        const bf16x8 raw = xreg[i];
-        *reinterpret_cast<bf16x8*>(XA + row * S + c8 * 8) = lrelu8_bf16(raw, sl);
-        *reinterpret_cast<bf16x8*>(RS + row * S + c8 * 8) = raw;
-      }
-    }
-  };
-  // step s in [0, nstep): convolution s / NG (conv1, conv2 of pair 0, conv1 of pair 1, ...), tap group s % NG
-  auto w_prefetch = [&](int s) {
-    const int ci = s / P::NG, grp = s % P::NG;
-    const bf16_t* src = a.w[ci] + (long long)grp * P::TAPS * C * C;
-    const int ntaps = (KS - grp * P::TAPS) < P::TAPS ? (KS - grp * P::TAPS) : P::TAPS;
-    const int nvec = ntaps * C * (C / 8);
-#pragma unroll
-    for (int i = 0; i < P::W_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      if (P::W_EXACT || v < nvec) wreg[P::WRES ? s : 0][i] = *reinterpret_cast<const bf16x8*>(src + (long long)v * 8);
-    }
-  };
-  auto w_commit = [&](int s) {
-    bf16_t* dst = WS + (s & (P::NWBUF - 1)) * P::W_TILE;
-    const int grp = s % P::NG;
-    const int ntaps = (KS - grp * P::TAPS) < P::TAPS ? (KS - grp * P::TAPS) : P::TAPS;
-    const int nvec = ntaps * C * (C / 8);
-#pragma unroll
-    for (int i = 0; i < P::W_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      if (P::W_EXACT || v < nvec) {
-        const int row = v / (C / 8), c8 = v % (C / 8);
-        *reinterpret_cast<bf16x8*>(dst + row * S + c8 * 8) = wreg[P::WRES ? s : 0][i];
-      }
-    }
-  };
-
-  int tile = tile_lo + slot;
-  if (tile >= tile_hi) return;
+  int tile = walk.first;
+  if (tile >= walk.end) return;
   // the three activation tiles start finite (what a tile never writes is read by garbage rows only, but must not be a NaN pattern
-  // that another row's MFMA could not survive -- it cannot: a B row feeds one output row -- nor trap the activation arithmetic)
-  {
-    bf16x8 z;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
-    for (int v = tid; v < 3 * P::RB * S / 8; v += P::NTHREADS) *reinterpret_cast<bf16x8*>(XA + v * 8) = z;
-  }
-  for (int i = tid; i < 4 * np * C; i += P::NTHREADS) BIAS[i] = a.b[(i % (2 * np * C)) / C][i % C];  // (two copies: see the pair kernel)
+  // that another row's MFMA could not survive -- it cannot: a B row feeds one output row -- nor trap the activation arithmetic).
+  // One flat fill of XA, RS and T1, pad columns included: whatever the layout inside a tile, every byte of the three is written
+  for (int v = tid; v < 3 * P::RB * S / 8; v += P::NTHREADS) *reinterpret_cast<bf16x8*>(XA + v * 8) = zero_bf16x8();
+  for (int i = tid; i < 4 * np * C; i += P::NTHREADS) BIAS[i] = a.b[(i % (2 * np * C)) / C][i % C];  // (two copies: acc_from_bias)
   lds_barrier();
-  x_issue(tile);
-  if (P::WRES) {
-#pragma unroll
-    for (int s = 0; s < nstep; ++s) w_prefetch(s);
-  } else {
-    w_prefetch(0);
-  }
+  x_issue<P, RAGGED>(xreg, xl, tile, tid);
+  w_preload<P>(wreg, a.w, tid);
 
-  for (; tile < tile_hi; tile += per_xcd_wg) {
+  for (; tile < walk.end; tile += walk.stride) {
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int r0 = rt * a.tt;       // first output row of this tile
     const int g0 = r0 - mtot;       // global row of LDS row 0
-    const int next = tile + per_xcd_wg;
+    const int next = tile + walk.stride < walk.end ? tile + walk.stride : -1;
     const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;  // valid rows of this item (wave-uniform)
     if (RAGGED && r0 >= Tb) {  // this slot of the walk lies at or beyond its item's length: no load, no store
-      if (next < tile_hi) x_issue(next);
+      if (next >= 0) x_issue<P, RAGGED>(xreg, xl, next, tid);
       continue;
     }
     const bool edge = g0 < 0 || g0 + P::RB > Tb;  // (wave-uniform) the tile holds rows outside the sequence
-    x_commit();
+    x_commit<P>(xreg, XA, RS, a.slope, xl.nvec, 0, P::RB, tid);  // RS: every row, y(0) = x
 
     f32x16 acc[P::MT][P::NT];
     int mp = 0;  // Mp
@@ -205,63 +134,14 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
       const int h1 = dil * H;
 #pragma unroll
       for (int conv = 0; conv < 2; ++conv) {
-        {  // accumulators start at the bias (accumulator layout: channels 8q + 4h .. + 3 per register quad): the epilogues only
-           // activate / add the residual -- they are VALU-bound (a k = 3 tile: 1600 vector ops per wave against 72 MFMAs)
-          const float* bias = BIAS + (2 * p + conv) * C;
-#pragma unroll
-          for (int i = 0; i < P::MT; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int j = 0; j < P::NT; ++j) {
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + (j & 1) * 2 * np * C + cb + i * 32 + 8 * q + 4 * (lane >> 5));
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][4 * q + r] = bv[r];
-              }
-        }
+        acc_from_bias<P>(acc, BIAS, 2 * p + conv, ln);
         // conv1: XA rows Mp + n + j d;  conv2: T1 rows Mp + h1 + n + j
-        const bf16_t* Bsrc = conv ? T1 + (mp + h1) * S : XA + mp * S;
-        const int b_tap_stride = (conv ? 1 : dil) * S;
 #pragma unroll
-        for (int grp = 0; grp < P::NG; ++grp) {
-          const int s = (2 * p + conv) * P::NG + grp;
-          if (P::NWBUF == 1 && s > 0) lds_barrier();  // everyone is done reading the single weight buffer (s = 0: the barrier that ends a tile)
-          w_commit(s);
-          lds_barrier();
-          if (!P::WRES) w_prefetch(s + 1 == nstep ? 0 : s + 1);  // wraps to the next tile's first group
-          if (s == 0 && next < tile_hi) x_issue(next);
-          const bf16_t* Arow = WS + (s & (P::NWBUF - 1)) * P::W_TILE + (cb + (lane & 31)) * S + (lane >> 5) * 8;
-          const bf16_t* Brow = Bsrc + (wn * P::NT * 32 + (lane & 31)) * S + grp * P::TAPS * b_tap_stride + (lane >> 5) * 8;
-          if (grp + 1 < P::NG || P::LAST_TAPS == P::TAPS)
-            mma_tap_group<P::MT, P::NT, C / 16, P::TAPS, C * S, 32 * S, 32 * S>(Arow, Brow, b_tap_stride, acc);
-          else
-            mma_tap_group<P::MT, P::NT, C / 16, P::LAST_TAPS, C * S, 32 * S, 32 * S>(Arow, Brow, b_tap_stride, acc);
-        }
-        if (conv == 0) {
-          // T1[Mp + h1 + n] = lrelu(conv1 + b1), zero outside the sequence (only a tile at an end of the sequence has such rows)
-          const float sl = a.slope;
-#pragma unroll
-          for (int mt = 0; mt < P::MT; ++mt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int c = cb + mt * 32 + 8 * q + 4 * (lane >> 5);
-#pragma unroll
-              for (int nt = 0; nt < P::NT; ++nt) {
-                const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
-                const int row = mp + h1 + n;
-                bf16x4 pk = lrelu4_bf16(f32x4{acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]}, sl);
-                if (edge) {
-                  const int g = g0 + row;
-                  if (g < 0 || g >= Tb) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)0.f;
-                  }
-                }
-                *reinterpret_cast<bf16x4*>(T1 + row * S + c) = pk;
-              }
-            }
-          }
-        }
+        for (int grp = 0; grp < P::NG; ++grp)
+          tap_group_step<P, RAGGED>(acc, wreg, xreg, WS, conv ? T1 : XA, conv ? mp + h1 : mp, conv ? 1 : dil, (2 * p + conv) * P::NG + grp, a.w, xl,
+                                    next, ln);
+        // T1[Mp + h1 + n] (only a tile at an end of the sequence has rows outside it)
+        if (conv == 0) t1_epilogue<P>(acc, T1, mp + h1, g0, edge, Tb, a.slope, ln);
       }
       const int mnext = mp + h1 + H;  // M(p+1): LDS row of conv2's output row 0
       if (p + 1 < np) {
@@ -272,12 +152,12 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
         for (int mt = 0; mt < P::MT; ++mt) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int c = cb + mt * 32 + 8 * q + 4 * (lane >> 5);
+            const int c = ln.cb + mt * 32 + 8 * q + 4 * (lane >> 5);
 #pragma unroll
             for (int nt = 0; nt < P::NT; ++nt) {
-              const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
+              const int n = ln.nb + nt * 32 + (lane & 31);
               const int row = mnext + n;
-              const bf16x4 rv = *reinterpret_cast<const bf16x4*>(RS + row * S + c);
+              const bf16x4 rv = *reinterpret_cast<const bf16x4*>(RS + lds_at_channel<S>(row, c));
               bf16x4 raw, act;
 #pragma unroll
               for (int i = 0; i < 4; ++i) raw[i] = (bf16_t)(acc[mt][nt][4 * q + i] + (float)rv[i]);
@@ -289,60 +169,13 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_branch_kernel(BranchArgs
                 }
               }
               act = lrelu4_bf16(f32x4{(float)raw[0], (float)raw[1], (float)raw[2], (float)raw[3]}, sl);
-              *reinterpret_cast<bf16x4*>(RS + row * S + c) = raw;
-              *reinterpret_cast<bf16x4*>(XA + row * S + c) = act;
+              *reinterpret_cast<bf16x4*>(RS + lds_at_channel<S>(row, c)) = raw;
+              *reinterpret_cast<bf16x4*>(XA + lds_at_channel<S>(row, c)) = act;
             }
           }
         }
       } else {
-        // ---- final epilogue: conv2 + b2 + residual (LDS) -> registers -> 16-byte stores (as the pair kernel's) ------------------
-        bf16_t* ob = a.out + (long long)item * a.T * C;
-        const float scale = a.out_scale, post = a.post_slope;
-        const int hh = lane >> 5;
-#pragma unroll
-        for (int nt = 0; nt < P::NT; ++nt) {
-          const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
-          const int r = r0 + n;
-          const bool ok = n < a.tt && r < Tb;
-          bf16_t* dst = ob + (long long)(ok ? r : 0) * C + 8 * hh;
-          u32x4 pv[P::MT][2];
-          if (a.accumulate) {
-#pragma unroll
-            for (int mt = 0; mt < P::MT; ++mt)
-#pragma unroll
-              for (int p2 = 0; p2 < 2; ++p2) pv[mt][p2] = *reinterpret_cast<const u32x4*>(dst + cb + mt * 32 + 16 * p2);
-          }
-#pragma unroll
-          for (int mt = 0; mt < P::MT; ++mt)
-#pragma unroll
-            for (int p2 = 0; p2 < 2; ++p2) {
-              float f[8];
-#pragma unroll
-              for (int qq = 0; qq < 2; ++qq) {
-                const int c = cb + mt * 32 + 8 * (2 * p2 + qq) + 4 * hh;
-                const bf16x4 rv = *reinterpret_cast<const bf16x4*>(RS + (mnext + n) * S + c);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) f[4 * qq + i] = (acc[mt][nt][4 * (2 * p2 + qq) + i] + (float)rv[i]) * scale;
-              }
-              if (a.accumulate) {
-                const u32x4 d = swap_quads_bf16(pv[mt][p2]);
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                  f[2 * w] += bf16_lo(d[w]);
-                  f[2 * w + 1] += bf16_hi(d[w]);
-                }
-              }
-              u32x4 o;
-#pragma unroll
-              for (int w = 0; w < 4; ++w) {
-                const float lo = post != 1.f ? fmaxf(f[2 * w], f[2 * w] * post) : f[2 * w];
-                const float hi = post != 1.f ? fmaxf(f[2 * w + 1], f[2 * w + 1] * post) : f[2 * w + 1];
-                o[w] = pack_bf16x2(lo, hi);
-              }
-              o = swap_quads_bf16(o);
-              if (ok) *reinterpret_cast<u32x4*>(dst + cb + mt * 32 + 16 * p2) = o;
-            }
-        }
+        final_epilogue<P>(acc, RS, mnext, a.out + (long long)item * a.T * C, r0, a.tt, Tb, a.out_scale, a.post_slope, a.accumulate, ln);
       }
       mp = mnext;
     }

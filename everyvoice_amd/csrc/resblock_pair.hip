@@ -1,28 +1,29 @@
-// Instantiations and launcher of the fused residual-pair kernel (resblock_pair_kernel.h).
+// Instantiations and launchers of the fused residual kernels (resblock_pair_kernel.h, resblock_pair_chunked_kernel.h,
+// resblock_branch_kernel.h; their shared device code: resblock_tiles.h).
 
 #include "resblock_branch_kernel.h"
 #include "resblock_pair_chunked_kernel.h"
 
 namespace evmi {
 
-//                  C  KS  BN  TAPS MAXDIL WAVES NWBUF OVL WRES WM   (sixteen waves at 32 channels: four per SIMD keep the VALU-bound activation
+//                  C  KS  BN  TAPS MAXDIL WAVES NWBUF WRES WM   (sixteen waves at 32 channels: four per SIMD keep the VALU-bound activation
 //                  passes and the LDS latency of the short MFMA steps covered, -7 ... -9 %; at 64 channels the 2 (channels) x 8 (rows) split
 //                  costs a fragment read per MFMA instead of 0.75 and measured equal or slower: eight waves there)
 // C = 32: all taps of one convolution fit LDS at once (single buffer): 2 weight steps per tile.  (Measured and removed in round 5:
 // a two-workgroups-per-CU form with T1 overlaying the operand tile, 1.22 vs 1.16 ms on c32 / k11; a conv1 / conv2 wave pipeline
 // with the weights in registers, 17.82 vs 17.63 ms per forward -- DESIGN.md §9.7, §9.11.)
 #define EVMI_PAIR_TABLE(X)               \
-  X(64, 3, 256, 2, 5, 8, 2, 0, WR, 1)    \
-  X(64, 7, 256, 2, 5, 8, 2, 0, WR, 1)    \
-  X(64, 11, 256, 2, 5, 8, 2, 0, WR, 1)   \
-  X(32, 3, 512, 3, 5, 8, 2, 0, 0, 1)     \
-  X(32, 7, 512, 7, 5, 8, 1, 0, 0, 1)     \
-  X(32, 11, 512, 11, 5, 16, 1, 0, WR, 1)
+  X(64, 3, 256, 2, 5, 8, 2, WR, 1)       \
+  X(64, 7, 256, 2, 5, 8, 2, WR, 1)       \
+  X(64, 11, 256, 2, 5, 8, 2, WR, 1)      \
+  X(32, 3, 512, 3, 5, 8, 2, 0, 1)        \
+  X(32, 7, 512, 7, 5, 8, 1, 0, 1)        \
+  X(32, 11, 512, 11, 5, 16, 1, WR, 1)
 
 static const PairLaunch* pair_table(int* n) {
 #define WR 1  // weights resident in registers (PairCfg::WRES)
-#define X(c, ks, bn, taps, md, waves, nwbuf, ovl, wres, wm) \
-  make_pair_launch<PairCfg<c, ks, bn, taps, md, waves, 0, nwbuf, ovl, wres, wm>>("resblock_pair_mfma<c" #c ",k" #ks ",bn" #bn ",t" #taps ">"),
+#define X(c, ks, bn, taps, md, waves, nwbuf, wres, wm) \
+  make_pair_launch<PairCfg<c, ks, bn, taps, md, waves, 0, nwbuf, wres, wm>>("resblock_pair_mfma<c" #c ",k" #ks ",bn" #bn ",t" #taps ">"),
   static const PairLaunch table[] = {
       EVMI_PAIR_TABLE(X)
       // C = 128: chunked variant (64-channel operand chunks, 2 x 4 waves of 64 x 64).  Measured on MI355X
@@ -54,15 +55,18 @@ void relayout_resblock_pair(const float* w, int c, int ks, int kc, uint16_t* dst
         dst[((((size_t)(ci / kc)) * ks + jt) * c + mo) * kc + ci % kc] = f32_to_bf16_bits(w[((size_t)mo * c + ci) * ks + jt]);
 }
 
+// Persistent grid of the fused kernels: wg_per_cu workgroups per CU (LDS-bound residency), a multiple of 8 so every XCD gets the same
+// number of workgroups (the kernels' tile walk relies on it), and no more than the tiles need
+static int persistent_grid(int n_cu, int wg_per_cu, int n_tiles) {
+  const int grid = ((n_cu > 0 ? n_cu : 256) * wg_per_cu + 7) / 8 * 8;
+  const int needed = (n_tiles + 7) / 8 * 8;
+  return grid > needed ? needed : grid;
+}
+
 int launch_resblock_pair(const PairLaunch* L, PairArgs a, int B, int n_cu, hipStream_t stream) {
   a.tiles_per_item = (a.T + L->tt - 1) / L->tt;
   a.n_tiles = a.tiles_per_item * B;
-  // persistent: one workgroup per CU (LDS-bound residency), a multiple of 8 so every XCD gets the
-  // same number of workgroups (the kernel's tile walk relies on it)
-  int grid = (n_cu > 0 ? n_cu : 256) * L->wg_per_cu;
-  grid = (grid + 7) / 8 * 8;
-  const int needed = (a.n_tiles + 7) / 8 * 8;
-  if (grid > needed) grid = needed;
+  const int grid = persistent_grid(n_cu, L->wg_per_cu, a.n_tiles);
   if (int rc = launch_with_lds(a.lens.frames ? L->kernel_ragged : L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
   EVMI_LAUNCH_CHECK(L->name);
   return EVMI_OK;
@@ -112,10 +116,7 @@ int launch_resblock_branch(const BranchLaunch* L, BranchArgs a, int B, int n_cu,
   if (a.tt <= 0) return fail(EVMI_ERR_UNSUPPORTED, "resblock_branch: dilations beyond the LDS tiles");
   a.tiles_per_item = (a.T + a.tt - 1) / a.tt;
   a.n_tiles = a.tiles_per_item * B;
-  int grid = (n_cu > 0 ? n_cu : 256);  // persistent: one workgroup per CU, a multiple of 8 (the kernel's tile walk relies on it)
-  grid = (grid + 7) / 8 * 8;
-  const int needed = (a.n_tiles + 7) / 8 * 8;
-  if (grid > needed) grid = needed;
+  const int grid = persistent_grid(n_cu, 1, a.n_tiles);
   if (int rc = launch_with_lds(a.lens.frames ? L->kernel_ragged : L->kernel, dim3(grid), dim3(L->threads), L->lds_bytes, stream, a)) return rc;
   EVMI_LAUNCH_CHECK(L->name);
   return EVMI_OK;

@@ -3,6 +3,8 @@
 // intermediate), the intermediate T1 holds all C channels, and the waves tile the output 2 (channels) x
 // 4 (rows) with 64 x 64 per wave.  Per tile: 2*NCH*KS weight steps, one activation load per chunk, one
 // epilogue — twice the K depth per tile of the unfused convolutions, and no T1 round trip through HBM.
+// The tile walk, the LDS addressing (three pitches: SX / ST / SW) and the T1 tail rows come from resblock_tiles.h; the loads through
+// buffer descriptors, the three-deep weight ring, the bias added in the epilogues and the staged stores are this kernel's own.
 #pragma once
 
 #include "resblock_pair_kernel.h"
@@ -45,18 +47,15 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
   bf16_t* OS = T1;  // epilogue staging [BN][ST] reuses the intermediate once conv2 has consumed it
 
   constexpr int C = P::C, KC = P::KC, KS = P::KS, H2 = (KS - 1) / 2;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / P::WN, wn = wave % P::WN;
+  const Lane ln = lane_coords<P>();
+  const int tid = ln.tid, lane = ln.lane;
   const int h1 = a.dil1 * (KS - 1) / 2;
   const int ra = P::BN + (KS - 1) * a.dil1;
   const int x_nvec = ra * (KC / 8);
 
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd_wg = (gridDim.x + 7) >> 3;
-  const int tiles_per_xcd = (a.n_tiles + 7) >> 3;
-  const int tile_lo = xcd * tiles_per_xcd;
-  const int tile_hi = min(a.n_tiles, tile_lo + tiles_per_xcd);
-  int tile = tile_lo + slot;
-  if (tile >= tile_hi) return;
+  const TileWalk walk = tile_walk(a.n_tiles);
+  int tile = walk.first;
+  if (tile >= walk.end) return;
 
   bf16x8 xreg[P::XV];
   // weight images are requested TWO steps ahead (a ring of three register sets): a step is 16 MFMAs per wave, far shorter than the
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
           const float f = (float)val[e];
           val[e] = (bf16_t)fmaxf(f, f * sl);
         }
-        *reinterpret_cast<bf16x8*>(XA + row * P::SX + c8 * 8) = val;
+        *reinterpret_cast<bf16x8*>(XA + lds_at<P::SX>(row, c8)) = val;
       }
     }
   };
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
 #pragma unroll
     for (int i = 0; i < P::W_PER_THREAD; ++i) {
       const int v = tid + i * P::NTHREADS;
-      *reinterpret_cast<bf16x8*>(dst + (v / (KC / 8)) * P::SW + (v % (KC / 8)) * 8) = wreg[slot][i];
+      *reinterpret_cast<bf16x8*>(dst + lds_at<P::SW>(v / (KC / 8), v % (KC / 8))) = wreg[slot][i];
     }
   };
   auto out_offset = [&](int r0, int Tb, int i) -> unsigned {
@@ -128,10 +127,10 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
   for (int s = 0; s < WRING - 1; ++s) w_prefetch(s, s);
   static_assert(P::NSTEP % WRING == 0, "the ring position of a step is the same in every tile");
 
-  for (; tile < tile_hi; tile += per_xcd_wg) {
+  for (; tile < walk.end; tile += walk.stride) {
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int r0 = rt * P::TT;
-    const int next = tile + per_xcd_wg < tile_hi ? tile + per_xcd_wg : tile;  // last tile: a harmless repeat
+    const int next = tile + walk.stride < walk.end ? tile + walk.stride : tile;  // last tile: a harmless repeat
     const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;  // valid rows of this item (wave-uniform)
     if (RAGGED && r0 >= Tb) {  // this slot of the walk lies at or beyond its item's length: no load, no store (the weight ring keeps its place)
       if (next != tile) x_issue(next, 0);
@@ -165,9 +164,9 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
           if (chunk + 1 < P::NCH) x_issue(tile, chunk + 1);
           else x_issue(next, 0);
         }
-        const bf16_t* Arow = WS + (s & 1) * P::W_TILE + (wm * P::MT * 32 + (lane & 31)) * P::SW + (lane >> 5) * 8;
-        const bf16_t* Brow = XA + (wn * P::NT * 32 + (lane & 31) + tap * a.dil1) * P::SX + (lane >> 5) * 8;
-        mma_tap_group<P::MT, P::NT, KC / 16, 1, 0, 32 * P::SW, 32 * P::SX>(Arow, Brow, 0, acc);
+        const bf16_t* Arow = WS + (s & 1) * P::W_TILE + frag_base<P::SW>(ln.cb, lane);
+        const bf16_t* Brow = XA + frag_base<P::SX>(ln.nb + tap * a.dil1, lane);
+        mma_tap_group<P::MT, P::NT, KC / 16, 1, 0, lds_at<P::SW>(32, 0), lds_at<P::SX>(32, 0)>(Arow, Brow, 0, acc);
       }
     }
     {  // T1[n][c] = lrelu(conv1 + b1) for global row r0 - H2 + n, zero outside the sequence
@@ -176,11 +175,11 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
       for (int mt = 0; mt < P::MT; ++mt)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int c = wm * P::MT * 32 + mt * 32 + 8 * q + 4 * (lane >> 5);
+          const int c = ln.cb + mt * 32 + 8 * q + 4 * (lane >> 5);
           const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b1 + c);
 #pragma unroll
           for (int nt = 0; nt < P::NT; ++nt) {
-            const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
+            const int n = ln.nb + nt * 32 + (lane & 31);
             const int g = r0 - H2 + n;
             const float mask = (g >= 0 && g < Tb) ? 1.f : 0.f;
             bf16x4 pk;
@@ -189,15 +188,10 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
               const float f = acc[mt][nt][4 * q + i] + bv[i];
               pk[i] = (bf16_t)(fmaxf(f, f * sl) * mask);
             }
-            *reinterpret_cast<bf16x4*>(T1 + n * P::ST + c) = pk;
+            *reinterpret_cast<bf16x4*>(T1 + lds_at_channel<P::ST>(n, c)) = pk;
           }
         }
-      for (int v = tid; v < (KS - 1) * (C / 8); v += P::NTHREADS) {  // rows that only feed discarded outputs
-        bf16x8 z;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
-        *reinterpret_cast<bf16x8*>(T1 + (P::BN + v / (C / 8)) * P::ST + (v % (C / 8)) * 8) = z;
-      }
+      zero_t1_tail<P, P::ST>(T1, tid);
     }
     // ---------------- conv2 (dense) over the intermediate in LDS ----------------
     zero_acc();
@@ -209,9 +203,9 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
         w_commit(s, tap % WRING);
         lds_barrier();
         w_prefetch((s + WRING - 1) % P::NSTEP, (tap + WRING - 1) % WRING);  // (wraps to the next tile's first images)
-        const bf16_t* Arow = WS + (s & 1) * P::W_TILE + (wm * P::MT * 32 + (lane & 31)) * P::SW + (lane >> 5) * 8;
-        const bf16_t* Brow = T1 + (wn * P::NT * 32 + (lane & 31) + tap) * P::ST + chunk * KC + (lane >> 5) * 8;
-        mma_tap_group<P::MT, P::NT, KC / 16, 1, 0, 32 * P::SW, 32 * P::ST>(Arow, Brow, 0, acc);
+        const bf16_t* Arow = WS + (s & 1) * P::W_TILE + frag_base<P::SW>(ln.cb, lane);
+        const bf16_t* Brow = T1 + frag_base<P::ST>(ln.nb + tap, lane, chunk * (KC / 8));
+        mma_tap_group<P::MT, P::NT, KC / 16, 1, 0, lds_at<P::SW>(32, 0), lds_at<P::ST>(32, 0)>(Arow, Brow, 0, acc);
       }
     }
     // ---------------- epilogue ----------------
@@ -226,15 +220,15 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
     for (int mt = 0; mt < P::MT; ++mt)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int c = wm * P::MT * 32 + mt * 32 + 8 * q + 4 * (lane >> 5);
+        const int c = ln.cb + mt * 32 + 8 * q + 4 * (lane >> 5);
         const f32x4 bv = *reinterpret_cast<const f32x4*>(a.b2 + c);
 #pragma unroll
         for (int nt = 0; nt < P::NT; ++nt) {
-          const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
+          const int n = ln.nb + nt * 32 + (lane & 31);
           bf16x4 pk;
 #pragma unroll
           for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)(acc[mt][nt][4 * q + i] + bv[i]);
-          *reinterpret_cast<bf16x4*>(OS + n * P::ST + c) = pk;
+          *reinterpret_cast<bf16x4*>(OS + lds_at_channel<P::ST>(n, c)) = pk;
         }
       }
     lds_barrier();
@@ -244,7 +238,7 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_chunked_kernel(Pair
       for (int i = 0; i < P::RV; ++i) {
         const int v = tid + i * P::NTHREADS;
         const unsigned off = out_offset(r0, Tb, i);
-        const bf16x8 o = *reinterpret_cast<const bf16x8*>(OS + (v / (C / 8)) * P::ST + (v % (C / 8)) * 8);
+        const bf16x8 o = *reinterpret_cast<const bf16x8*>(OS + lds_at<P::ST>(v / (C / 8), v % (C / 8)));
         float f[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = ((float)o[e] + (float)rreg[i][e]) * scale;

@@ -14,10 +14,10 @@
 //   WS 2 x [TAPS][C][C+8]      weight tap groups, streamed global -> regs -> LDS one group ahead
 // The workgroup is persistent: it walks tiles tile0, tile0 + grid, ... and keeps the NEXT tile's
 // activation rows in flight in registers while the current tile computes, so the only exposed
-// HBM latency is the first tile's.
+// HBM latency is the first tile's.  The blocks this kernel shares with the branch and chunked kernels are in resblock_tiles.h.
 #pragma once
 
-#include "common.h"
+#include "resblock_tiles.h"
 
 namespace evmi {
 
@@ -51,14 +51,13 @@ struct PairLaunch {
   const char* name;
 };
 
-// OVL_: must be 0 (round 2's form with T1 overlaying the conv1 operand tile, two workgroups per CU, was measured slower and removed in round 5)
 // WRES_: the weights of both convolutions stay in registers for the life of the persistent workgroup (NSTEP x W_PER_THREAD vectors,
 // loaded once) and are committed to the LDS from there: a two-tap step at 64 channels is 16 MFMAs per wave, shorter than the L2 round
 // trip of the next step's weights that the one-step-ahead prefetch has to cover.
 // WM_: waves along the output channels (the others along the rows): 64 channels on sixteen waves = 2 x 8 of 32 x 32 tiles
-template <int C_, int KS_, int BN_, int TAPS_, int MAXDIL_, int WAVES_, int DBG_ = 0, int NWBUF_ = 2, int OVL_ = 0, int WRES_ = 0, int WM_ = 1>
+template <int C_, int KS_, int BN_, int TAPS_, int MAXDIL_, int WAVES_, int DBG_ = 0, int NWBUF_ = 2, int WRES_ = 0, int WM_ = 1>
 struct PairCfg {
-  static constexpr int C = C_, KS = KS_, BN = BN_, TAPS = TAPS_, MAXDIL = MAXDIL_, WAVES = WAVES_, DBG = DBG_, OVL = OVL_, WRES = WRES_;
+  static constexpr int C = C_, KS = KS_, BN = BN_, TAPS = TAPS_, MAXDIL = MAXDIL_, WAVES = WAVES_, DBG = DBG_, WRES = WRES_;
   static constexpr int WM = WM_, WN = WAVES / WM;
   // weight tap-group buffers in LDS: 2 = commit the next group while the current one is read; 1 = one
   // buffer (lets a whole convolution's taps sit in LDS at once) at the price of a barrier before each commit
@@ -86,7 +85,6 @@ struct PairCfg {
   static constexpr size_t LDS = (OFF_BIAS + 8 * size_t(C)) * 2;
   static constexpr int WG_PER_CU = (2 * LDS <= 160 * 1024 && WAVES <= 4) ? 2 : 1;
   static_assert(BN % (WN * 32) == 0 && C % (WM * 32) == 0 && WAVES % WM == 0, "tiling");
-  static_assert(OVL == 0, "the overlay form was removed");
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
@@ -98,243 +96,64 @@ __global__ __launch_bounds__(P::NTHREADS) void resblock_pair_kernel(PairArgs a) 
   bf16_t* RS = reinterpret_cast<bf16_t*>(smem) + P::OFF_RS;
   bf16_t* T1 = reinterpret_cast<bf16_t*>(smem) + P::OFF_T1;
   bf16_t* WS = reinterpret_cast<bf16_t*>(smem) + P::OFF_WS;
+  float* BIAS = reinterpret_cast<float*>(reinterpret_cast<bf16_t*>(smem) + P::OFF_BIAS);
 
-  constexpr int C = P::C, S = P::S, KS = P::KS, H2 = (KS - 1) / 2;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / P::WN, wn = wave % P::WN;
-  const int cb = wm * P::MT * 32;  // first output channel of this wave
+  constexpr int C = P::C, KS = P::KS, H2 = (KS - 1) / 2;
+  const Lane ln = lane_coords<P>();
+  const int tid = ln.tid;
   const int h1 = a.dil1 * (KS - 1) / 2;
-  const int ra = P::BN + (KS - 1) * a.dil1;  // rows of XA actually needed
-  const int x_nvec = ra * (C / 8);
+  // XA row 0 is global row r0 - H2 - h1; BN + (KS-1) * dil1 rows of XA are actually needed
+  const XLoad xl = {a.x, a.lens, a.T, a.tiles_per_item, P::TT, H2 + h1, (P::BN + (KS - 1) * a.dil1) * (C / 8)};
+  const bf16_t* const w[2] = {a.w1, a.w2};
+  const TileWalk walk = tile_walk(a.n_tiles);
 
-  // XCD-aware tile walk: workgroup b runs on XCD b % 8; give each XCD one contiguous range of
-  // tiles so neighbouring tiles (which share halo rows) meet in the same L2.
-  const int nwg = gridDim.x;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd_wg = (nwg + 7) >> 3;
-  const int tiles_per_xcd = (a.n_tiles + 7) >> 3;
-  const int tile_lo = xcd * tiles_per_xcd;
-  const int tile_hi = min(a.n_tiles, tile_lo + tiles_per_xcd);
-
-  bf16x8 xreg[P::X_PER_THREAD];
-  bf16x8 wreg[P::WRES ? P::NSTEP : 1][P::W_PER_THREAD];
-
-  auto x_issue = [&](int tile) {
-    const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
-    const int g0 = rt * P::TT - H2 - h1;  // global row of XA row 0
-    const bf16_t* xb = a.x + (long long)item * a.T * C;
-    const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;
-    if (RAGGED && rt * P::TT >= Tb) return;  // a tile at or beyond its item's length is skipped: nothing to load
-#pragma unroll
-    for (int i = 0; i < P::X_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      const int row = v / (C / 8), c8 = v % (C / 8);
-      const int g = g0 + row;
-      bf16x8 val;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) val[e] = (bf16_t)0.f;
-      if (v < x_nvec && g >= 0 && g < Tb) val = *reinterpret_cast<const bf16x8*>(xb + (long long)g * C + c8 * 8);
-      xreg[i] = val;
-    }
-  };
-  auto x_commit = [&]() {
-    const float sl = a.slope;
-#pragma unroll
-    for (int i = 0; i < P::X_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      if (v < x_nvec) {
-        const int row = v / (C / 8), c8 = v % (C / 8);
-        const bf16x8 raw = xreg[i];
-        const bf16x8 act = lrelu8_bf16(raw, sl);
-        *reinterpret_cast<bf16x8*>(XA + row * S + c8 * 8) = act;
-        const int n = row - H2 - h1;
-        if (n >= 0 && n < P::BN) *reinterpret_cast<bf16x8*>(RS + n * S + c8 * 8) = raw;
-      }
-    }
-  };
-  // step s in [0, NSTEP): conv = s / NG, tap group = s % NG
-  auto w_prefetch = [&](int s) {
-    const int conv = s / P::NG, grp = s % P::NG;
-    const bf16_t* src = (conv ? a.w2 : a.w1) + (long long)grp * P::TAPS * C * C;
-    const int ntaps = (KS - grp * P::TAPS) < P::TAPS ? (KS - grp * P::TAPS) : P::TAPS;
-    const int nvec = ntaps * C * (C / 8);
-#pragma unroll
-    for (int i = 0; i < P::W_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      if (P::W_EXACT || v < nvec) wreg[P::WRES ? s : 0][i] = *reinterpret_cast<const bf16x8*>(src + (long long)v * 8);
-    }
-  };
-  auto w_commit = [&](int s) {
-    bf16_t* dst = WS + (s & (P::NWBUF - 1)) * P::W_TILE;
-    const int grp = s % P::NG;
-    const int ntaps = (KS - grp * P::TAPS) < P::TAPS ? (KS - grp * P::TAPS) : P::TAPS;
-    const int nvec = ntaps * C * (C / 8);
-#pragma unroll
-    for (int i = 0; i < P::W_PER_THREAD; ++i) {
-      const int v = tid + i * P::NTHREADS;
-      if (P::W_EXACT || v < nvec) {
-        const int row = v / (C / 8), c8 = v % (C / 8);
-        *reinterpret_cast<bf16x8*>(dst + row * S + c8 * 8) = wreg[P::WRES ? s : 0][i];
-      }
-    }
-  };
+  u32x4 xreg[P::X_PER_THREAD];
+  u32x4 wreg[P::WRES ? P::NSTEP : 1][P::W_PER_THREAD];
 
   int n_stamp = 0;
   auto stamp = [&]() {
     if (P::DBG && a.timeline && blockIdx.x == 0 && tid == 0 && n_stamp < 256)
       a.timeline[n_stamp++] = (long long)__builtin_readcyclecounter();
   };
-  int tile = tile_lo + slot;
-  if (tile >= tile_hi) return;
-  // both bias vectors sit in LDS for the life of the (persistent) workgroup: accumulators start at the bias, read in the
-  // accumulator layout (channels 8q + 4h .. + 3 per register quad) under the first weight commit of each convolution
-  float* BIAS = reinterpret_cast<float*>(reinterpret_cast<bf16_t*>(smem) + P::OFF_BIAS);
-  // (two copies: the accumulators of the second row tile are initialised by loads of their own -- from one copy the compiler shares the
-  //  loads and pays a v_mov per accumulator register, on the VALU these kernels are bound by)
+  int tile = walk.first;
+  if (tile >= walk.end) return;
+  // both bias vectors sit in LDS, twice, for the life of the (persistent) workgroup (acc_from_bias)
   for (int i = tid; i < 4 * C; i += P::NTHREADS) BIAS[i] = (i % (2 * C)) < C ? a.b1[i % (2 * C)] : a.b2[i % (2 * C) - C];
   lds_barrier();  // (the first tile's accumulators are initialised from it before the first step's barrier)
-  x_issue(tile);
-  if (P::WRES) {
-#pragma unroll
-    for (int s = 0; s < P::NSTEP; ++s) w_prefetch(s);
-  } else {
-    w_prefetch(0);
-  }
+  x_issue<P, RAGGED>(xreg, xl, tile, tid);
+  w_preload<P>(wreg, w, tid);
 
-  for (; tile < tile_hi; tile += per_xcd_wg) {
+  for (; tile < walk.end; tile += walk.stride) {
     const int item = tile / a.tiles_per_item, rt = tile % a.tiles_per_item;
     const int r0 = rt * P::TT;  // first output row of this tile
-    const int next = tile + per_xcd_wg;
+    const int next = tile + walk.stride < walk.end ? tile + walk.stride : -1;
     const int Tb = RAGGED ? item_rows(a.lens, item, a.T) : a.T;  // valid rows of this item (wave-uniform)
     if (RAGGED && r0 >= Tb) {  // this slot of the walk lies at or beyond its item's length: no load, no store
-      if (next < tile_hi) x_issue(next);
+      if (next >= 0) x_issue<P, RAGGED>(xreg, xl, next, tid);
       continue;
     }
     stamp();  // tile start
-    x_commit();
+    x_commit<P>(xreg, XA, RS, a.slope, xl.nvec, H2 + h1, P::BN, tid);  // RS: raw x of the output rows
     stamp();  // x committed
 
     f32x16 acc[P::MT][P::NT];
 #pragma unroll
     for (int conv = 0; conv < 2; ++conv) {
-      {  // accumulators start at the bias (accumulator layout: channels 8q + 4h .. + 3 per register quad): the epilogues, which are
-         // VALU-bound at these channel counts, only activate / add the residual
-        const float* bias = BIAS + conv * C;
-#pragma unroll
-        for (int i = 0; i < P::MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int j = 0; j < P::NT; ++j) {
-              const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + (j & 1) * 2 * C + cb + i * 32 + 8 * q + 4 * (lane >> 5));
-#pragma unroll
-              for (int r = 0; r < 4; ++r) acc[i][j][4 * q + r] = bv[r];
-            }
-      }
-      const bf16_t* Bsrc = conv ? T1 : XA;
-      const int b_tap_stride = (conv ? 1 : a.dil1) * S;
+      acc_from_bias<P>(acc, BIAS, conv, ln);
       // tap groups are fully unrolled so that the (possibly shorter) last group is static too
 #pragma unroll
       for (int grp = 0; grp < P::NG; ++grp) {
-        const int s = conv * P::NG + grp;
-        if (P::NWBUF == 1 && s > 0) lds_barrier();  // everyone is done reading the single weight buffer
-        w_commit(s);
-        lds_barrier();
-        if (!P::WRES) w_prefetch(s + 1 == P::NSTEP ? 0 : s + 1);  // wraps to the next tile's first group
-        if (s == 0 && next < tile_hi) x_issue(next);  // after the weight loads: they stay in flight
-        const bf16_t* Arow = WS + (s & (P::NWBUF - 1)) * P::W_TILE + (cb + (lane & 31)) * S + (lane >> 5) * 8;
-        const bf16_t* Brow = Bsrc + (wn * P::NT * 32 + (lane & 31)) * S + grp * P::TAPS * b_tap_stride + (lane >> 5) * 8;
-        if (grp + 1 < P::NG || P::LAST_TAPS == P::TAPS)
-          mma_tap_group<P::MT, P::NT, C / 16, P::TAPS, C * S, 32 * S, 32 * S>(Arow, Brow, b_tap_stride, acc);
-        else
-          mma_tap_group<P::MT, P::NT, C / 16, P::LAST_TAPS, C * S, 32 * S, 32 * S>(Arow, Brow, b_tap_stride, acc);
+        tap_group_step<P, RAGGED>(acc, wreg, xreg, WS, conv ? T1 : XA, 0, conv ? 1 : a.dil1, conv * P::NG + grp, w, xl, next, ln);
         stamp();  // step done
       }
-      if (conv == 0) {
-        // T1[n] = lrelu(conv1 + b1) for global row r0 - H2 + n, zero outside the sequence
-        const float sl = a.slope;
+      if (conv == 0) {  // T1[n] is global row r0 - H2 + n
         const bool edge = r0 - H2 < 0 || r0 - H2 + P::BN > Tb;  // (wave-uniform) rows outside the sequence in this tile
-#pragma unroll
-        for (int mt = 0; mt < P::MT; ++mt) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int c = cb + mt * 32 + 8 * q + 4 * (lane >> 5);
-#pragma unroll
-            for (int nt = 0; nt < P::NT; ++nt) {
-              const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
-              bf16x4 pk = lrelu4_bf16(f32x4{acc[mt][nt][4 * q], acc[mt][nt][4 * q + 1], acc[mt][nt][4 * q + 2], acc[mt][nt][4 * q + 3]}, sl);
-              if (edge) {
-                const int g = r0 - H2 + n;
-                if (g < 0 || g >= Tb) {
-#pragma unroll
-                  for (int i = 0; i < 4; ++i) pk[i] = (bf16_t)0.f;
-                }
-              }
-              *reinterpret_cast<bf16x4*>(T1 + n * S + c) = pk;
-            }
-          }
-        }
-        // rows BN .. BN+KS-2 of T1 only feed discarded outputs; keep them finite
-        for (int v = tid; v < (KS - 1) * (C / 8); v += P::NTHREADS) {
-          bf16x8 z;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
-          *reinterpret_cast<bf16x8*>(T1 + (P::BN + v / (C / 8)) * S + (v % (C / 8)) * 8) = z;
-        }
+        t1_epilogue<P>(acc, T1, 0, r0 - H2, edge, Tb, a.slope, ln);
+        zero_t1_tail<P, P::S>(T1, tid);
       }
     }
-
     stamp();  // conv loops done (includes the T1 epilogue of conv1)
-    // ---- epilogue: conv2 + b2 + residual (LDS, accumulator layout) -> registers -> 16-byte stores ---------------
-    // No staging pass and no barrier: every wave retires its rows on its own.  Lane (n, h) holds channels 8q + 4h .. + 3 of row
-    // n per register quad q; swap_quads_bf16 turns the packed quads (2p, 2p + 1) into 16 contiguous bytes per lane.
-    {
-      bf16_t* ob = a.out + (long long)item * a.T * C;
-      const float scale = a.out_scale, post = a.post_slope;
-      const int hh = lane >> 5;
-#pragma unroll
-      for (int nt = 0; nt < P::NT; ++nt) {
-        const int n = wn * P::NT * 32 + nt * 32 + (lane & 31);
-        const int r = r0 + n;
-        const bool ok = n < P::TT && r < Tb;
-        bf16_t* dst = ob + (long long)(ok ? r : 0) * C + 8 * hh;
-        u32x4 pv[P::MT][2];
-        if (a.accumulate) {  // wave-uniform; all of the lane's vectors are requested before the first is consumed
-#pragma unroll
-          for (int mt = 0; mt < P::MT; ++mt)
-#pragma unroll
-            for (int p2 = 0; p2 < 2; ++p2) pv[mt][p2] = *reinterpret_cast<const u32x4*>(dst + cb + mt * 32 + 16 * p2);
-        }
-#pragma unroll
-        for (int mt = 0; mt < P::MT; ++mt)
-#pragma unroll
-          for (int p2 = 0; p2 < 2; ++p2) {
-            float f[8];
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-              const int c = cb + mt * 32 + 8 * (2 * p2 + qq) + 4 * hh;
-              const bf16x4 rv = *reinterpret_cast<const bf16x4*>(RS + n * S + c);
-#pragma unroll
-              for (int i = 0; i < 4; ++i) f[4 * qq + i] = (acc[mt][nt][4 * (2 * p2 + qq) + i] + (float)rv[i]) * scale;
-            }
-            if (a.accumulate) {
-              const u32x4 d = swap_quads_bf16(pv[mt][p2]);
-#pragma unroll
-              for (int w = 0; w < 4; ++w) {
-                f[2 * w] += bf16_lo(d[w]);
-                f[2 * w + 1] += bf16_hi(d[w]);
-              }
-            }
-            u32x4 o;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-              const float lo = post != 1.f ? fmaxf(f[2 * w], f[2 * w] * post) : f[2 * w];
-              const float hi = post != 1.f ? fmaxf(f[2 * w + 1], f[2 * w + 1] * post) : f[2 * w + 1];
-              o[w] = pack_bf16x2(lo, hi);
-            }
-            o = swap_quads_bf16(o);
-            if (ok) *reinterpret_cast<u32x4*>(dst + cb + mt * 32 + 16 * p2) = o;
-          }
-      }
-    }
+    final_epilogue<P>(acc, RS, 0, a.out + (long long)item * a.T * C, r0, P::TT, Tb, a.out_scale, a.post_slope, a.accumulate, ln);
     stamp();  // stores issued
     lds_barrier();  // staging / residual tiles are free again for the next tile's commit
   }
