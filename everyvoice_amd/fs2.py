@@ -268,6 +268,22 @@ def gst_state_dict_shapes(c: "FastSpeech2ModelConfig") -> dict:
     return shapes
 
 
+ALIGNER_CHANNELS = 80  # the attention dimension of the aligner (``train.fs2._AlignerT.n_att``)
+
+
+def aligner_state_dict_shapes(c: "FastSpeech2ModelConfig") -> dict:
+    """Names and shapes of the aligner of ``learn_alignment: true`` as the trainer declares them (``train.fs2._AlignerT``; FastPitch
+    ``ConvAttention``): keys = Conv(k 3) - ReLU - Conv(1) over the symbol embeddings, queries = Conv(k 3) - ReLU - Conv(1) - ReLU -
+    Conv(1) over the mel.  A checkpoint of a model trained with a learnt alignment holds them; ``FastSpeech2.load_state_dict`` takes
+    them when all are there, and ``FastSpeech2.align`` then finds an utterance's durations from its own mel."""
+    d, m, n = c.encoder.input_dim, c.n_mels, ALIGNER_CHANNELS
+    shapes = {}
+    for name, (cout, cin, k) in (("key_proj.0", (2 * d, d, 3)), ("key_proj.2", (n, 2 * d, 1)),
+                                 ("query_proj.0", (2 * m, m, 3)), ("query_proj.2", (m, 2 * m, 1)), ("query_proj.4", (n, m, 1))):
+        shapes[f"attention.{name}.conv.weight"], shapes[f"attention.{name}.conv.bias"] = (cout, cin, k), (cout,)
+    return shapes
+
+
 class StyleTokens:
     """Global Style Token module, inference: a reference mel [B, T, n_mels] -> a style embedding [B, E] that is added to the encoder
     output at every non-padded text position (where the speaker / language embeddings go).  Eval-mode BatchNorm is folded into the
@@ -472,8 +488,15 @@ class FastSpeech2:
                 p = f"postnet.convolutions.{i}"
                 w, b = _fold_bn(sd[p + ".0.weight"].float(), sd[p + ".0.bias"].float(), sd, p + ".1")
                 self.postnet.append((put(w), put(b)))
+        names = aligner_state_dict_shapes(c)
+        self.aligner = {n: put(sd[n]) for n in names} if c.learn_alignment and all(n in sd for n in names) else None
         self._ready = True
         return self
+
+    @property
+    def has_aligner(self) -> bool:
+        """The loaded state dict held every tensor of ``aligner_state_dict_shapes`` (and ``learn_alignment`` is on): ``align`` works."""
+        return getattr(self, "aligner", None) is not None
 
     @staticmethod
     def state_dict_shapes(c: FastSpeech2ModelConfig) -> dict:
@@ -526,11 +549,17 @@ class FastSpeech2:
                                p + ".1.running_mean": (dims[i + 1],), p + ".1.running_var": (dims[i + 1],)})
         return shapes
 
-    def init_random(self, seed: int = 1234):
-        """Random parameters of the right shapes (benchmarks; there is no network for checkpoints)."""
+    def init_random(self, seed: int = 1234, aligner: bool = False):
+        """Random parameters of the right shapes (benchmarks; there is no network for checkpoints).  ``aligner``: also the tensors of
+        ``aligner_state_dict_shapes``, drawn after all the others (the model's own parameters do not depend on the flag)."""
+        if aligner and not self.config.learn_alignment:
+            raise ValueError("init_random(aligner=True): model.learn_alignment is off, this model has no aligner")
         g = torch.Generator().manual_seed(seed)
         sd = {}
-        for name, shape in self.state_dict_shapes(self.config).items():
+        shapes = self.state_dict_shapes(self.config)
+        if aligner:
+            shapes.update(aligner_state_dict_shapes(self.config))
+        for name, shape in shapes.items():
             if name.endswith("inv_freq"):
                 d = self.config.encoder.input_dim
                 sd[name] = 1.0 / (10000 ** (torch.arange(0.0, d, 2.0) / d))
@@ -592,6 +621,78 @@ class FastSpeech2:
         with ops.mode(operands=self.precision):
             return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel, style_lens)
 
+    def _text_embedding(self, ids, lens32, positional: bool):
+        """ids [B, L] (or [B, L, 43] phonological feature vectors) -> [D, B, L], zero at the padded columns; ``positional``: plus the
+        sinusoid (what the encoder reads; the aligner's keys are the embeddings alone)."""
+        lib, dev, c = _lib.load(), self.device, self.config
+        B, L = ids.shape[:2]
+        D = c.encoder.input_dim
+        if c.target_text_representation_level == "phonological_features":
+            # Linear(43 -> D) as a pointwise convolution over [43, B, L]; the positional term also zeroes the padded columns
+            if ids.dim() != 3 or ids.shape[2] != N_PHONOLOGICAL_FEATURES:
+                raise ValueError(f"phonological features: expected [B, L, {N_PHONOLOGICAL_FEATURES}], got {tuple(ids.shape)}")
+            feats = ids.to(dev, torch.float32).permute(2, 0, 1).contiguous()
+            x = _conv(feats, self.table.view(D, N_PHONOLOGICAL_FEATURES, 1), None)
+            if not positional:
+                return _mask_cols_(x, lens32)
+            _chk(lib.evmi_fs2_add_posemb_f32(x.data_ptr(), lens32.data_ptr(), self.inv_freq.data_ptr(), B, L, D, _s(x)), "evmi_fs2_add_posemb_f32")
+            return x
+        ids32 = ids.to(dev, torch.int32).contiguous()
+        x = torch.empty(D, B, L, device=dev, dtype=torch.float32)
+        _chk(lib.evmi_fs2_embed_f32(ids32.data_ptr(), lens32.data_ptr(), self.table.data_ptr(), self.inv_freq.data_ptr() if positional else 0,
+                                    x.data_ptr(), B, L, D, _s(x)), "evmi_fs2_embed_f32")
+        return x
+
+    @torch.no_grad()
+    def align(self, ids: torch.Tensor, lens: torch.Tensor, mel: torch.Tensor, mel_lens: torch.Tensor, speakers: torch.Tensor | None = None,
+              languages: torch.Tensor | None = None) -> torch.Tensor:
+        """The durations [B, L] int64 (frames per symbol, zero at padded symbols; row b sums to mel_lens[b]) that the model's learnt
+        aligner gives utterance b: ids [B, L], lens [B], its own mel [B, T, n_mels] and mel_lens [B].  What the trainer's aligner
+        computes in a step, without the gradients' tensors: keys = the symbol embeddings (no positional term)
+        through Conv(k 3) - ReLU - Conv(1), queries = the mel, zeroed at and beyond mel_lens, through Conv(k 3) - ReLU - Conv(1) - ReLU -
+        Conv(1), both in fp32 in either precision mode; the beta-binomial prior of each item's (frames, symbols); the monotonic search
+        over -temperature * ||q - k||^2 + log prior (``evmi_align_durations_f32``).  ``speakers`` / ``languages`` are accepted for symmetry
+        with the forward and not used: the aligner reads the symbol embeddings alone.
+        ``ValueError`` before any launch: a model without an aligner (``has_aligner``), ``mel`` not [B, T, n_mels], an item with fewer
+        frames than symbols."""
+        if not self._ready:
+            raise RuntimeError("load_state_dict() or init_random() first")
+        c, dev = self.config, self.device
+        if not self.has_aligner:
+            raise ValueError("align: this model has no aligner (model.learn_alignment off, or the state dict held no `attention.*` tensors)")
+        B, L = ids.shape[:2]
+        if mel.dim() != 3 or mel.shape[0] != B or mel.shape[1] < 1 or mel.shape[2] != c.n_mels:
+            raise ValueError(f"align: mel: expected [{B}, T, {c.n_mels}], got {tuple(mel.shape)}")
+        T = mel.shape[1]
+        n_sym, n_frm = [int(v) for v in lens.tolist()], [int(v) for v in mel_lens.tolist()]
+        if len(n_sym) != B or len(n_frm) != B:
+            raise ValueError(f"align: expected {B} lengths and {B} mel lengths, got {len(n_sym)} and {len(n_frm)}")
+        for i in range(B):
+            if not (1 <= n_sym[i] <= L and n_frm[i] <= T):
+                raise ValueError(f"align: item {i}: {n_sym[i]} symbols of {L}, {n_frm[i]} frames of {T}")
+            if n_frm[i] < n_sym[i]:
+                raise ValueError(f"align: item {i} has {n_frm[i]} frames for {n_sym[i]} symbols: every symbol needs at least one frame")
+        from .heavy import BetaBinomialInterpolator
+        from .train.fs2 import _AlignerT
+
+        lens32 = torch.tensor(n_sym, dtype=torch.int32, device=dev)
+        mel_lens32 = torch.tensor(n_frm, dtype=torch.int32, device=dev)
+        P = lambda name: (self.aligner[f"attention.{name}.conv.weight"], self.aligner[f"attention.{name}.conv.bias"])  # noqa: E731
+        frames = torch.empty(c.n_mels, B, T, device=dev, dtype=torch.float32)
+        frames.copy_(mel.to(dev).permute(2, 0, 1))
+        _mask_cols_(frames, mel_lens32)
+        with ops.exact_f32():
+            k = ops.conv1d_fwd(self._text_embedding(ids, lens32, positional=False), *P("key_proj.0"), 1, 1, act=ops.ACT_RELU)
+            k = ops.conv1d_fwd(k, *P("key_proj.2"))
+            q = ops.conv1d_fwd(frames, *P("query_proj.0"), 1, 1, act=ops.ACT_RELU)
+            q = ops.conv1d_fwd(ops.conv1d_fwd(q, *P("query_proj.2"), act=ops.ACT_RELU), *P("query_proj.4"))
+        if getattr(self, "_prior", None) is None:
+            self._prior = BetaBinomialInterpolator(device=dev)
+        prior = torch.zeros(B, T, L, device=dev, dtype=torch.float64)
+        for i in range(B):  # a function of (frames, symbols) alone: what the preprocessor's attn/ files hold
+            prior[i, : n_frm[i], : n_sym[i]] = self._prior(n_frm[i], n_sym[i])
+        return ops.align_durations(q, k, prior, lens32, mel_lens32, _AlignerT.temperature).to(torch.int64)
+
     def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None, style_lens=None):
         lib, dev, c = _lib.load(), self.device, self.config
         B, L = ids.shape[:2]
@@ -606,20 +707,7 @@ class FastSpeech2:
                 raise ValueError(f"style_mel: expected [{B} or 1, Ts, {c.n_mels}], got {tuple(style_mel.shape)}")
         D = c.encoder.input_dim
         lens32 = lens.to(dev, torch.int32).contiguous()
-        if c.target_text_representation_level == "phonological_features":
-            # ids [B, L, 43] feature vectors: Linear(43 -> D) as a pointwise convolution over [43, B, L], then the positional term
-            # (which also zeroes the padded columns, as the embedding kernel does)
-            if ids.dim() != 3 or ids.shape[2] != N_PHONOLOGICAL_FEATURES:
-                raise ValueError(f"phonological features: expected [B, L, {N_PHONOLOGICAL_FEATURES}], got {tuple(ids.shape)}")
-            feats = ids.to(dev, torch.float32).permute(2, 0, 1).contiguous()
-            x = _conv(feats, self.table.view(D, N_PHONOLOGICAL_FEATURES, 1), None)
-            _chk(lib.evmi_fs2_add_posemb_f32(x.data_ptr(), lens32.data_ptr(), self.inv_freq.data_ptr(), B, L, D, _s(x)), "evmi_fs2_add_posemb_f32")
-        else:
-            ids32 = ids.to(dev, torch.int32).contiguous()
-            x = torch.empty(D, B, L, device=dev, dtype=torch.float32)
-            _chk(lib.evmi_fs2_embed_f32(ids32.data_ptr(), lens32.data_ptr(), self.table.data_ptr(), self.inv_freq.data_ptr(), x.data_ptr(),
-                                        B, L, D, _s(x)), "evmi_fs2_embed_f32")
-        x = self.encoder.forward(x, lens32)
+        x = self.encoder.forward(self._text_embedding(ids, lens32, positional=True), lens32)
         for table, item_ids, what in ((self.speaker_table, speakers, "speakers"), (self.language_table, languages, "languages")):
             if table is not None:
                 if item_ids is None:

@@ -775,15 +775,20 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                       filelist=None, filelist_data=None, output_dir: Path = Path("synthesis_output"), teacher_forcing_directory: Path | None = None,
                       vocoder_model=None, vocoder_config=None, vocoder_global_step: int | None = None, style_reference=None, return_scores: bool = False,
                       text_to_ids=None, audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None,
-                      mask_vocoder_padding: bool = False):
+                      mask_vocoder_padding: bool = False, write_durations: bool = False):
     """``fs2.cli.synthesize.synthesize_helper`` (call site ``everyvoice/demo/app.py:84-106``, same keyword names) for the path this
     library accelerates: texts -> symbol ids -> FastSpeech2 -> (vocoder) -> files through per-format writers.
     Returns ``(config, device, predictions, callbacks)`` with ``callbacks`` keyed by output format ("wav", "spec").
 
     ``texts`` are strings mapped to ids by ``text_to_ids`` (the reference's TextProcessor: CPU string work, out of scope) or already
     lists / tensors of symbol ids; ``filelist_data`` rows (dicts with basename / ids / speaker / language) replace ``texts``.
-    ``teacher_forcing_directory``: read ``duration/<basename>--<speaker>--<language>--duration.pt`` from there and synthesise with
-    those durations -- how the spectrograms for vocoder matching are produced (docs/guides/finetune.md:18-43).
+    ``teacher_forcing_directory``: synthesise every utterance with its ground-truth durations -- how the spectrograms for vocoder
+    matching are produced (docs/guides/finetune.md:18-43): the written spectrogram has the frame count of the real one.  The durations
+    are read from ``duration/<basename>--<speaker>--<language>--duration.pt`` there where that file exists (a model trained with
+    ``learn_alignment: false`` on supplied durations).  Where it does not and the model carries its aligner (``model.has_aligner``: trained
+    with the default ``learn_alignment: true``, whose durations never reach the disk) they come from ``model.align`` over the utterance's
+    ``spec/<basename>--<speaker>--<language>--spec-<input_sr>-<spec_type>.pt`` ([n_mels, T]); otherwise ``FileNotFoundError`` names both
+    files.  ``write_durations``: also save what the aligner found as the ``duration/`` file.
     ``style_reference``: the path of a wav file (the demo's ``gr.Audio(type="filepath")``) or a 1-D float waveform (at
     ``style_reference_sampling_rate``, default the front end's input rate), for a model with the Global Style Token module: it goes through
     the front end the training mels were made with (``audio_config``; default: the model's own ``audio_config`` /
@@ -802,6 +807,8 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
     sr = vocoder_config.preprocessing.audio.output_sampling_rate if vocoder_config is not None else 22050
     in_sr = vocoder_config.preprocessing.audio.input_sampling_rate if vocoder_config is not None else 22050
     hop_out = (vocoder_config.preprocessing.audio.fft_hop_size * (sr // in_sr)) if vocoder_config is not None else 256
+    tf_audio = vocoder_config.preprocessing.audio if vocoder_config is not None else audio_config
+    spec_fn = f"spec-{in_sr}-{getattr(tf_audio, 'spec_type', 'mel-librosa')}.pt"  # the ground-truth spectrogram teacher forcing aligns
     callbacks = {}
     if "wav" in formats:
         if vocoder_model is None:
@@ -838,9 +845,27 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
             kw["languages"] = torch.tensor([model.lang2id[x] for x in lang])
         if teacher_forcing_directory is not None:
             durs = torch.zeros_like(ids)
-            for j, r in enumerate(chunk):
-                d = torch.load(Path(teacher_forcing_directory) / "duration" / SEP.join([r["basename"], spk[j], lang[j], "duration.pt"]), weights_only=True)
-                durs[j, : lens[j]] = d[: lens[j]].long()
+            found = [feature_path(teacher_forcing_directory, "duration", r["basename"], spk[j], lang[j], "duration.pt") for j, r in enumerate(chunk)]
+            for j in range(len(chunk)):
+                if found[j].exists():
+                    durs[j, : lens[j]] = torch.load(found[j], weights_only=True)[: lens[j]].long()
+            missing = [j for j in range(len(chunk)) if not found[j].exists()]
+            if missing:  # no duration file: the model's own aligner over the utterance's ground-truth spectrogram
+                specs = [feature_path(teacher_forcing_directory, "spec", chunk[j]["basename"], spk[j], lang[j], spec_fn) for j in missing]
+                for j, p in zip(missing, specs):
+                    if not getattr(model, "has_aligner", False) or not p.exists():
+                        raise FileNotFoundError(f"teacher forcing {chunk[j]['basename']!r}: no duration file {found[j]} and "
+                                                + (f"no spectrogram {p} to align" if getattr(model, "has_aligner", False)
+                                                   else f"the model has no aligner to find the durations from {p}"))
+                mels = [torch.load(p, weights_only=True).to(torch.float32).transpose(0, 1) for p in specs]  # [T, n_mels] each
+                mel = torch.nn.utils.rnn.pad_sequence(mels, batch_first=True)
+                sel = torch.tensor(missing)
+                akw = {key: kw[key][sel] for key in ("speakers", "languages") if key in kw}
+                aligned = model.align(ids[sel], lens[sel], mel, torch.tensor([m.shape[0] for m in mels]), **akw).cpu()
+                for row, j in enumerate(missing):
+                    durs[j, : lens[j]] = aligned[row, : lens[j]]
+                    if write_durations:
+                        save_tensor(aligned[row, : lens[j]].clone(), found[j])
             kw["durations"] = durs
         if style_mel is not None:
             kw["style_mel"] = style_mel
@@ -864,11 +889,14 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
     return model.config, dev, predictions, callbacks
 
 
-def generate_teacher_forced_specs(model, filelist_data: list[dict], preprocessed_dir, global_step: int = 0, batch_size: int = 16):
+def generate_teacher_forced_specs(model, filelist_data: list[dict], preprocessed_dir, global_step: int = 0, batch_size: int = 16,
+                                  write_durations: bool = False):
     """Vocoder matching, step 1 (docs/guides/finetune.md:18-43: ``everyvoice synthesize from-text ... -O spec
     --teacher-forcing-directory <preprocessed>``): the feature-prediction network's spectrogram of every training utterance under its
     ground-truth durations, written next to the real features as ``synthesized_spec/...--spec-pred-<sr>-mel-librosa.pt`` -- what
-    ``training.finetune: true`` then feeds the vocoder (dataset.SpecDataset)."""
+    ``training.finetune: true`` then feeds the vocoder (dataset.SpecDataset).  The durations: the ``duration/`` files, or the model's
+    aligner over ``spec/`` (``synthesize_helper``); ``write_durations`` keeps what the aligner found as ``duration/`` files."""
     _, _, preds, callbacks = synthesize_helper(model, [], None, None, 1.0, global_step, ["spec"], filelist_data=filelist_data,
-                                               output_dir=Path(preprocessed_dir), teacher_forcing_directory=Path(preprocessed_dir), batch_size=batch_size)
+                                               output_dir=Path(preprocessed_dir), teacher_forcing_directory=Path(preprocessed_dir), batch_size=batch_size,
+                                               write_durations=write_durations)
     return preds

@@ -1399,6 +1399,27 @@ def align_attention_fwd(q, k, prior, text_lens32, temperature):
     return soft, logprob
 
 
+def align_durations(q, k, prior, text_lens32, mel_lens32, temperature, out=None, ws=None):
+    """The aligner at inference (evmi_align_durations_f32): q [A, B, T], k [A, B, L], prior [B, T, L] float64 or None, the lengths
+    int32 [B] on the device -> durations [B, L] int32 of the monotonic search over -temperature * ||q - k||^2 (+ log prior), each item
+    over its own lengths.  ``out`` / ``ws``: the result and the uint8 workspace (``align_durations_ws_bytes``; a torch allocation
+    is aligned) where the caller keeps them, e.g. for a captured call."""
+    A, B, T = q.shape
+    L = k.shape[2]
+    n = align_durations_ws_bytes(B, T, L)
+    if out is None:
+        out = torch.empty(B, L, device=q.device, dtype=torch.int32)
+    if ws is None:
+        ws = WS.get("align_durations", (n + 3) // 4, q.device).view(torch.uint8)
+    _chk(_lib.load().evmi_align_durations_f32(q.data_ptr(), k.data_ptr(), _lib.ptr(prior), text_lens32.data_ptr(), mel_lens32.data_ptr(), out.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), A, B, T, L, temperature, _s(q)), "evmi_align_durations_f32")
+    return out
+
+
+def align_durations_ws_bytes(B, T, L):
+    return int(_lib.load().evmi_align_durations_ws_bytes(B, T, L))
+
+
 def align_attention_bwd(q, k, soft, logprob, prior, hard, dlogprob, text_lens32, temperature, bin_scale, bin_count=None):
     """-> (dq [A, B, T], dk [A, B, L]); ``bin_count``: device scalar the binarisation weight is divided by (the frame count)."""
     lib = _lib.load()

@@ -1058,6 +1058,21 @@ int evmi_align_attention_bwd_f32(const float* soft_dev, const float* logprob_dev
 int evmi_align_qk_grad_f32(const float* x_dev, const float* sums_dev, float* m_dev, int A, long long BN, float coef,
                            void* stream);
 
+/* Alignment at inference (csrc/align_infer.hip): the projected mel q [A][B][T] and text k [A][B][L] straight to the durations
+ * dur [B][L] (frames per token) of the monotonic search, one workgroup per item over its own T_b = clamp(mel_lens[b], 0, T) frames
+ * and L_b = clamp(text_lens[b], 0, L) tokens (both read on the device: a captured call follows each batch).
+ *   value[t][l] = -temperature * sum_a (q[a][t] - k[a][l])^2 (+ logf((float)prior[t][l] + 1e-8f); prior [B][T][L] float64 or NULL)
+ * in fp32, a ascending with fmaf as evmi_align_attention_f32; the per-frame softmax normalisers of that chain cannot change a
+ * monotonic path and are not computed.  The search is evmi_monotonic_align_f32's (same band, arithmetic and tie rule).
+ * dur[b][l] = 0 for l >= L_b; an item with L_b == 0, T_b == 0 or T_b < L_b gets a row of zeros.  Nothing beyond an item's extent
+ * of q, k and prior is read.  ws: evmi_align_durations_ws_bytes bytes, 16-byte aligned (one decision byte a cell, rows padded to
+ * 16 bytes).  1 <= A <= 128 and L <= 1024; more returns EVMI_ERR_UNSUPPORTED.  EVMI_ERR_INVALID_ARG before any device work: a
+ * null pointer (prior excepted), a size below 1, a workspace too small or misaligned. */
+long long evmi_align_durations_ws_bytes(int B, int T, int L);
+int evmi_align_durations_f32(const float* q_dev, const float* k_dev, const double* prior_dev, const int* text_lens_dev,
+                             const int* mel_lens_dev, int* dur_dev, unsigned char* ws_dev, long long ws_bytes, int A, int B,
+                             int T, int L, float temperature, void* stream);
+
 /* Global Style Token module of FastSpeech2 (csrc/gst.hip), fp32.
  * Reference encoder: 3 x 3 convolution with stride 2 and padding 1 on channel-major x [Cin][B][H][W] -> y [Cout][B][OH][OW],
  * O = (n - 1) / 2 + 1 on both axes, w [Cout][Cin][3][3], bias [Cout] or NULL; act 0 (none) or 3 (ReLU: the folded eval-mode
