@@ -341,6 +341,62 @@ def check_style_lens(style_lens, style_mel_shape, what="style_lens"):
     return style_lens
 
 
+FIT_MAX_SYMBOLS = _lib.EVMI_FS2_FIT_MAX_SYMBOLS  # the longest text ``target_frames`` takes (evmi_fs2_fit_durations_i32)
+
+
+def _is_scalar_control(control) -> bool:
+    """One number for the whole batch: whatever ``float()`` takes (a Python or numpy number, a tensor of one element and no axis)."""
+    if isinstance(control, torch.Tensor) and control.dim() > 0:
+        return False
+    try:
+        float(control)
+    except (TypeError, ValueError):
+        return False
+    return True
+
+
+def check_prosody_arguments(B: int, L: int, levels: dict | None = None, duration_control=1.0, pitch_control=1.0, energy_control=1.0,
+                            pitch=None, energy=None, target_frames=None, durations=None) -> None:
+    """Host-side refusals for the steering arguments of ``FastSpeech2.__call__``, for a batch of ``B`` items of
+    ``L`` symbols; ``levels``: ``{"pitch": "phone" | "frame", "energy": ...}`` (default: both "phone").  ``ValueError``, before any launch:
+    a control that is neither a number nor a floating-point tensor [B, L] or [B]; a forced ``pitch`` / ``energy`` that is not a
+    floating-point [B, L] (phone level) or [B, T'] (frame level), or that comes with a non-default control of the same variance (a
+    forced value is embedded as given: the control would be ignored); ``target_frames`` that is not an integer [B], that comes with
+    ``durations``, or with a text above ``FIT_MAX_SYMBOLS`` symbols; a negative target.  Values are looked at only where the tensor lives
+    on the host (a device tensor is not synchronised with; the fit kernel takes a target below 1 as no target)."""
+    levels = levels or {}
+    controls = {"duration": duration_control, "pitch": pitch_control, "energy": energy_control}
+    for name, control in controls.items():
+        if _is_scalar_control(control):
+            continue
+        if not isinstance(control, torch.Tensor) or not control.dtype.is_floating_point or tuple(control.shape) not in ((B, L), (B,)):
+            what = f"{control.dtype} {tuple(control.shape)}" if isinstance(control, torch.Tensor) else type(control).__name__
+            raise ValueError(f"{name}_control: a number, or a floating-point tensor [{B}, {L}] (per symbol) or [{B}] (per item), got {what}")
+    for name, forced in (("pitch", pitch), ("energy", energy)):
+        if forced is None:
+            continue
+        level = levels.get(name, "phone")
+        ok = isinstance(forced, torch.Tensor) and forced.dtype.is_floating_point and forced.dim() == 2 and forced.shape[0] == B \
+            and (forced.shape[1] == L if level == "phone" else forced.shape[1] >= 1)
+        if not ok:
+            what = f"{forced.dtype} {tuple(forced.shape)}" if isinstance(forced, torch.Tensor) else type(forced).__name__
+            raise ValueError(f"{name}: forced values of a {level}-level predictor are a floating-point tensor "
+                             + (f"[{B}, {L}]" if level == "phone" else f"[{B}, T'] with T' at least the longest item's frames") + f", got {what}")
+        if not (_is_scalar_control(controls[name]) and float(controls[name]) == 1.0):
+            raise ValueError(f"{name} is forced and {name}_control is given: forced values are embedded as they are, a control would be ignored")
+    if target_frames is not None:
+        if durations is not None:
+            raise ValueError("target_frames and durations are both given: given durations already fix every item's length")
+        t = target_frames
+        if not isinstance(t, torch.Tensor) or t.dtype.is_floating_point or t.dtype == torch.bool or tuple(t.shape) != (B,):
+            what = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"target_frames: an integer tensor [{B}] (0 = no target for that item), got {what}")
+        if t.device.type == "cpu" and B and int(t.min()) < 0:
+            raise ValueError(f"target_frames: a target cannot be negative, got {t.tolist()}")
+        if L > FIT_MAX_SYMBOLS:
+            raise ValueError(f"target_frames: a text of {L} symbols is above the {FIT_MAX_SYMBOLS} the fit takes")
+
+
 class _Conformer:
     def __init__(self, cfg: ConformerConfig, sd: dict, prefix: str, dev, mask_padding: bool = False):
         self.cfg, self.mask_padding = cfg, mask_padding
@@ -608,18 +664,32 @@ class FastSpeech2:
     @torch.no_grad()
     def __call__(self, ids: torch.Tensor, lens: torch.Tensor, duration_control=1.0, pitch_control=1.0, energy_control=1.0,
                  durations: torch.Tensor | None = None, speakers: torch.Tensor | None = None, languages: torch.Tensor | None = None,
-                 style_mel: torch.Tensor | None = None, style_lens: torch.Tensor | None = None):
+                 style_mel: torch.Tensor | None = None, style_lens: torch.Tensor | None = None, pitch: torch.Tensor | None = None,
+                 energy: torch.Tensor | None = None, target_frames: torch.Tensor | None = None):
         """ids [B, L] (0 = padding), lens [B] -> (mel [B, T, n_mels], postnet mel, durations [B, L], pitch, energy, mel_lens [B]) on the
         device.  ``pitch`` / ``energy`` (the predictions times their control, zero at padded positions) are [B, L] for a phone-level
         predictor and [B, T] for a frame-level one (``variance_predictors.<name>.level``).  ``style_mel`` (a model with the Global Style Token module needs it, any other
         refuses it): the style reference's mel [B, Ts, n_mels], or [1, Ts, n_mels] for one reference serving the whole batch.
         ``style_lens`` ([B] or [1], matching ``style_mel``): the references' frame counts; frames beyond them are absent (DESIGN.md
-        section 25).  None: the references are consumed as given, padding included."""
+        section 25).  None: the references are consumed as given, padding included.
+
+        Steering (refusals: ``check_prosody_arguments``).  Each ``*_control`` is a number for the whole batch, or a
+        float tensor [B, L] (per symbol; values at padded symbols are ignored) or [B] (per item); a per-symbol control of a frame-level
+        predictor follows its symbol through the length regulator.  ``pitch=`` / ``energy=`` force the embedded values, in the domain of
+        the trainer's targets: [B, L] for a phone-level predictor, [B, T'] with T' at least the longest item's frames for a frame-level
+        one; that predictor is not run, and the returned ``pitch`` / ``energy`` are the values that were embedded, zero at padding.
+        ``target_frames`` (integer [B], 0 = no target): the item's mel has exactly that many frames, shared out over its symbols in
+        proportion to the predicted durations times their controls (at most ``FIT_MAX_SYMBOLS`` symbols).  A negative target is refused
+        where ``target_frames`` lives on the host; a tensor on the device is not synchronised with, and a target below 1 there means
+        no target."""
         if not self._ready:
             raise RuntimeError("load_state_dict() or init_random() first")
         style_lens = check_style_lens(style_lens, None if style_mel is None else style_mel.shape)
+        check_prosody_arguments(ids.shape[0], ids.shape[1], self.levels, duration_control, pitch_control, energy_control, pitch, energy,
+                                target_frames, durations)
         with ops.mode(operands=self.precision):
-            return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel, style_lens)
+            return self._forward(ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel, style_lens,
+                                 {"pitch": pitch, "energy": energy}, target_frames)
 
     def _text_embedding(self, ids, lens32, positional: bool):
         """ids [B, L] (or [B, L, 43] phonological feature vectors) -> [D, B, L], zero at the padded columns; ``positional``: plus the
@@ -693,9 +763,18 @@ class FastSpeech2:
             prior[i, : n_frm[i], : n_sym[i]] = self._prior(n_frm[i], n_sym[i])
         return ops.align_durations(q, k, prior, lens32, mel_lens32, _AlignerT.temperature).to(torch.int64)
 
-    def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None, style_lens=None):
+    def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None, style_lens=None,
+                 forced=None, target_frames=None):
         lib, dev, c = _lib.load(), self.device, self.config
         B, L = ids.shape[:2]
+        forced = {k: v for k, v in (forced or {}).items() if v is not None}
+
+        def per_symbol(control):
+            """A tensor control as float32 [B, L] on the device (a [B] one repeated along its row); None for a number."""
+            if _is_scalar_control(control):
+                return None
+            t = control.to(dev, torch.float32)
+            return (t[:, None].expand(B, L) if t.dim() == 1 else t).contiguous()
         if L > c.max_length:
             raise ValueError(f"text of {L} symbols exceeds max_length {c.max_length}")
         if self.gst is None and style_mel is not None:
@@ -726,19 +805,44 @@ class FastSpeech2:
         vp = c.variance_predictors
         variances = (("pitch", self.pitch_predictor, self.pitch_bins, self.pitch_table, vp.pitch.n_bins, pitch_control),
                      ("energy", self.energy_predictor, self.energy_bins, self.energy_table, vp.energy.n_bins, energy_control))
-        out = {}
+        out, steered = {}, {}  # steered[name]: the embedded values as the steered kernel wrote them (what the call returns for that variance)
 
-        def adapt(level, h, h_lens, n):
+        def adapt(level, h, h_lens, n, cum=None):
             """pitch, then energy, for the predictors of this level: predict on h [D, B, n], add the bucket embedding of prediction * control
-            in place (at padded positions too: the value there is 0, and the next predictor's k = 3 convolutions see those columns)"""
+            in place (at padded positions too: the value there is 0, and the next predictor's k = 3 convolutions see those columns).
+            A forced variance or a tensor control goes through evmi_fs2_variance_apply_f32 (``cum``: the frame axis, where a control
+            follows its symbol), everything else through the call it always went through."""
             for name, pred, bins, table, n_bins, control in variances:
-                if self.levels[name] == level:
+                if self.levels[name] != level:
+                    continue
+                values, ctl = forced.get(name), per_symbol(control)
+                if values is None and ctl is None:
                     out[name] = pred.forward(h, h_lens)
                     _chk(lib.evmi_fs2_bucket_embed_add_f32(h.data_ptr(), out[name].data_ptr(), bins.data_ptr(), table.data_ptr(), n_bins, B, n, D,
                                                            float(control), _s(h)), "evmi_fs2_bucket_embed_add_f32")
+                    continue
+                if values is not None:
+                    values, p = values.to(dev, torch.float32).contiguous(), None
+                else:
+                    p = pred.forward(h, h_lens)
+                steered[name] = out[name] = torch.empty(B, n, device=dev, dtype=torch.float32)
+                _chk(lib.evmi_fs2_variance_apply_f32(h.data_ptr(), _lib.ptr(p), _lib.ptr(values), 0 if values is None else values.shape[1],
+                                                     _lib.ptr(ctl), _lib.ptr(cum if ctl is not None else None), h_lens.data_ptr(), bins.data_ptr(),
+                                                     table.data_ptr(), out[name].data_ptr(), n_bins, B, L if cum is not None and ctl is not None else n,
+                                                     n, D, 1.0, _s(h)), "evmi_fs2_variance_apply_f32")
 
         adapt("phone", x, lens32, L)
-        if durations is None:
+        dur_ctl = per_symbol(duration_control)
+        if durations is None and (dur_ctl is not None or target_frames is not None):
+            dur = torch.empty(B, L, device=dev, dtype=torch.int32)
+            weights = torch.empty(B, L, device=dev, dtype=torch.float32) if target_frames is not None else None
+            _chk(lib.evmi_fs2_durations_ctl_i32(log_d.data_ptr(), lens32.data_ptr(), _lib.ptr(dur_ctl), dur.data_ptr(), _lib.ptr(weights), B, L,
+                                                1.0 if dur_ctl is not None else float(duration_control), _s(x)), "evmi_fs2_durations_ctl_i32")
+            if target_frames is not None:
+                target32 = target_frames.to(dev, torch.int32).contiguous()
+                _chk(lib.evmi_fs2_fit_durations_i32(weights.data_ptr(), lens32.data_ptr(), target32.data_ptr(), dur.data_ptr(), B, L, _s(x)),
+                     "evmi_fs2_fit_durations_i32")
+        elif durations is None:
             dur = torch.empty(B, L, device=dev, dtype=torch.int32)
             _chk(lib.evmi_fs2_durations_i32(log_d.data_ptr(), lens32.data_ptr(), dur.data_ptr(), B, L, float(duration_control), _s(x)),
                  "evmi_fs2_durations_i32")
@@ -750,9 +854,12 @@ class FastSpeech2:
         T = int(mel_lens.max())  # the one host sync of the forward: the output length (in front of every frame-level predictor)
         if T <= 0:
             raise ValueError("all predicted durations are zero")
+        for name, values in forced.items():  # (a frame-level tensor can be held to T only here; phone level was checked before any launch)
+            if self.levels[name] == "frame" and values.shape[1] < T:
+                raise ValueError(f"{name}: forced values [{B}, {values.shape[1]}] are shorter than the longest item's {T} frames")
         frames = torch.empty(D, B, T, device=dev, dtype=torch.float32)
         _chk(lib.evmi_length_regulate_cbt_f32(x.data_ptr(), cum.data_ptr(), frames.data_ptr(), D, B, L, T, _s(x)), "evmi_length_regulate_cbt_f32")
-        adapt("frame", frames, mel_lens, T)
+        adapt("frame", frames, mel_lens, T, cum)
         pitch, energy = out["pitch"], out["energy"]
         _chk(lib.evmi_fs2_add_posemb_f32(frames.data_ptr(), mel_lens.data_ptr(), self.inv_freq.data_ptr(), B, T, D, _s(x)), "evmi_fs2_add_posemb_f32")
         y = self.decoder.forward(frames, mel_lens)
@@ -768,5 +875,6 @@ class FastSpeech2:
             post = ops.axpby(1.0, mel, 1.0, h)
             _chk(lib.evmi_mask_cols_f32(post.data_ptr(), mel_lens.data_ptr(), c.n_mels, B, T, _s(x)), "evmi_mask_cols_f32")
         to_btc = lambda t: t.permute(1, 2, 0).contiguous()
-        mult = lambda v, s: v if s == 1.0 else v * s
-        return to_btc(mel), to_btc(post), dur.to(torch.int64), mult(pitch, pitch_control), mult(energy, energy_control), mel_lens.to(torch.int64)
+        mult = lambda name, v, s: v if name in steered or s == 1.0 else v * s
+        return (to_btc(mel), to_btc(post), dur.to(torch.int64), mult("pitch", pitch, pitch_control), mult("energy", energy, energy_control),
+                mel_lens.to(torch.int64))

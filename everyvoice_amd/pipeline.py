@@ -700,11 +700,89 @@ def style_reference_batch(references, cfg: AudioConfig | None = None, device="cu
     return mel, lens.to(mel.device)
 
 
+def target_frames_of(seconds, sampling_rate: int, hop: int) -> torch.Tensor:
+    """Lengths in seconds (one per item; None or 0 = no target) -> ``target_frames`` as ``FastSpeech2.__call__`` takes them:
+    ``round(seconds * sampling_rate / hop)`` frames of the model's front end (``input_sampling_rate`` / ``fft_hop_size``)."""
+    return torch.tensor([int(round(float(s or 0.0) * sampling_rate / hop)) for s in seconds], dtype=torch.int64)
+
+
+def _padded_controls(rows: list[dict], lens: torch.Tensor, defaults: dict) -> dict:
+    """The ``duration_control`` / ``pitch_control`` / ``energy_control`` of a batch of rows: where no row carries one, the call's own
+    value (``defaults``); where one does, a tensor [B, L] -- a row's per-symbol list (one value per symbol, ``ValueError`` otherwise) or
+    number, the call's value for the rows without one, 1 at the padding."""
+    out = {}
+    for key, default in defaults.items():
+        if not any(r.get(key) is not None for r in rows):
+            out[key] = default
+            continue
+        if isinstance(default, torch.Tensor):
+            raise ValueError(f"{key}: given as a tensor for the call and in a row of filelist_data; use one of the two")
+        t = torch.ones(len(rows), int(lens.max()), dtype=torch.float32)
+        for j, r in enumerate(rows):
+            v, n = r.get(key), int(lens[j])
+            if v is None or isinstance(v, (int, float)):
+                t[j, :n] = float(default if v is None else v)
+                continue
+            v = torch.as_tensor(v, dtype=torch.float32).flatten()
+            if v.shape[0] != n:
+                raise ValueError(f"{r.get('basename')!r}: {key} has {v.shape[0]} values for {n} symbols")
+            t[j, :n] = v
+        out[key] = t
+    return out
+
+
+FORCED_FRAMES_SLACK = 11  # values a per-frame pitch / energy file may hold beyond the item's frames (fs2_dataset.py: 10 of the durations + 1)
+
+
+def _forced_variances(model, directory, chunk: list[dict], spk: list, lang: list, durs: torch.Tensor, lens: torch.Tensor) -> dict:
+    """``pitch=`` / ``energy=`` of a teacher-forced batch from the ``pitch/`` and ``energy/`` files next to its spectrograms: what the trainer
+    embedded for these utterances.  Whether a file holds one value per symbol or per frame is the dataset's rule (``FastSpeech2Dataset``),
+    never the tensor's length: per symbol iff ``learn_alignment`` is off and the predictor's level is "phone".  A per-frame file is held
+    to the item's frames under the durations in use (``durs``) with the dataset's tolerances: one value short repeats the last and one
+    value more is cut (pyworld's frame count against the STFT's), and up to ``FORCED_FRAMES_SLACK`` = 11 values more are cut -- that one,
+    plus the 10 frames by which the dataset lets given durations sum to fewer frames than the spectrogram has; anything else is a
+    ``ValueError``.  For a phone-level predictor the per-frame values are averaged over the durations in use
+    (``ops.phone_average``, the trainer's function)."""
+    from .fs2 import variance_settings
+    from .train import ops
+
+    cfg = getattr(model.config, "model", model.config)
+    levels = variance_settings(cfg)["level"]
+    L, frames = durs.shape[1], durs.clamp_min(0).sum(1)
+    out = {}
+    for key in ("pitch", "energy"):
+        file_phone = (not bool(cfg.learn_alignment)) and levels[key] == "phone"
+        rows = []
+        for j, r in enumerate(chunk):
+            p = feature_path(directory, key, r["basename"], spk[j], lang[j], f"{key}.pt")
+            if not p.exists():
+                raise FileNotFoundError(f"teacher forcing {r['basename']!r}: no {key} file {p}")
+            v = torch.load(p, weights_only=True).to(torch.float32).flatten()
+            want = int(lens[j]) if file_phone else int(frames[j])
+            if not file_phone and v.shape[0] > 0 and -1 <= v.shape[0] - want <= FORCED_FRAMES_SLACK:
+                v = v[:want] if v.shape[0] >= want else torch.cat([v, v[-1:]])
+            if v.shape[0] != want:
+                raise ValueError(f"teacher forcing {r['basename']!r}: {p} has {v.shape[0]} values, the configuration "
+                                 f"({'phone' if file_phone else 'frame'} level) wants {want}")
+            rows.append(v)
+        width = L if file_phone else max(1, int(frames.max()))
+        t = torch.zeros(len(chunk), width, dtype=torch.float32)
+        for j, v in enumerate(rows):
+            t[j, : v.shape[0]] = v
+        if not file_phone and levels[key] == "phone":
+            dev = model.device
+            dur32 = durs.clamp_min(0).to(dev, torch.int32).contiguous()
+            pad = torch.arange(L, device=dev)[None, :] >= lens.to(dev)[:, None]
+            t = ops.phone_average(t.to(dev).contiguous(), torch.cumsum(dur32, 1, dtype=torch.int32).contiguous(), dur32, pad)
+        out[key] = t
+    return out
+
+
 def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, out_dir, basenames: list[str], speaker: str = "default",
                          language: str = "default", output_types=("wav", "spec"), sr: int = 22050, hop: int = 256,
                          duration_control: float = 1.0, global_step: int | None = None, style_reference=None,
                          audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None,
-                         mask_vocoder_padding: bool = False) -> list[dict]:
+                         mask_vocoder_padding: bool = False, pitch_control=1.0, energy_control=1.0, target_seconds=None) -> list[dict]:
     """The device part of ``everyvoice synthesize from-text`` (``fs2.cli.synthesize.synthesize_helper``,
     ``everyvoice/demo/app.py:84-106``): token ids -> FastSpeech2 (postnet mel) -> HiFiGAN -> files named as the reference's
     prediction writers name them (``everyvoice/base_cli/prediction_writing_callback.py:35-41``):
@@ -714,8 +792,14 @@ def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, ou
     ``preprocessing.audio``, default as in ``synthesize_helper``): a model with the Global Style Token module needs it, any other refuses it.
     A list of references gives every item its own (``style_reference_batch``: padded together, passed with their lengths).
     ``mask_vocoder_padding``: the vocoder gets the mel lengths (``vocoder(mel, lens=mel_lens)``), so every item's waveform is the one
-    it gets alone, whatever else is in the batch, and the padding frames are not computed.  Off: the batch runs as a rectangle."""
+    it gets alone, whatever else is in the batch, and the padding frames are not computed.  Off: the batch runs as a rectangle.
+    ``duration_control`` / ``pitch_control`` / ``energy_control``: a number, or a tensor per symbol [B, L] or per item [B], as
+    ``FastSpeech2.__call__`` takes them.  ``target_seconds`` (a number for every item, or one per item; None or 0 = no target): the item is
+    synthesised in exactly ``round(seconds * sr / hop)`` frames, i.e. that many times ``hop`` samples."""
     kw = {}
+    if target_seconds is not None:
+        per_item = target_seconds if isinstance(target_seconds, (list, tuple, torch.Tensor)) else [target_seconds] * ids.shape[0]
+        kw["target_frames"] = target_frames_of(per_item, sr, hop)
     if style_reference is not None:
         if not _has_style_tokens(fs2):
             raise ValueError("style_reference given, but this model has no Global Style Token module (model.use_global_style_token_module)")
@@ -726,6 +810,9 @@ def synthesize_from_text(ids: torch.Tensor, lens: torch.Tensor, fs2, vocoder, ou
             kw["style_mel"], kw["style_lens"] = style_reference_batch(style_reference, cfg, fs2.device, style_reference_sampling_rate)
         else:
             kw["style_mel"] = style_reference_mel(style_reference, cfg, fs2.device, style_reference_sampling_rate)
+    for key, control in (("pitch_control", pitch_control), ("energy_control", energy_control)):
+        if isinstance(control, torch.Tensor) or control != 1.0:  # (a call that steers nothing stays the call it was)
+            kw[key] = control
     mel, post, durations, _, _, mel_lens = fs2(ids, lens, duration_control=duration_control, **kw)
     wav = None
     if "wav" in output_types:
@@ -775,7 +862,8 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                       filelist=None, filelist_data=None, output_dir: Path = Path("synthesis_output"), teacher_forcing_directory: Path | None = None,
                       vocoder_model=None, vocoder_config=None, vocoder_global_step: int | None = None, style_reference=None, return_scores: bool = False,
                       text_to_ids=None, audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None,
-                      mask_vocoder_padding: bool = False, write_durations: bool = False):
+                      mask_vocoder_padding: bool = False, write_durations: bool = False, pitch_control=1.0, energy_control=1.0, target_seconds=None,
+                      teacher_force_variances: bool = False):
     """``fs2.cli.synthesize.synthesize_helper`` (call site ``everyvoice/demo/app.py:84-106``, same keyword names) for the path this
     library accelerates: texts -> symbol ids -> FastSpeech2 -> (vocoder) -> files through per-format writers.
     Returns ``(config, device, predictions, callbacks)`` with ``callbacks`` keyed by output format ("wav", "spec").
@@ -795,7 +883,16 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
     ``config.preprocessing.audio``, else the vocoder configuration's, else the defaults) and ONE style embedding serves every text of the call.  A model without the module refuses it; a model with the module refuses a call without it.
     ``mask_vocoder_padding``: the vocoder gets each batch's mel lengths (``vocoder_model(mel, lens=mel_lens)``): an utterance's audio no
     longer depends on ``batch_size`` or on its neighbours, and the padding frames are not computed.  A keyword, not a configuration
-    field (the vocoder's model configuration mirrors the reference's schema).  Off (the default): the batch runs as a rectangle."""
+    field (the vocoder's model configuration mirrors the reference's schema).  Off (the default): the batch runs as a rectangle.
+    Steering: ``pitch_control`` / ``energy_control`` beside ``duration_control``, numbers for the whole call; a
+    ``filelist_data`` row may carry its own under the same names -- a number, or a list with one value per symbol -- which are padded
+    into the batch's [B, L] tensors.  ``target_seconds`` (for the call, or a row's own): the utterance is synthesised in exactly
+    ``round(seconds * input_sampling_rate / fft_hop_size)`` frames of the audio configuration the file names come from.
+    ``teacher_force_variances`` (needs ``teacher_forcing_directory``): every utterance's ``pitch/...--pitch.pt`` and ``energy/...--energy.pt``
+    are read and forced as well, so that the spectrogram is made under what the trainer embedded (``_forced_variances``: the dataset's
+    rule for phone- or frame-level files; a missing file is a ``FileNotFoundError`` naming it).  Off: the predictors' own values."""
+    if teacher_force_variances and teacher_forcing_directory is None:
+        raise ValueError("teacher_force_variances needs a teacher_forcing_directory: the pitch/ and energy/ files are read from it")
     if style_reference is not None and not _has_style_tokens(model):
         raise ValueError("style_reference given, but this model has no Global Style Token module (model.use_global_style_token_module)")
     formats = [getattr(f, "value", f) for f in (output_type if isinstance(output_type, (list, tuple)) else [output_type])]
@@ -807,6 +904,7 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
     sr = vocoder_config.preprocessing.audio.output_sampling_rate if vocoder_config is not None else 22050
     in_sr = vocoder_config.preprocessing.audio.input_sampling_rate if vocoder_config is not None else 22050
     hop_out = (vocoder_config.preprocessing.audio.fft_hop_size * (sr // in_sr)) if vocoder_config is not None else 256
+    hop_in = vocoder_config.preprocessing.audio.fft_hop_size if vocoder_config is not None else 256  # (a frame of the model, in input samples)
     tf_audio = vocoder_config.preprocessing.audio if vocoder_config is not None else audio_config
     spec_fn = f"spec-{in_sr}-{getattr(tf_audio, 'spec_type', 'mel-librosa')}.pt"  # the ground-truth spectrogram teacher forcing aligns
     callbacks = {}
@@ -867,9 +965,18 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                     if write_durations:
                         save_tensor(aligned[row, : lens[j]].clone(), found[j])
             kw["durations"] = durs
+            if teacher_force_variances:
+                kw.update(_forced_variances(model, teacher_forcing_directory, chunk, spk, lang, durs, lens))
         if style_mel is not None:
             kw["style_mel"] = style_mel
-        _, post, durations, _, _, mel_lens = model(ids, lens, duration_control=1.0 if duration_control is None else duration_control, **kw)
+        controls = _padded_controls(chunk, lens, {"duration_control": 1.0 if duration_control is None else duration_control,
+                                                  "pitch_control": pitch_control, "energy_control": energy_control})
+        for key in ("pitch_control", "energy_control"):
+            if isinstance(controls[key], torch.Tensor) or controls[key] != 1.0:  # (a call that steers nothing stays the call it was)
+                kw[key] = controls[key]
+        if target_seconds is not None or any(r.get("target_seconds") is not None for r in chunk):
+            kw["target_frames"] = target_frames_of([target_seconds if r.get("target_seconds") is None else r["target_seconds"] for r in chunk], in_sr, hop_in)
+        _, post, durations, _, _, mel_lens = model(ids, lens, duration_control=controls["duration_control"], **kw)
         wav = None
         if "wav" in formats:
             vmel = post.transpose(1, 2).contiguous()
@@ -890,13 +997,14 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
 
 
 def generate_teacher_forced_specs(model, filelist_data: list[dict], preprocessed_dir, global_step: int = 0, batch_size: int = 16,
-                                  write_durations: bool = False):
+                                  write_durations: bool = False, teacher_force_variances: bool = False):
     """Vocoder matching, step 1 (docs/guides/finetune.md:18-43: ``everyvoice synthesize from-text ... -O spec
     --teacher-forcing-directory <preprocessed>``): the feature-prediction network's spectrogram of every training utterance under its
     ground-truth durations, written next to the real features as ``synthesized_spec/...--spec-pred-<sr>-mel-librosa.pt`` -- what
     ``training.finetune: true`` then feeds the vocoder (dataset.SpecDataset).  The durations: the ``duration/`` files, or the model's
-    aligner over ``spec/`` (``synthesize_helper``); ``write_durations`` keeps what the aligner found as ``duration/`` files."""
+    aligner over ``spec/`` (``synthesize_helper``); ``write_durations`` keeps what the aligner found as ``duration/`` files.
+    ``teacher_force_variances``: the ``pitch/`` and ``energy/`` files are forced too, as the trainer embedded them (``synthesize_helper``)."""
     _, _, preds, callbacks = synthesize_helper(model, [], None, None, 1.0, global_step, ["spec"], filelist_data=filelist_data,
                                                output_dir=Path(preprocessed_dir), teacher_forcing_directory=Path(preprocessed_dir), batch_size=batch_size,
-                                               write_durations=write_durations)
+                                               write_durations=write_durations, teacher_force_variances=teacher_force_variances)
     return preds

@@ -1416,14 +1416,9 @@ class FastSpeech2Trainer(CapturedStep):
     def _phone_level(self, batch, key, cum, dur, pad, T):
         """Phone-level variance targets [B, L]: given as such (``pitch``), or frame-level (``pitch_frames`` [B, T]) averaged over
         each symbol's frames -- ``average_data_by_durations``, everyvoice/preprocessor/preprocessor.py:287-300 (1e-7 for zero frames)."""
-        dev = self.device
         if key in batch:
             return batch[key].masked_fill(pad, 0.0).contiguous()
-        fr = batch[key + "_frames"]
-        B, L = dur.shape
-        sums = torch.empty(B, L, device=dev, dtype=torch.float32)
-        _chk(_lib.load().evmi_length_regulate_bwd_cbt_f32(fr.data_ptr(), cum.data_ptr(), sums.data_ptr(), 1, B, L, T, _s(fr)), "evmi_length_regulate_bwd_cbt_f32")
-        return torch.where(dur > 0, sums / dur.clamp_min(1), torch.full_like(sums, 1e-7)).masked_fill(pad, 0.0).contiguous()
+        return ops.phone_average(batch[key + "_frames"].view(-1, T), cum, dur, pad)
 
     def training_step(self, batch: dict) -> dict:
         """One optimiser step; returns the losses as device scalars (no host synchronisation inside the step).

@@ -1331,6 +1331,19 @@ def mask_cols_(x, lens32):
     return x
 
 
+def phone_average(frames, cum, dur, pad):
+    """Frame-level values [B, T] (float32, contiguous) -> one value per symbol [B, L]: the mean over each symbol's frames
+    (``average_data_by_durations``, everyvoice/preprocessor/preprocessor.py:287-300), 1e-7 for a symbol of no frames, 0 at the padded
+    symbols.  ``cum`` (int32 [B, L]): the inclusive prefix sums of the durations ``dur``; ``pad`` [B, L]: True at the padded symbols.
+    The sums are evmi_length_regulate_bwd_cbt_f32 over one channel.  The trainer's targets and the synthesis path's forced values both
+    come from here."""
+    B, L = dur.shape
+    sums = torch.empty(B, L, device=frames.device, dtype=torch.float32)
+    _chk(_lib.load().evmi_length_regulate_bwd_cbt_f32(frames.data_ptr(), cum.data_ptr(), sums.data_ptr(), 1, B, L, frames.shape[1], _s(frames)),
+         "evmi_length_regulate_bwd_cbt_f32")
+    return torch.where(dur > 0, sums / dur.clamp_min(1), torch.full_like(sums, 1e-7)).masked_fill(pad, 0.0).contiguous()
+
+
 # The attention kernels specialised on the head dimension (csrc/attention_train.hip, attention_cbt_kernel of csrc/fs2_ops.hip) and the
 # largest one the kernels of csrc/attention_generic.hip take.
 ATTENTION_SPECIALISED_HEAD_DIMS = (32, 64, 128)

@@ -859,6 +859,41 @@ int evmi_fs2_bucket_embed_add_f32(float* x_dev, const float* values_dev, const f
 /* dur[b][l] = l < lens[b] ? max(0, round_half_even(exp(log_d) - 1) * control) : 0. */
 int evmi_fs2_durations_i32(const float* log_d_dev, const int* lens_dev, int* dur_dev, int B, int L,
                            float control, void* stream);
+/* Prosody steering (csrc/fs2_prosody.hip): the two entry points above with a control per symbol, forced
+ * values, and the fit of an utterance to a number of frames.  Each refuses its arguments with EVMI_ERR_INVALID_ARG before anything is
+ * launched: a null pointer that is not marked optional, B, L, n or D below 1, n_bins below 2.
+ *
+ * evmi_fs2_variance_apply_f32: the bucket-embedding step.  Per column (b, t) of x [D][B][n] the value v is
+ *   0                                             where t >= lens[b];
+ *   forced[b * forced_stride + t]                 else, where forced is non-null (forced_stride >= n; columns at or beyond lens[b]
+ *                                                 are not read, whatever they hold; pred may then be NULL);
+ *   (pred[b][t] * scalar) * control[b][sym(b, t)] else, taking 1 for a NULL control.
+ * sym(b, t) = t for a NULL cum (a predictor on the symbol axis: control is [B][n], and L must equal n); otherwise the first l with
+ * cum[b][l] > t over the inclusive prefix sums cum [B][L] of the durations, as evmi_length_regulate_cbt_f32 reads them (control is
+ * [B][L]; repeated values = symbols of no frames, the first one included, never own a column).  Writes used[b][t] = v and adds
+ * table[bucket(v)][c] to x[c][b][t] at EVERY column, padded ones included (v = 0 there), bucket = the number of the n_bins - 1
+ * boundaries strictly below v.  With forced and control NULL, and pred zero at the padded columns, x comes out bit for bit as
+ * evmi_fs2_bucket_embed_add_f32(control = scalar) leaves it and used = pred * scalar.  B * n and B * L fit an int. */
+int evmi_fs2_variance_apply_f32(float* x_dev, const float* pred_dev, const float* forced_dev, int forced_stride,
+                                const float* control_dev, const int* cum_dev, const int* lens_dev, const float* bins_dev,
+                                const float* table_dev, float* used_dev, int n_bins, int B, int L, int n, int D, float scalar,
+                                void* stream);
+/* dur[b][l] = l < lens[b] ? (int)max(0, (round_half_even(exp(log_d) - 1) * scalar) * control[b][l]) : 0; control [B][L] or NULL (= 1:
+ * then bit for bit evmi_fs2_durations_i32).  weights_dev (optional, [B][L]): the un-rounded max(0, (exp(log_d) - 1) * scalar *
+ * control[b][l]), zero at padded symbols -- what evmi_fs2_fit_durations_i32 apportions. */
+int evmi_fs2_durations_ctl_i32(const float* log_d_dev, const int* lens_dev, const float* control_dev, int* dur_dev,
+                               float* weights_dev, int B, int L, float scalar, void* stream);
+/* The largest number of symbols evmi_fs2_fit_durations_i32 takes (the remainders of an item live in LDS). */
+#define EVMI_FS2_FIT_MAX_SYMBOLS 4096
+/* Fits items to a number of frames: weights [B][L], lens [B], target [B], dur [B][L] in/out.  target[b] <= 0: row b of dur stays as
+ * it is.  Otherwise row b becomes the largest-remainder apportionment of target[b] frames over the n = lens[b] symbols, in double:
+ * S = sum of w_l (every w_l counts as 1 if S == 0; a negative or NaN weight counts as 0), x_l = (w_l * target) / S, q_l = floor(x_l),
+ * R = target - sum q_l, and the R symbols with the largest x_l - q_l get one frame more, ties to the lower index.  (0 <= R <= n
+ * whatever the roundings of S and x_l: csrc/fs2_prosody.hip has the argument.  The row always sums to the target.)  Symbols of no
+ * frames are allowed; padded symbols get 0.  An item with lens[b] < 1 has no symbol to give a frame to: with a target its row becomes
+ * all zero.  One workgroup per item.  L <= EVMI_FS2_FIT_MAX_SYMBOLS; more returns EVMI_ERR_UNSUPPORTED. */
+int evmi_fs2_fit_durations_i32(const float* weights_dev, const int* lens_dev, const int* target_dev, int* dur_dev, int B, int L,
+                               void* stream);
 /* Length regulator in this layout (everyvoice/utils/heavy.py:12-21 per item, zero padded to T):
  * out[c][b][t] = x[c][b][token(b, t)], cum = inclusive prefix sums of the integer durations [B][L]. */
 int evmi_length_regulate_cbt_f32(const float* x_dev, const int* cum_dev, float* out_dev, int C, int B, int L,
