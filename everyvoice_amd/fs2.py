@@ -18,6 +18,7 @@ folded at load time), embeddings, bucketisation, the integer length regulator in
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import torch
 
@@ -492,6 +493,14 @@ class _VariancePredictor:
         return _mask_cols_(y, lens)[0]
 
 
+class AlignmentScores(NamedTuple):
+    """What ``FastSpeech2.align(return_scores=True)`` says about an alignment (float32 on the device)."""
+
+    ctc: torch.Tensor     # [B]    CTC forward-sum loss of the utterance aligned alone, divided by its symbols (the trainer's loss, without a batch's padding)
+    path: torch.Tensor    # [B]    binarisation loss on the path of the durations: -mean over the frames of log soft attention
+    symbol: torch.Tensor  # [B, L] mean log soft attention of each symbol over its own frames; 0 at padded symbols
+
+
 class FastSpeech2:
     """``model = FastSpeech2(config, stats); model.load_state_dict(sd); mel, post, durations, pitch, energy, mel_lens = model(ids, lens)``
 
@@ -715,7 +724,7 @@ class FastSpeech2:
 
     @torch.no_grad()
     def align(self, ids: torch.Tensor, lens: torch.Tensor, mel: torch.Tensor, mel_lens: torch.Tensor, speakers: torch.Tensor | None = None,
-              languages: torch.Tensor | None = None) -> torch.Tensor:
+              languages: torch.Tensor | None = None, return_scores: bool = False, durations: torch.Tensor | None = None):
         """The durations [B, L] int64 (frames per symbol, zero at padded symbols; row b sums to mel_lens[b]) that the model's learnt
         aligner gives utterance b: ids [B, L], lens [B], its own mel [B, T, n_mels] and mel_lens [B].  What the trainer's aligner
         computes in a step, without the gradients' tensors: keys = the symbol embeddings (no positional term)
@@ -723,8 +732,18 @@ class FastSpeech2:
         Conv(1), both in fp32 in either precision mode; the beta-binomial prior of each item's (frames, symbols); the monotonic search
         over -temperature * ||q - k||^2 + log prior (``evmi_align_durations_f32``).  ``speakers`` / ``languages`` are accepted for symmetry
         with the forward and not used: the aligner reads the symbol embeddings alone.
+        ``return_scores=True`` returns ``(durations, AlignmentScores(ctc, path, symbol))``: how well the aligner's soft attention agrees
+        with those durations (``evmi_align_scores_f32``; float32 on the device) -- ctc [B], the CTC forward-sum loss
+        of each utterance; path [B], its binarisation loss on the path of the durations; symbol [B, L], the mean log soft attention of
+        each symbol over its own frames (0 at padded symbols).  ``durations=`` [B, L] of any integer type are scored in place of the
+        search's, for alignments that come from elsewhere; they are returned as int64 on the device.  A row that does not give its
+        lens[b] symbols mel_lens[b] frames in all is a ``ValueError`` where the tensor lives on the host, and NaN in ``path`` and
+        ``symbol`` where it lives on the device (no transfer is made to look; an int64 entry beyond the int32 range is such a row too, it
+        does not wrap); a symbol with no frame scores NaN.  ``ctc`` is the loss of the utterance aligned ALONE, over its own symbols:
+        with the prior the trainer's value for the same utterance in a padded batch differs, because its first log-softmax runs over
+        the padded symbols too.
         ``ValueError`` before any launch: a model without an aligner (``has_aligner``), ``mel`` not [B, T, n_mels], an item with fewer
-        frames than symbols."""
+        frames than symbols, ``durations`` without ``return_scores`` or not [B, L] integers."""
         if not self._ready:
             raise RuntimeError("load_state_dict() or init_random() first")
         c, dev = self.config, self.device
@@ -742,9 +761,38 @@ class FastSpeech2:
                 raise ValueError(f"align: item {i}: {n_sym[i]} symbols of {L}, {n_frm[i]} frames of {T}")
             if n_frm[i] < n_sym[i]:
                 raise ValueError(f"align: item {i} has {n_frm[i]} frames for {n_sym[i]} symbols: every symbol needs at least one frame")
-        from .heavy import BetaBinomialInterpolator
+        if durations is not None:
+            if not return_scores:
+                raise ValueError("align: durations= are scored, not searched: pass return_scores=True")
+            if tuple(durations.shape) != (B, L) or durations.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError(f"align: durations: expected [{B}, {L}] integers, got {tuple(durations.shape)} {durations.dtype}")
+            if durations.device.type == "cpu":
+                for i in range(B):
+                    row = durations[i, : n_sym[i]].to(torch.int64)
+                    if bool((row < 0).any()) or int(row.sum()) != n_frm[i]:
+                        raise ValueError(f"align: durations: item {i}: the row gives its {n_sym[i]} symbols {int(row.sum())} frames "
+                                         f"(least entry {int(row.min())}), the utterance has {n_frm[i]}")
         from .train.fs2 import _AlignerT
 
+        q, k, prior, lens32, mel_lens32 = self._aligner_inputs(ids, mel, n_sym, n_frm)
+        if not return_scores:
+            return ops.align_durations(q, k, prior, lens32, mel_lens32, _AlignerT.temperature).to(torch.int64)
+        if durations is None:
+            dur32 = ops.align_durations(q, k, prior, lens32, mel_lens32, _AlignerT.temperature)
+            dur64 = dur32.to(torch.int64)
+        else:  # the kernel reads int32: an entry that does not fit there goes in as -1, which no valid row holds (NaN, as any negative entry)
+            dur64 = durations.to(dev, torch.int64)
+            dur32 = torch.where((dur64 >= 0) & (dur64 < 2 ** 31), dur64, -1).to(torch.int32).contiguous()
+        scores = AlignmentScores(*ops.align_scores(q, k, prior, lens32, mel_lens32, dur32, _AlignerT.temperature))
+        return dur64, scores
+
+    def _aligner_inputs(self, ids, mel, n_sym, n_frm):
+        """What both aligner kernels read, computed once: (q [A, B, T], k [A, B, L], prior [B, T, L] float64, lens32, mel_lens32) for
+        ids [B, L], mel [B, T, n_mels] and the checked per-item symbol and frame counts."""
+        from .heavy import BetaBinomialInterpolator
+
+        c, dev = self.config, self.device
+        (B, L), T = ids.shape[:2], mel.shape[1]
         lens32 = torch.tensor(n_sym, dtype=torch.int32, device=dev)
         mel_lens32 = torch.tensor(n_frm, dtype=torch.int32, device=dev)
         P = lambda name: (self.aligner[f"attention.{name}.conv.weight"], self.aligner[f"attention.{name}.conv.bias"])  # noqa: E731
@@ -761,7 +809,7 @@ class FastSpeech2:
         prior = torch.zeros(B, T, L, device=dev, dtype=torch.float64)
         for i in range(B):  # a function of (frames, symbols) alone: what the preprocessor's attn/ files hold
             prior[i, : n_frm[i], : n_sym[i]] = self._prior(n_frm[i], n_sym[i])
-        return ops.align_durations(q, k, prior, lens32, mel_lens32, _AlignerT.temperature).to(torch.int64)
+        return q, k, prior, lens32, mel_lens32
 
     def _forward(self, ids, lens, duration_control, pitch_control, energy_control, durations, speakers, languages, style_mel=None, style_lens=None,
                  forced=None, target_frames=None):

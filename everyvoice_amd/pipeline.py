@@ -863,7 +863,7 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                       vocoder_model=None, vocoder_config=None, vocoder_global_step: int | None = None, style_reference=None, return_scores: bool = False,
                       text_to_ids=None, audio_config: AudioConfig | None = None, style_reference_sampling_rate: int | None = None,
                       mask_vocoder_padding: bool = False, write_durations: bool = False, pitch_control=1.0, energy_control=1.0, target_seconds=None,
-                      teacher_force_variances: bool = False):
+                      teacher_force_variances: bool = False, alignment_scores: bool = False):
     """``fs2.cli.synthesize.synthesize_helper`` (call site ``everyvoice/demo/app.py:84-106``, same keyword names) for the path this
     library accelerates: texts -> symbol ids -> FastSpeech2 -> (vocoder) -> files through per-format writers.
     Returns ``(config, device, predictions, callbacks)`` with ``callbacks`` keyed by output format ("wav", "spec").
@@ -890,7 +890,13 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
     ``round(seconds * input_sampling_rate / fft_hop_size)`` frames of the audio configuration the file names come from.
     ``teacher_force_variances`` (needs ``teacher_forcing_directory``): every utterance's ``pitch/...--pitch.pt`` and ``energy/...--energy.pt``
     are read and forced as well, so that the spectrogram is made under what the trainer embedded (``_forced_variances``: the dataset's
-    rule for phone- or frame-level files; a missing file is a ``FileNotFoundError`` naming it).  Off: the predictors' own values."""
+    rule for phone- or frame-level files; a missing file is a ``FileNotFoundError`` naming it).  Off: the predictors' own values.
+    ``alignment_scores`` (needs ``teacher_forcing_directory``): every prediction record gets the key
+    ``alignment_scores`` -- for an utterance the model aligned itself ``{"attn_ctc", "attn_path"}`` (numbers) and ``"symbol"`` (float32
+    [symbols]: the mean log soft attention of each symbol over its frames), from ``model.align(return_scores=True)``; ``None`` for one
+    whose durations were read from a ``duration/`` file.  (``return_scores`` is the reference's keyword and is not this.)"""
+    if alignment_scores and teacher_forcing_directory is None:
+        raise ValueError("alignment_scores needs a teacher_forcing_directory: the scores are those of the utterances the model aligns there")
     if teacher_force_variances and teacher_forcing_directory is None:
         raise ValueError("teacher_force_variances needs a teacher_forcing_directory: the pitch/ and energy/ files are read from it")
     if style_reference is not None and not _has_style_tokens(model):
@@ -941,6 +947,7 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
             kw["speakers"] = torch.tensor([model.speaker2id[s] for s in spk])
         if getattr(model, "lang2id", None) and getattr(model.config, "multilingual", False):
             kw["languages"] = torch.tensor([model.lang2id[x] for x in lang])
+        scored = {}  # row of the chunk -> the alignment scores of an utterance the model aligned itself
         if teacher_forcing_directory is not None:
             durs = torch.zeros_like(ids)
             found = [feature_path(teacher_forcing_directory, "duration", r["basename"], spk[j], lang[j], "duration.pt") for j, r in enumerate(chunk)]
@@ -959,7 +966,15 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
                 mel = torch.nn.utils.rnn.pad_sequence(mels, batch_first=True)
                 sel = torch.tensor(missing)
                 akw = {key: kw[key][sel] for key in ("speakers", "languages") if key in kw}
-                aligned = model.align(ids[sel], lens[sel], mel, torch.tensor([m.shape[0] for m in mels]), **akw).cpu()
+                if alignment_scores:
+                    akw["return_scores"] = True
+                aligned = model.align(ids[sel], lens[sel], mel, torch.tensor([m.shape[0] for m in mels]), **akw)
+                if alignment_scores:
+                    aligned, sc = aligned
+                    ctc, on_path, symbol = sc.ctc.cpu(), sc.path.cpu(), sc.symbol.cpu()
+                    for row, j in enumerate(missing):
+                        scored[j] = {"attn_ctc": float(ctc[row]), "attn_path": float(on_path[row]), "symbol": symbol[row, : lens[j]].clone()}
+                aligned = aligned.cpu()
                 for row, j in enumerate(missing):
                     durs[j, : lens[j]] = aligned[row, : lens[j]]
                     if write_durations:
@@ -984,6 +999,8 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
         for j, r in enumerate(chunk):
             T = int(mel_lens[j])
             rec = {"basename": r["basename"], "speaker": spk[j], "language": lang[j], "frames": T, "durations": durations[j, : int(lens[j])].cpu()}
+            if alignment_scores:
+                rec["alignment_scores"] = scored.get(j)
             if "spec" in formats:
                 path = callbacks["spec"].get_filename(r["basename"], spk[j], lang[j])
                 save_tensor(post[j, :T].transpose(0, 1).contiguous(), path)
@@ -997,14 +1014,70 @@ def synthesize_helper(model, texts: list, language: str | None, speaker: str | N
 
 
 def generate_teacher_forced_specs(model, filelist_data: list[dict], preprocessed_dir, global_step: int = 0, batch_size: int = 16,
-                                  write_durations: bool = False, teacher_force_variances: bool = False):
+                                  write_durations: bool = False, teacher_force_variances: bool = False, alignment_scores: bool = False):
     """Vocoder matching, step 1 (docs/guides/finetune.md:18-43: ``everyvoice synthesize from-text ... -O spec
     --teacher-forcing-directory <preprocessed>``): the feature-prediction network's spectrogram of every training utterance under its
     ground-truth durations, written next to the real features as ``synthesized_spec/...--spec-pred-<sr>-mel-librosa.pt`` -- what
     ``training.finetune: true`` then feeds the vocoder (dataset.SpecDataset).  The durations: the ``duration/`` files, or the model's
     aligner over ``spec/`` (``synthesize_helper``); ``write_durations`` keeps what the aligner found as ``duration/`` files.
-    ``teacher_force_variances``: the ``pitch/`` and ``energy/`` files are forced too, as the trainer embedded them (``synthesize_helper``)."""
+    ``teacher_force_variances``: the ``pitch/`` and ``energy/`` files are forced too, as the trainer embedded them (``synthesize_helper``).
+    ``alignment_scores``: each record carries the aligner's scores of the utterance, ``None`` where a ``duration/`` file was read
+    (``synthesize_helper``)."""
     _, _, preds, callbacks = synthesize_helper(model, [], None, None, 1.0, global_step, ["spec"], filelist_data=filelist_data,
                                                output_dir=Path(preprocessed_dir), teacher_forcing_directory=Path(preprocessed_dir), batch_size=batch_size,
-                                               write_durations=write_durations, teacher_force_variances=teacher_force_variances)
+                                               write_durations=write_durations, teacher_force_variances=teacher_force_variances,
+                                               alignment_scores=alignment_scores)
     return preds
+
+
+ALIGNMENT_SCORE_FIELDS = ("basename", "speaker", "language", "symbols", "frames", "seconds", "symbols_per_second", "attn_ctc", "attn_path",
+                          "worst_symbol", "worst_symbol_score")
+
+
+def score_alignments(model, filelist_data: list[dict], preprocessed_dir, batch_size: int = 16, audio_config: AudioConfig | None = None,
+                     out_path=None) -> list[dict]:
+    """The device half of the reference's ``everyvoice check data`` (``base_cli/check_group.py:15-50``): how well the model's own aligner
+    explains every utterance of a preprocessed dataset, for finding the mis-transcribed and the clipped ones.
+    Each row's ``spec/<basename>--<speaker>--<language>--spec-<input_sr>-<spec_type>.pt`` ([n_mels, T]; rate and type from
+    ``audio_config``, default 22050 / mel-librosa) is read as teacher forcing reads it, the rows are aligned in ragged batches of
+    ``batch_size`` by ``model.align(return_scores=True)``, and one record per row comes back in input order: ``basename``, ``speaker``,
+    ``language``, ``symbols``, ``frames``, ``seconds`` (frames * fft_hop_size / input_sampling_rate), ``symbols_per_second``, ``attn_ctc``
+    (the CTC forward-sum loss the trainer minimises, per symbol, of the utterance aligned ALONE over its own symbols: not the value a
+    padded training batch produces, whose first log-softmax runs over the padded symbols too -- DESIGN.md section 34), ``attn_path`` (the binarisation loss on the aligner's own path),
+    ``worst_symbol`` / ``worst_symbol_score`` (the index and the value of the lowest mean log soft attention over a symbol's frames) and
+    ``durations`` (int64 [symbols]).  An utterance's record does not depend on ``batch_size`` or on its neighbours.
+    ``out_path``: the records without the durations as a pipe-separated file with a header line.
+    ``ValueError`` before any file is read: a model without an aligner.  ``FileNotFoundError``: a missing spectrogram, by name."""
+    if not getattr(model, "has_aligner", False):
+        raise ValueError("score_alignments: this model has no aligner (model.learn_alignment off, or the state dict held no `attention.*` tensors)")
+    in_sr = audio_config.input_sampling_rate if audio_config is not None else 22050
+    hop = audio_config.fft_hop_size if audio_config is not None else 256
+    spec_fn = f"spec-{in_sr}-{getattr(audio_config, 'spec_type', 'mel-librosa')}.pt"
+    rows = [dict(r) for r in filelist_data]
+    records = []
+    for lo in range(0, len(rows), batch_size):
+        chunk = rows[lo : lo + batch_size]
+        spk = [r.get("speaker") or "default" for r in chunk]
+        lang = [r.get("language") or "default" for r in chunk]
+        paths = [feature_path(preprocessed_dir, "spec", r["basename"], spk[j], lang[j], spec_fn) for j, r in enumerate(chunk)]
+        for r, p in zip(chunk, paths):
+            if not p.exists():
+                raise FileNotFoundError(f"score_alignments {r['basename']!r}: no spectrogram {p} to align")
+        lens = torch.tensor([len(r["ids"]) for r in chunk])
+        ids = torch.zeros(len(chunk), int(lens.max()), dtype=torch.long)
+        for j, r in enumerate(chunk):
+            ids[j, : lens[j]] = torch.as_tensor(r["ids"], dtype=torch.long)
+        mels = [torch.load(p, weights_only=True).to(torch.float32).transpose(0, 1) for p in paths]  # [T, n_mels] each
+        durations, sc = model.align(ids, lens, torch.nn.utils.rnn.pad_sequence(mels, batch_first=True), torch.tensor([m.shape[0] for m in mels]),
+                                    return_scores=True)
+        durations, ctc, on_path, symbol = durations.cpu(), sc.ctc.cpu(), sc.path.cpu(), sc.symbol.cpu()
+        for j, r in enumerate(chunk):
+            n, frames = int(lens[j]), mels[j].shape[0]
+            worst = int(torch.argmin(symbol[j, :n]))
+            seconds = frames * hop / in_sr
+            records.append({"basename": r["basename"], "speaker": spk[j], "language": lang[j], "symbols": n, "frames": frames, "seconds": seconds,
+                            "symbols_per_second": n / seconds, "attn_ctc": float(ctc[j]), "attn_path": float(on_path[j]), "worst_symbol": worst,
+                            "worst_symbol_score": float(symbol[j, worst]), "durations": durations[j, :n].clone()})
+    if out_path is not None:
+        GpuPreprocessor.write_filelist(records, out_path, fields=ALIGNMENT_SCORE_FIELDS)
+    return records

@@ -1433,6 +1433,31 @@ def align_durations_ws_bytes(B, T, L):
     return int(_lib.load().evmi_align_durations_ws_bytes(B, T, L))
 
 
+def align_scores(q, k, prior, text_lens32, mel_lens32, dur32, temperature, blank_logprob=-1.0, out=None):
+    """How well the aligner's soft attention agrees with the duration rows ``dur32`` [B, L] int32 (evmi_align_scores_f32; q, k, prior
+    and the lengths as for ``align_durations``) -> (ctc [B], path [B], symbol [B, L]) float32 on the device: the CTC forward-sum loss
+    of each item, its binarisation loss on the path of its row, and the mean log soft attention of each symbol over its own frames
+    (0 at padded symbols, NaN for a symbol without a frame; NaN path and symbols for a row that does not sum to the item's frames).
+    ``out``: the three results where the caller keeps them, e.g. for a captured call."""
+    A, B, T = q.shape
+    L = k.shape[2]
+    ctc, path, symbol = out if out is not None else (torch.empty(B, device=q.device, dtype=torch.float32), torch.empty(B, device=q.device, dtype=torch.float32),
+                                                     torch.empty(B, L, device=q.device, dtype=torch.float32))
+    _chk(_lib.load().evmi_align_scores_f32(q.data_ptr(), k.data_ptr(), _lib.ptr(prior), text_lens32.data_ptr(), mel_lens32.data_ptr(), dur32.data_ptr(),
+                                           ctc.data_ptr(), path.data_ptr(), symbol.data_ptr(), A, B, T, L, temperature, blank_logprob, _s(q)),
+         "evmi_align_scores_f32")
+    return ctc, path, symbol
+
+
+def align_scores_plan(A, L):
+    """(frames of one LDS tile, whether the k image sits in LDS) of evmi_align_scores_f32 at A channels and L symbols: host arithmetic."""
+    import ctypes
+
+    ty, klds = ctypes.c_int(0), ctypes.c_int(0)
+    _chk(_lib.load().evmi_align_scores_plan(A, L, ctypes.byref(ty), ctypes.byref(klds)), "evmi_align_scores_plan")
+    return ty.value, bool(klds.value)
+
+
 def align_attention_bwd(q, k, soft, logprob, prior, hard, dlogprob, text_lens32, temperature, bin_scale, bin_count=None):
     """-> (dq [A, B, T], dk [A, B, L]); ``bin_count``: device scalar the binarisation weight is divided by (the frame count)."""
     lib = _lib.load()

@@ -1108,6 +1108,27 @@ int evmi_align_durations_f32(const float* q_dev, const float* k_dev, const doubl
                              const int* mel_lens_dev, int* dur_dev, unsigned char* ws_dev, long long ws_bytes, int A, int B,
                              int T, int L, float temperature, void* stream);
 
+/* Alignment scores (csrc/align_scores.hip): how well the aligner's soft attention agrees with a duration row.  q, k, prior and the
+ * lengths as for evmi_align_durations_f32; dur [B][L] int32 is the row to score (what that call wrote, or any other).  One workgroup
+ * per item over its own T_b x L_b rectangle, no workspace.  In fp32:
+ *   logit[y][x] = -temperature * sum_a (q[a][y] - k[a][x])^2, all x < L_b;  lp = logit - lse_x(logit) + logf((float)prior + 1e-8f)
+ *   with a prior, lp = logit without;  soft = exp(lp - lse_x(lp)).
+ *   ctc[b]       the CTC forward-sum loss of the item as evmi_forward_sum_loss_f32 writes it for lp: log-softmax over
+ *                [blank_logprob, lp[y][0 .. L_b)] per frame, targets 1 .. L_b, divided by L_b.  It never reads dur.
+ *   path[b]      -(1 / T_b) * sum_y log(max(soft[y][p(y)], 1e-12)) on the path where symbol x holds dur[b][x] consecutive frames.
+ *   symbol[b][x] the mean of log(max(soft, 1e-12)) over symbol x's own frames; 0 for x >= L_b; NaN for a symbol with no frame.
+ * A row whose first L_b entries do not sum to T_b (or hold a negative entry) gives NaN in path[b] and in symbol[b][0 .. L_b); no
+ * value in dur makes the kernel address memory outside the item.  An item with L_b == 0, T_b == 0 or T_b < L_b gets NaN in ctc and
+ * path and a row of zeros in symbol.  An item's outputs are the same bits alone and in any batch, at any padded T and L; nothing
+ * beyond an item's extent of q, k, prior and dur is read.  1 <= A <= 128 and L <= 1023 (evmi_forward_sum_grad_f32's limit); more
+ * returns EVMI_ERR_UNSUPPORTED.  EVMI_ERR_INVALID_ARG before any device work: a null pointer (prior excepted), a size below 1.
+ * evmi_align_scores_plan (host arithmetic, no GPU; the same refusals): the frames of one LDS tile at (A, L) and whether the item's k
+ * image sits in LDS (1) or is read through the caches (0). */
+int evmi_align_scores_plan(int A, int L, int* frame_tile, int* k_in_lds);
+int evmi_align_scores_f32(const float* q_dev, const float* k_dev, const double* prior_dev, const int* text_lens_dev,
+                          const int* mel_lens_dev, const int* dur_dev, float* ctc_dev, float* path_dev, float* symbol_dev, int A,
+                          int B, int T, int L, float temperature, float blank_logprob, void* stream);
+
 /* Global Style Token module of FastSpeech2 (csrc/gst.hip), fp32.
  * Reference encoder: 3 x 3 convolution with stride 2 and padding 1 on channel-major x [Cin][B][H][W] -> y [Cout][B][OH][OW],
  * O = (n - 1) / 2 + 1 on both axes, w [Cout][Cin][3][3], bias [Cout] or NULL; act 0 (none) or 3 (ReLU: the folded eval-mode
