@@ -28,6 +28,7 @@ import math
 import wave
 from glob import glob
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -1080,4 +1081,201 @@ def score_alignments(model, filelist_data: list[dict], preprocessed_dir, batch_s
                             "worst_symbol_score": float(symbol[j, worst]), "durations": durations[j, :n].clone()})
     if out_path is not None:
         GpuPreprocessor.write_filelist(records, out_path, fields=ALIGNMENT_SCORE_FIELDS)
+    return records
+
+
+# ---- synthesis against the recordings ------------------------------------------------------------------------
+MCD_DB_SCALE = 10.0 * math.sqrt(2.0) / math.log(10.0)
+MCD_MAX_CEPSTRA = 24  # evmi_dtw_cepstral_f32's limit on K
+
+
+class MelCepstralDistortion(NamedTuple):
+    """``mel_cepstral_distortion``'s results, on the device: mcd [B] (dB, the mean along the warping path), steps [B] int32 (the path's
+    cells), lo / hi [B, Tb] int32 (first and last frame of ``mel_a`` the path pairs with frame j of ``mel_b``; -1 beyond the item),
+    frame_mcd [B, Tb] (dB, the mean over the path's cells of that column; 0 beyond the item)."""
+
+    mcd: torch.Tensor
+    steps: torch.Tensor
+    lo: torch.Tensor
+    hi: torch.Tensor
+    frame_mcd: torch.Tensor
+
+
+def mel_cepstral_basis(n_mels: int, n_cepstra: int = 13) -> torch.Tensor:
+    """Rows k = 1 .. n_cepstra of the orthonormal DCT-II over n_mels bins, sqrt(2 / M) cos(pi / M (m + 1/2) k), built in float64 and
+    returned as float32 [n_cepstra, n_mels].  c0 (the frame's level) is left out."""
+    if not 1 <= n_cepstra <= n_mels - 1:
+        raise ValueError(f"mel_cepstral_basis: n_cepstra must be between 1 and n_mels - 1 = {n_mels - 1}, got {n_cepstra}")
+    m = torch.arange(n_mels, dtype=torch.float64)
+    k = torch.arange(1, n_cepstra + 1, dtype=torch.float64)
+    return (math.sqrt(2.0 / n_mels) * torch.cos(math.pi / n_mels * (m[None, :] + 0.5) * k[:, None])).to(torch.float32)
+
+
+def _check_n_cepstra(n_cepstra: int, n_mels: int, who: str) -> None:
+    if not 1 <= n_cepstra <= MCD_MAX_CEPSTRA or n_cepstra > n_mels - 1:
+        raise ValueError(f"{who}: n_cepstra must be between 1 and min({MCD_MAX_CEPSTRA}, n_mels - 1 = {n_mels - 1}), got {n_cepstra}")
+
+
+def mel_cepstral_distortion(mel_a: torch.Tensor, lens_a: torch.Tensor, mel_b: torch.Tensor, lens_b: torch.Tensor,
+                            n_cepstra: int = 13) -> MelCepstralDistortion:
+    """Mel-cepstral distortion along the dynamic-time-warping path (MCD-DTW), in dB, of two batches of natural-log mels as the
+    preprocessor stores them and ``FastSpeech2.__call__`` returns them: mel_a [B, Ta, n_mels], mel_b [B, Tb, n_mels] time-major with
+    their frame counts; one launch (``evmi_dtw_cepstral_f32``), each item over its own lengths, Tb <= 1024.
+
+    This is the distortion of the LOG-MEL CEPSTRUM (the DCT of the log-mel frame: MFCC 1 .. n_cepstra, c0 left out), scaled by
+    10 sqrt(2) / ln 10 -- not of an mcep (mel-generalised cepstral) analysis of the waveform.  Absolute values compare only with
+    tools that define it the same way."""
+    from .train import ops
+
+    if mel_a.dim() != 3 or mel_b.dim() != 3 or mel_a.shape[0] != mel_b.shape[0] or mel_a.shape[2] != mel_b.shape[2]:
+        raise ValueError(f"mel_cepstral_distortion: expected [B, Ta, n_mels] and [B, Tb, n_mels], got {tuple(mel_a.shape)} and {tuple(mel_b.shape)}")
+    _check_n_cepstra(n_cepstra, mel_a.shape[2], "mel_cepstral_distortion")
+    if not mel_a.is_cuda:
+        raise RuntimeError("everyvoice_amd.pipeline.mel_cepstral_distortion computes on the GPU only (no CPU fallback)")
+    dev = mel_a.device
+    a, b = mel_a.to(torch.float32).contiguous(), mel_b.to(dev, torch.float32).contiguous()
+    basis = mel_cepstral_basis(a.shape[2], n_cepstra).to(dev)
+    la, lb = torch.as_tensor(lens_a).to(dev, torch.int32).contiguous(), torch.as_tensor(lens_b).to(dev, torch.int32).contiguous()
+    return MelCepstralDistortion(*ops.dtw_cepstral(a, la, b, lb, basis, MCD_DB_SCALE))
+
+
+SYNTHESIS_EVALUATION_FIELDS = ("basename", "speaker", "language", "symbols", "frames_ref", "frames_syn", "length_ratio", "mcd_dtw", "mcd_dtw_sl",
+                               "path_steps", "off_diagonal", "worst_symbol", "worst_symbol_mcd", "f0_rmse_cents", "vuv_error", "voiced_pairs", "note")
+
+
+def f0_agreement(f0_syn, f0_ref, hi):
+    """(f0_rmse_cents, vuv_error, voiced_pairs) of two uninterpolated F0 tracks (Hz, 0 = unvoiced; 1-D, on the host): recorded frame j
+    is paired with synthesized frame hi[j].  RMSE in cents over the pairs that are both voiced (NaN without any); the share of recorded
+    frames whose voicing differs."""
+    f0_syn, f0_ref, hi = np.asarray(f0_syn, np.float64), np.asarray(f0_ref, np.float64), np.asarray(hi, np.int64)
+    n = min(len(hi), len(f0_ref))
+    ref, syn = f0_ref[:n], f0_syn[np.clip(hi[:n], 0, len(f0_syn) - 1)]
+    both = (ref > 0) & (syn > 0)
+    rmse = float(np.sqrt(np.mean((1200.0 * np.log2(syn[both] / ref[both])) ** 2))) if both.any() else float("nan")
+    return rmse, float(np.mean((ref > 0) != (syn > 0))), int(both.sum())
+
+
+def evaluate_synthesis(model, filelist_data: list[dict], preprocessed_dir, batch_size: int = 16, audio_config: AudioConfig | None = None,
+                       vocoder=None, duration_control: float = 1.0, n_cepstra: int = 13, out_path=None) -> list[dict]:
+    """How close the model's own, free-running synthesis is to the recording, per utterance of a preprocessed dataset (DESIGN.md section
+    35): the free-running twin of ``score_alignments``.  Every row is synthesized from its symbols alone (speakers and languages
+    resolved as ``synthesize_helper`` does; a model with the Global Style Token module gets the utterance's own recorded mel, with its
+    length, as its style reference), its ``spec/`` file is read exactly as ``score_alignments`` reads it, and
+    ``mel_cepstral_distortion(synthesized, recording)`` warps one onto the other.  One record per row, in input order:
+    ``basename``, ``speaker``, ``language``, ``symbols``, ``frames_ref``, ``frames_syn``, ``length_ratio`` (syn / ref), ``mcd_dtw`` (dB; of
+    the log-mel cepstrum, see ``mel_cepstral_distortion``), ``mcd_dtw_sl`` (mcd_dtw x max(frames) / min(frames): a wrong length costs),
+    ``path_steps``, ``off_diagonal`` (1 - diagonal steps / (path_steps - 1); 0 for a one-cell path), ``worst_symbol`` /
+    ``worst_symbol_mcd`` (the symbol with the highest mean per-frame distortion over its recorded frames; the recording's durations
+    come from its ``duration/`` file, else from ``model.align`` where ``model.has_aligner``, else both are None; symbols without frames
+    are skipped), ``lo`` / ``hi`` (int32 [frames_ref]: the synthesized frames the path pairs with each recorded frame).
+    ``vocoder``: also ``f0_rmse_cents``, ``vuv_error``, ``voiced_pairs`` (``f0_agreement``) between ``extract_pitch(interpolate=False)`` of
+    the vocoded synthesis and of the recording ``audio/...--audio-<output_sr>.wav``, both at the output rate with a hop of
+    fft_hop_size x (output_sr // input_sr); recorded frame j is paired with synthesized frame hi[j].  Without a vocoder: None.
+    An utterance beyond the kernel's limits (more than 1024 recorded frames, or more synthesized frames than ``ops.dtw_plan`` allows)
+    gets NaN metrics and a ``note``, not an exception.
+    A record does not depend on ``batch_size`` or on its neighbours whenever the model's mel does not: that needs the model's
+    ``mask_padding``; the warping itself never depends on them.
+    ``out_path``: the records without the tensors as a pipe-separated file with a header line.
+    ``ValueError`` before any file is read: ``n_cepstra`` outside 1 .. 24 or above n_mels - 1.  ``FileNotFoundError``: a missing
+    spectrogram or (with a vocoder) recording, by name."""
+    from .train import ops
+
+    n_mels = model.config.n_mels
+    _check_n_cepstra(n_cepstra, n_mels, "evaluate_synthesis")
+    in_sr = audio_config.input_sampling_rate if audio_config is not None else 22050
+    out_sr = audio_config.output_sampling_rate if audio_config is not None else 22050
+    hop = audio_config.fft_hop_size if audio_config is not None else 256
+    hop_out = hop * (out_sr // in_sr)
+    spec_fn = f"spec-{in_sr}-{getattr(audio_config, 'spec_type', 'mel-librosa')}.pt"
+    nan = float("nan")
+    rows = [dict(r) for r in filelist_data]
+    records = []
+    for start in range(0, len(rows), batch_size):
+        chunk = rows[start : start + batch_size]
+        spk = [r.get("speaker") or "default" for r in chunk]
+        lang = [r.get("language") or "default" for r in chunk]
+        paths = [feature_path(preprocessed_dir, "spec", r["basename"], spk[j], lang[j], spec_fn) for j, r in enumerate(chunk)]
+        for r, p in zip(chunk, paths):
+            if not p.exists():
+                raise FileNotFoundError(f"evaluate_synthesis {r['basename']!r}: no spectrogram {p} to compare with")
+        wavs = [feature_path(preprocessed_dir, "audio", r["basename"], spk[j], lang[j], f"audio-{out_sr}.wav") for j, r in enumerate(chunk)]
+        if vocoder is not None:
+            for r, p in zip(chunk, wavs):
+                if not p.exists():
+                    raise FileNotFoundError(f"evaluate_synthesis {r['basename']!r}: no recording {p} for the F0 comparison")
+        lens = torch.tensor([len(r["ids"]) for r in chunk])
+        ids = torch.zeros(len(chunk), int(lens.max()), dtype=torch.long)
+        for j, r in enumerate(chunk):
+            ids[j, : lens[j]] = torch.as_tensor(r["ids"], dtype=torch.long)
+        mels = [torch.load(p, weights_only=True).to(torch.float32).transpose(0, 1) for p in paths]  # [T, n_mels] each
+        ref = torch.nn.utils.rnn.pad_sequence(mels, batch_first=True)
+        ref_lens = torch.tensor([m.shape[0] for m in mels])
+        kw = {}
+        if getattr(model, "speaker2id", None) and getattr(model.config, "multispeaker", False):
+            kw["speakers"] = torch.tensor([model.speaker2id[s] for s in spk])
+        if getattr(model, "lang2id", None) and getattr(model.config, "multilingual", False):
+            kw["languages"] = torch.tensor([model.lang2id[x] for x in lang])
+        if _has_style_tokens(model):
+            kw["style_mel"], kw["style_lens"] = ref, ref_lens
+        _, post, _, _, _, syn_lens = model(ids, lens, duration_control=duration_control, **kw)
+        syn_lens = syn_lens.cpu()
+        dev = post.device
+        # the warping, over the rows inside the kernel's limits
+        max_ta = ops.dtw_plan(n_cepstra, 1)[0]
+        notes = [f"more than 1024 recorded frames ({int(ref_lens[j])}): not warped" if int(ref_lens[j]) > 1024 else
+                 f"more than {max_ta} synthesized frames ({int(syn_lens[j])}): not warped" if int(syn_lens[j]) > max_ta else None for j in range(len(chunk))]
+        ok = [j for j in range(len(chunk)) if notes[j] is None]
+        warped = {}
+        if ok:
+            sel = torch.tensor(ok)
+            a = post[sel.to(dev), : int(syn_lens[sel].max())].contiguous()
+            b = ref[sel, : int(ref_lens[sel].max())].contiguous().to(dev)
+            got = mel_cepstral_distortion(a, syn_lens[sel], b, ref_lens[sel], n_cepstra)
+            mcd, steps, lo, hi, frame_mcd = (t.cpu() for t in got)
+            warped = {j: (float(mcd[row]), int(steps[row]), lo[row, : int(ref_lens[j])].clone(), hi[row, : int(ref_lens[j])].clone(),
+                          frame_mcd[row, : int(ref_lens[j])]) for row, j in enumerate(ok)}
+        # the recording's durations: the duration/ file, else the model's aligner
+        durs = {}
+        found = [feature_path(preprocessed_dir, "duration", r["basename"], spk[j], lang[j], "duration.pt") for j, r in enumerate(chunk)]
+        for j in range(len(chunk)):
+            if found[j].exists():
+                durs[j] = torch.load(found[j], weights_only=True)[: lens[j]].long()
+        missing = [j for j in range(len(chunk)) if j not in durs]
+        if missing and getattr(model, "has_aligner", False):
+            sel = torch.tensor(missing)
+            akw = {key: kw[key][sel] for key in ("speakers", "languages") if key in kw}
+            aligned = model.align(ids[sel], lens[sel], ref[sel, : int(ref_lens[sel].max())].contiguous(), ref_lens[sel], **akw).cpu()
+            for row, j in enumerate(missing):
+                durs[j] = aligned[row, : lens[j]].long()
+        f0 = {}
+        if vocoder is not None:
+            wav = vocoder(post.transpose(1, 2).contiguous(), lens=syn_lens.to(dev))
+            for j in ok:
+                recorded = load_wav(wavs[j])[0][:1].to(dev)
+                pair = [extract_pitch(x, None, hop_out, out_sr, interpolate=False)[0].cpu().numpy()
+                        for x in (wav[j, :1, : int(syn_lens[j]) * hop_out], recorded)]
+                f0[j] = f0_agreement(pair[0], pair[1], warped[j][3].numpy())
+        for j, r in enumerate(chunk):
+            n, f_ref, f_syn = int(lens[j]), int(ref_lens[j]), int(syn_lens[j])
+            rec = {"basename": r["basename"], "speaker": spk[j], "language": lang[j], "symbols": n, "frames_ref": f_ref, "frames_syn": f_syn,
+                   "length_ratio": f_syn / f_ref, "mcd_dtw": nan, "mcd_dtw_sl": nan, "path_steps": 0, "off_diagonal": nan, "worst_symbol": None,
+                   "worst_symbol_mcd": None, "f0_rmse_cents": None, "vuv_error": None, "voiced_pairs": None, "lo": None, "hi": None}
+            if vocoder is not None:
+                rec["f0_rmse_cents"], rec["vuv_error"], rec["voiced_pairs"] = f0.get(j, (nan, nan, 0))
+            if notes[j] is not None:
+                rec["note"] = notes[j]
+            else:
+                mcd_j, steps_j, lo_j, hi_j, frame_j = warped[j]
+                diagonal = int((lo_j[1:] == hi_j[:-1] + 1).sum())
+                rec.update({"mcd_dtw": mcd_j, "mcd_dtw_sl": mcd_j * max(f_ref, f_syn) / max(min(f_ref, f_syn), 1), "path_steps": steps_j,
+                            "off_diagonal": 1.0 - diagonal / (steps_j - 1) if steps_j > 1 else 0.0, "lo": lo_j, "hi": hi_j})
+                if j in durs:
+                    ends = torch.cumsum(durs[j], 0).clamp(max=f_ref)
+                    starts = torch.cat([torch.zeros(1, dtype=ends.dtype), ends[:-1]])
+                    scores = [(float(frame_j[int(s) : int(e)].mean()), x) for x, (s, e) in enumerate(zip(starts, ends)) if e > s]
+                    if scores:
+                        rec["worst_symbol_mcd"], rec["worst_symbol"] = max(scores, key=lambda t: (t[0], -t[1]))
+            records.append(rec)
+    if out_path is not None:
+        GpuPreprocessor.write_filelist(records, out_path, fields=SYNTHESIS_EVALUATION_FIELDS)
     return records

@@ -1458,6 +1458,49 @@ def align_scores_plan(A, L):
     return ty.value, bool(klds.value)
 
 
+def dtw_cepstral(a, a_lens32, b, b_lens32, basis, scale, out=None, ws=None):
+    """Distortion along the dynamic-time-warping path (evmi_dtw_cepstral_f32): a [B, Ta, M], b [B, Tb, M] time-major float32, the
+    lengths int32 [B] on the device, basis [K, M] float32 -> (dist [B], steps [B] int32, lo [B, Tb] int32, hi [B, Tb] int32,
+    col [B, Tb]): scale x the mean cost along each item's path, the path's cells, its first and last row (of a) in each column (of b;
+    -1 beyond the item) and scale x the mean cost of the path's cells of each column.  Each item runs over its own lengths.
+    ``out`` / ``ws``: the five results and the uint8 workspace (``dtw_ws_bytes``; a torch allocation is aligned) where the caller
+    keeps them, e.g. for a captured call."""
+    B, Ta, M = a.shape
+    Tb = b.shape[1]
+    K = basis.shape[0]
+    if b.shape[0] != B or b.shape[2] != M or basis.shape[1] != M:
+        raise ValueError(f"dtw_cepstral: a {tuple(a.shape)}, b {tuple(b.shape)} and basis {tuple(basis.shape)} do not agree")
+    for name, t in (("a", a), ("b", b), ("basis", basis)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"dtw_cepstral: {name} must be contiguous float32")
+    n = dtw_ws_bytes(B, Ta, Tb)
+    if out is None:
+        dev = a.device
+        out = (torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.int32),
+               torch.empty(B, Tb, device=dev, dtype=torch.int32), torch.empty(B, Tb, device=dev, dtype=torch.int32),
+               torch.empty(B, Tb, device=dev, dtype=torch.float32))
+    if ws is None:
+        ws = WS.get("dtw_cepstral", (n + 3) // 4, a.device).view(torch.uint8)
+    dist, steps, lo, hi, col = out
+    _chk(_lib.load().evmi_dtw_cepstral_f32(a.data_ptr(), b.data_ptr(), a_lens32.data_ptr(), b_lens32.data_ptr(), basis.data_ptr(), dist.data_ptr(),
+                                           steps.data_ptr(), lo.data_ptr(), hi.data_ptr(), col.data_ptr(), ws.data_ptr(), ws.numel(), B, Ta, Tb, M, K,
+                                           scale, _s(a)), "evmi_dtw_cepstral_f32")
+    return dist, steps, lo, hi, col
+
+
+def dtw_ws_bytes(B, Ta, Tb):
+    return int(_lib.load().evmi_dtw_ws_bytes(B, Ta, Tb))
+
+
+def dtw_plan(K, Tb):
+    """(largest Ta, diagonals of one workspace flush) of evmi_dtw_cepstral_f32 at K cepstra and Tb columns: host arithmetic."""
+    import ctypes
+
+    max_ta, chunk = ctypes.c_int(0), ctypes.c_int(0)
+    _chk(_lib.load().evmi_dtw_plan(K, Tb, ctypes.byref(max_ta), ctypes.byref(chunk)), "evmi_dtw_plan")
+    return max_ta.value, chunk.value
+
+
 def align_attention_bwd(q, k, soft, logprob, prior, hard, dlogprob, text_lens32, temperature, bin_scale, bin_count=None):
     """-> (dq [A, B, T], dk [A, B, L]); ``bin_count``: device scalar the binarisation weight is divided by (the frame count)."""
     lib = _lib.load()

@@ -1129,6 +1129,33 @@ int evmi_align_scores_f32(const float* q_dev, const float* k_dev, const double* 
                           const int* mel_lens_dev, const int* dur_dev, float* ctc_dev, float* path_dev, float* symbol_dev, int A,
                           int B, int T, int L, float temperature, float blank_logprob, void* stream);
 
+/* Mel-cepstral distortion along the dynamic-time-warping path (csrc/dtw_cepstral.hip).  a [B][Ta][M] and
+ * b [B][Tb][M] are time-major feature sequences (a synthesized mel and its recording), basis [K][M] any linear map (a DCT), the
+ * lengths int32 in device memory, clamped to [0, Ta] / [0, Tb] (a captured call follows each batch).  One workgroup per item over
+ * its own Na x Nb rectangle.  All arithmetic fp32; each cell is a pure function of its three predecessors:
+ *   ca[i][k] = sum_m fmaf(basis[k][m], a[i][m], acc), m ascending from 0; cb likewise from b
+ *   c[i][j]  = sqrtf(s) (correctly rounded), s = fmaf(d_k, d_k, s), d_k = ca[i][k] - cb[j][k], k ascending, s from 0
+ *   D[0][0]  = c[0][0]; otherwise D[i][j] = c[i][j] + best: best is the diagonal D[i-1][j-1] where it exists, else +inf; then up,
+ *              D[i-1][j], if strictly smaller; then left, D[i][j-1], if strictly smaller
+ * The path is read back from (Na - 1, Nb - 1) to (0, 0):
+ *   steps[b]  the number of path cells;  dist[b] = scale * D[Na-1][Nb-1] / (float)steps
+ *   lo / hi [b][j]  the first and the last row of the path in column j (with steps (1,0), (0,1), (1,1) they are the whole path)
+ *   col[b][j] = scale * (sum_{i = lo .. hi} c[i][j], i ascending) / (float)(hi - lo + 1)
+ *   for j >= Nb: lo = hi = -1 and col = 0;  an item with Na == 0 or Nb == 0: dist NaN, steps 0, rows of -1, a zero col row
+ * An item's outputs are the same bits alone and in any batch, at any padded Ta and Tb; nothing beyond an item's extent of a and b
+ * is read, and no value in a, b or the workspace, NaN included, makes the kernel address memory outside the item or fail to
+ * terminate (a comparison with NaN is false and keeps the diagonal).  ws: evmi_dtw_ws_bytes bytes, 16-byte aligned (one decision
+ * byte a cell, diagonal-major, diagonals padded to 16 bytes).  1 <= K <= 24, Tb <= 1024 (a thread owns a column) and Ta <= max_ta of
+ * evmi_dtw_plan (the item's ca sits in LDS: at least 1024 at every K); more returns EVMI_ERR_UNSUPPORTED naming the limit.
+ * EVMI_ERR_INVALID_ARG: a null pointer, a size below 1, a workspace too small or misaligned.  Both before any device work.
+ * evmi_dtw_plan (host arithmetic, no GPU; the same refusals): the largest Ta at K and the diagonals of one workspace flush. */
+long long evmi_dtw_ws_bytes(int B, int Ta, int Tb);
+int evmi_dtw_plan(int K, int Tb, int* max_ta, int* diag_chunk);
+int evmi_dtw_cepstral_f32(const float* a_dev, const float* b_dev, const int* a_lens_dev, const int* b_lens_dev,
+                          const float* basis_dev, float* dist_dev, int* steps_dev, int* lo_dev, int* hi_dev, float* col_dev,
+                          unsigned char* ws_dev, long long ws_bytes, int B, int Ta, int Tb, int M, int K, float scale,
+                          void* stream);
+
 /* Global Style Token module of FastSpeech2 (csrc/gst.hip), fp32.
  * Reference encoder: 3 x 3 convolution with stride 2 and padding 1 on channel-major x [Cin][B][H][W] -> y [Cout][B][OH][OW],
  * O = (n - 1) / 2 + 1 on both axes, w [Cout][Cin][3][3], bias [Cout] or NULL; act 0 (none) or 3 (ReLU: the folded eval-mode
