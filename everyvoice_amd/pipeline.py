@@ -1279,3 +1279,178 @@ def evaluate_synthesis(model, filelist_data: list[dict], preprocessed_dir, batch
     if out_path is not None:
         GpuPreprocessor.write_filelist(records, out_path, fields=SYNTHESIS_EVALUATION_FIELDS)
     return records
+
+
+# ---- a vocoder against the recordings ------------------------------------------------------------------------
+STOI_SAMPLE_RATE = 10000  # the rate the measure is defined at
+STOI_HOP = 128            # samples between its frames at that rate
+
+
+class Stoi(NamedTuple):
+    """``stoi``'s results, on the device: stoi [B] (NaN without a segment), frames / active / segments [B] int32 (the frames of the
+    common length, those within 40 dB of the recording's loudest, and the 384 ms segments scored), segment_stoi [B, J_cap] (the mean
+    over the 15 bands of each segment; 0 beyond the item's), frame_of [B, F_cap] int32 (the original frame of each active frame: segment
+    s starts at sample 128 frame_of[s] of the 10 kHz signal; -1 beyond the item's)."""
+
+    stoi: torch.Tensor
+    frames: torch.Tensor
+    active: torch.Tensor
+    segments: torch.Tensor
+    segment_stoi: torch.Tensor
+    frame_of: torch.Tensor
+
+
+def third_octave_bands() -> list[tuple[int, int]]:
+    """The 15 one-third-octave bands of STOI as (first bin, one past the last bin) of a 512-point transform at 10 kHz: centres
+    150 x 2^(b/3) Hz, edges x 2^(-1/6) and x 2^(1/6), each snapped to the nearest of the 257 bins of linspace(0, 10000, 513); float64."""
+    f = np.linspace(0.0, float(STOI_SAMPLE_RATE), 513)[:257]
+    centres = 150.0 * 2.0 ** (np.arange(15, dtype=np.float64) / 3.0)
+    lo, hi = centres * 2.0 ** (-1.0 / 6.0), centres * 2.0 ** (1.0 / 6.0)
+    return [(int(np.argmin(np.abs(f - a))), int(np.argmin(np.abs(f - b)))) for a, b in zip(lo, hi)]
+
+
+def _rows_at_10k(wav: torch.Tensor, lens: torch.Tensor, sample_rate: int):
+    """[B, S] and lengths at ``sample_rate`` -> the same at 10 kHz: samples at or beyond an item's length zeroed, ``resample``, its length rule."""
+    if sample_rate == STOI_SAMPLE_RATE:
+        return wav.contiguous(), lens
+    g = math.gcd(sample_rate, STOI_SAMPLE_RATE)
+    orig, new = sample_rate // g, STOI_SAMPLE_RATE // g
+    inside = torch.arange(wav.shape[1], device=wav.device)[None, :] < lens[:, None]
+    return resample(torch.where(inside, wav, torch.zeros((), device=wav.device)), sample_rate, STOI_SAMPLE_RATE), (new * lens + orig - 1) // orig
+
+
+def stoi(ref_wav: torch.Tensor, ref_lens, deg_wav: torch.Tensor, deg_lens, sample_rate: int) -> Stoi:
+    """Short-time objective intelligibility (intrusive STOI: Taal, Hendriks, Heusdens, Jensen 2011, with the frame conventions of the
+    widely used open implementation) of ``deg_wav`` (a synthesis) against ``ref_wav`` (its recording): [B, S] or [B, 1, S] on the GPU
+    with their sample counts, one launch (``evmi_stoi_f32``), each item over its own min(length) samples, at most
+    ``ops.stoi_plan``'s limit (11 s and more) in the shorter padded row.
+
+    The measure is defined at 10 kHz.  At any other ``sample_rate`` both sides go through ``resample`` first (samples at or beyond an
+    item's length zeroed, so an item's value does not depend on its batch; lengths by ``resample``'s own rule).  Absolute values
+    therefore depend on this project's resampler in the fifth or sixth digit: they compare with the literature, not to the bit with a
+    tool that resamples otherwise."""
+    from .train import ops
+
+    r = ref_wav[:, 0] if ref_wav.dim() == 3 and ref_wav.shape[1] == 1 else ref_wav
+    d = deg_wav[:, 0] if deg_wav.dim() == 3 and deg_wav.shape[1] == 1 else deg_wav
+    lr, ld = torch.as_tensor(ref_lens), torch.as_tensor(deg_lens)
+    if r.dim() != 2 or d.dim() != 2 or r.shape[0] != d.shape[0] or tuple(lr.shape) != (r.shape[0],) or tuple(ld.shape) != (r.shape[0],):
+        raise ValueError(f"stoi: expected [B, S] or [B, 1, S] waveforms with [B] lengths, got {tuple(ref_wav.shape)} / {tuple(lr.shape)} and "
+                         f"{tuple(deg_wav.shape)} / {tuple(ld.shape)}")
+    if int(sample_rate) != sample_rate or sample_rate <= 0:
+        raise ValueError(f"stoi: sample_rate must be a positive integer, got {sample_rate!r}")
+    if not r.is_cuda:
+        raise RuntimeError("everyvoice_amd.pipeline.stoi computes on the GPU only (no CPU fallback)")
+    dev = r.device
+    r, d = r.to(torch.float32), d.to(dev, torch.float32)
+    lr, ld = lr.to(dev, torch.int64).clamp(0, r.shape[1]), ld.to(dev, torch.int64).clamp(0, d.shape[1])
+    r, lr = _rows_at_10k(r, lr, int(sample_rate))
+    d, ld = _rows_at_10k(d, ld, int(sample_rate))
+    value, counts, segment, frame_of = ops.stoi(r, lr.to(torch.int32).contiguous(), d, ld.to(torch.int32).contiguous())
+    return Stoi(value, counts[:, 0], counts[:, 1], counts[:, 2], segment, frame_of)
+
+
+VOCODER_EVALUATION_FIELDS = ("basename", "speaker", "language", "frames", "samples", "seconds", "mel_error", "stoi", "stoi_active", "stoi_segments",
+                             "stoi_worst", "stoi_worst_at", "f0_rmse_cents", "vuv_error", "voiced_pairs", "note")
+
+
+def _output_log_mel(cfg: AudioConfig):
+    """The log-spectrogram ``validation/mel_spec_error`` is measured with: ``spectral.vocoder_output_transform`` of ``cfg``, [B, S] -> log."""
+    from .spectral import vocoder_output_transform
+
+    t = vocoder_output_transform(cfg)
+    fn = get_spectral_transform(t["spec_type"], t["n_fft"], t["win_length"], t["hop_length"], t["filter_sample_rate"], t["n_mels"], t["f_min"], t["f_max"])
+    if t["spec_type"] == "mel":  # the torchaudio mel comes out linear: log(clamp(., 1e-5)) as the preprocessor applies it
+        from .train import ops
+
+        return lambda x: ops.elementwise(ops.EW_LOG_CLAMP, fn(x).contiguous(), p0=1e-5)
+    return lambda x: fn(x, log=True)
+
+
+def evaluate_vocoder(vocoder, filelist_data: list[dict], preprocessed_dir, batch_size: int = 16, audio_config: AudioConfig | None = None,
+                     out_path=None) -> list[dict]:
+    """How close a vocoder's copy-synthesis is to the recording, per utterance of a preprocessed dataset: the
+    copy-synthesis twin of ``evaluate_synthesis``.  Every row's ``spec/...--spec-<input_sr>-<spec_type>.pt`` is vocoded in ragged
+    batches (``vocoder(mel, lens=)``) and compared with ``audio/...--audio-<output_sr>.wav`` on the first ``samples`` = min(synthesized,
+    recorded) samples of both.  One record per row, in input order:
+    ``basename``, ``speaker``, ``language``, ``frames`` (of the spectrogram), ``samples``, ``seconds`` (samples / output_sr),
+    ``mel_error`` (the definition of ``validation/mel_spec_error``: the mean absolute difference of the log-spectrograms of both
+    signals through ``spectral.vocoder_output_transform``, per item on its own samples),
+    ``stoi`` (``stoi`` above, resampled to 10 kHz), ``stoi_active`` (active / all frames), ``stoi_segments``, ``stoi_worst`` /
+    ``stoi_worst_at`` (the lowest segment value and the time in seconds, in the recording, where that segment starts:
+    frame_of[s] x 128 / 10000),
+    ``f0_rmse_cents``, ``vuv_error``, ``voiced_pairs`` (``f0_agreement`` of ``extract_pitch(interpolate=False)`` of both at the output
+    rate and hop, paired frame by frame).
+    An utterance beyond ``ops.stoi_plan``'s limit, or without a segment (fewer than 31 active frames: under about 0.4 s), gets NaN in
+    the STOI fields and a ``note``, not an exception.  A record does not depend on ``batch_size`` or on its neighbours.
+    ``out_path``: the records as a pipe-separated file with a header line.
+    ``FileNotFoundError``: a missing spectrogram or recording, by name, before any device work on its batch."""
+    from .train import ops
+
+    cfg = audio_config if audio_config is not None else AudioConfig()
+    in_sr, out_sr = cfg.input_sampling_rate, cfg.output_sampling_rate
+    hop_out = cfg.fft_hop_size * (out_sr // in_sr)
+    spec_fn = f"spec-{in_sr}-{cfg.spec_type}.pt"
+    nan = float("nan")
+    rows = [dict(r) for r in filelist_data]
+    records = []
+    log_mel, max_n = None, None
+    for start in range(0, len(rows), batch_size):
+        chunk = rows[start : start + batch_size]
+        spk = [r.get("speaker") or "default" for r in chunk]
+        lang = [r.get("language") or "default" for r in chunk]
+        specs = [feature_path(preprocessed_dir, "spec", r["basename"], spk[j], lang[j], spec_fn) for j, r in enumerate(chunk)]
+        wavs = [feature_path(preprocessed_dir, "audio", r["basename"], spk[j], lang[j], f"audio-{out_sr}.wav") for j, r in enumerate(chunk)]
+        for r, p, q in zip(chunk, specs, wavs):
+            if not p.exists():
+                raise FileNotFoundError(f"evaluate_vocoder {r['basename']!r}: no spectrogram {p} to vocode")
+            if not q.exists():
+                raise FileNotFoundError(f"evaluate_vocoder {r['basename']!r}: no recording {q} to compare with")
+        dev = next(vocoder.parameters()).device
+        if log_mel is None:
+            log_mel, max_n = _output_log_mel(cfg), ops.stoi_plan(1)[0]
+        mels = [torch.load(p, weights_only=True).to(torch.float32) for p in specs]  # [n_mels, T] each
+        frames = torch.tensor([m.shape[1] for m in mels])
+        mel = torch.nn.utils.rnn.pad_sequence([m.transpose(0, 1) for m in mels], batch_first=True).transpose(1, 2).contiguous().to(dev)
+        syn = vocoder(mel, lens=frames.to(dev))[:, 0]
+        per_frame = syn.shape[1] // mel.shape[2]
+        recorded = [load_wav(q)[0][0] for q in wavs]
+        samples = [min(int(frames[j]) * per_frame, recorded[j].shape[0]) for j in range(len(chunk))]
+        ref = torch.nn.utils.rnn.pad_sequence([x[:n] for x, n in zip(recorded, samples)], batch_first=True).to(dev)
+        g = math.gcd(out_sr, STOI_SAMPLE_RATE)
+        at_10k = [(STOI_SAMPLE_RATE // g * n + out_sr // g - 1) // (out_sr // g) for n in samples]
+        notes = [f"more than {max_n} samples at 10 kHz ({at_10k[j]}): no STOI" if at_10k[j] > max_n else "no samples" if samples[j] == 0 else None
+                 for j in range(len(chunk))]
+        ok = [j for j in range(len(chunk)) if notes[j] is None]
+        scored = {}
+        if ok:
+            sel, lens = torch.tensor(ok, device=dev), torch.tensor([samples[j] for j in ok])
+            S = max(int(lens.max()), 1)
+            got = stoi(ref[sel, :S], lens, syn[sel, :S], lens, out_sr)
+            value, n_frames, active, segments, segment_stoi, frame_of = (t.cpu() for t in got)
+            scored = {j: (float(value[row]), int(n_frames[row]), int(active[row]), int(segments[row]), segment_stoi[row], frame_of[row])
+                      for row, j in enumerate(ok)}
+        for j, r in enumerate(chunk):
+            n = samples[j]
+            rec = {"basename": r["basename"], "speaker": spk[j], "language": lang[j], "frames": int(frames[j]), "samples": n, "seconds": n / out_sr,
+                   "mel_error": nan, "stoi": nan, "stoi_active": nan, "stoi_segments": 0, "stoi_worst": nan, "stoi_worst_at": nan,
+                   "f0_rmse_cents": nan, "vuv_error": nan, "voiced_pairs": 0}
+            if n > 0:
+                a, b = syn[j : j + 1, :n].contiguous(), ref[j : j + 1, :n].contiguous()
+                rec["mel_error"] = float((log_mel(a) - log_mel(b)).abs().mean())
+                f0_syn, f0_ref = (extract_pitch(x, None, hop_out, out_sr, interpolate=False)[0].cpu().numpy() for x in (a, b))
+                rec["f0_rmse_cents"], rec["vuv_error"], rec["voiced_pairs"] = f0_agreement(f0_syn, f0_ref, np.arange(len(f0_ref)))
+            if j in scored:
+                value, n_frames, active, segments, segment_stoi, frame_of = scored[j]
+                rec.update({"stoi": value, "stoi_active": active / n_frames if n_frames else nan, "stoi_segments": segments})
+                if segments > 0:
+                    worst = int(torch.argmin(segment_stoi[:segments]))
+                    rec.update({"stoi_worst": float(segment_stoi[worst]), "stoi_worst_at": int(frame_of[worst]) * STOI_HOP / STOI_SAMPLE_RATE})
+                else:
+                    notes[j] = f"fewer than 31 active frames ({active} of {n_frames}): no STOI segment"
+            if notes[j] is not None:
+                rec["note"] = notes[j]
+            records.append(rec)
+    if out_path is not None:
+        GpuPreprocessor.write_filelist(records, out_path, fields=VOCODER_EVALUATION_FIELDS)
+    return records

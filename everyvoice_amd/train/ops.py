@@ -1501,6 +1501,42 @@ def dtw_plan(K, Tb):
     return max_ta.value, chunk.value
 
 
+def stoi(ref, ref_lens32, deg, deg_lens32, out=None):
+    """Short-time objective intelligibility (evmi_stoi_f32): ref [B, S_ref] (the recording) and deg [B, S_deg] (the synthesis)
+    contiguous float32 AT 10 kHz, the lengths int32 [B] on the device -> (stoi [B], counts [B, 3] int32 = (frames, kept frames,
+    segments), segment [B, j_cap] (0 beyond the item's segments), frame_of [B, f_cap] int32 (the original index of each kept frame,
+    -1 beyond them)) with ``stoi_plan(min(S_ref, S_deg))``'s strides.  Each item runs over its own min(len_ref, len_deg) samples.
+    ``out``: the four results where the caller keeps them, e.g. for a captured call."""
+    if ref.dim() != 2 or deg.dim() != 2 or ref.shape[0] != deg.shape[0]:
+        raise ValueError(f"stoi: ref {tuple(ref.shape)} and deg {tuple(deg.shape)} do not agree")
+    for name, t in (("ref", ref), ("deg", deg)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"stoi: {name} must be contiguous float32")
+    B, S_ref = ref.shape
+    S_deg = deg.shape[1]
+    _, f_cap, j_cap = stoi_plan(max(min(S_ref, S_deg), 1))
+    if out is None:
+        dev = ref.device
+        out = (torch.empty(B, device=dev, dtype=torch.float32), torch.empty(B, 3, device=dev, dtype=torch.int32),
+               torch.empty(B, j_cap, device=dev, dtype=torch.float32), torch.empty(B, f_cap, device=dev, dtype=torch.int32))
+    value, counts, segment, frame_of = out
+    if (tuple(value.shape), tuple(counts.shape), tuple(segment.shape), tuple(frame_of.shape)) != ((B,), (B, 3), (B, j_cap), (B, f_cap)):
+        raise ValueError(f"stoi: out must be [{B}], [{B}, 3], [{B}, {j_cap}] and [{B}, {f_cap}]")
+    _chk(_lib.load().evmi_stoi_f32(ref.data_ptr(), deg.data_ptr(), ref_lens32.data_ptr(), deg_lens32.data_ptr(), value.data_ptr(), counts.data_ptr(),
+                                   segment.data_ptr(), frame_of.data_ptr(), B, S_ref, S_deg, _s(ref)), "evmi_stoi_f32")
+    return value, counts, segment, frame_of
+
+
+def stoi_plan(S):
+    """(largest min(S_ref, S_deg), f_cap, j_cap) of evmi_stoi_f32: the samples one workgroup's LDS takes and the row strides of
+    ``frame_of`` and ``segment`` at a padded length S: host arithmetic."""
+    import ctypes
+
+    max_n, f_cap, j_cap = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _chk(_lib.load().evmi_stoi_plan(S, ctypes.byref(max_n), ctypes.byref(f_cap), ctypes.byref(j_cap)), "evmi_stoi_plan")
+    return max_n.value, f_cap.value, j_cap.value
+
+
 def align_attention_bwd(q, k, soft, logprob, prior, hard, dlogprob, text_lens32, temperature, bin_scale, bin_count=None):
     """-> (dq [A, B, T], dk [A, B, L]); ``bin_count``: device scalar the binarisation weight is divided by (the frame count)."""
     lib = _lib.load()

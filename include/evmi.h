@@ -1156,6 +1156,35 @@ int evmi_dtw_cepstral_f32(const float* a_dev, const float* b_dev, const int* a_l
                           unsigned char* ws_dev, long long ws_bytes, int B, int Ta, int Tb, int M, int K, float scale,
                           void* stream);
 
+/* Short-time objective intelligibility of a synthesis against its recording (csrc/stoi.hip): intrusive STOI of
+ * Taal, Hendriks, Heusdens and Jensen (2011) with the frame-count conventions of the widely used open implementation.  ref [B][S_ref]
+ * (the recording) and deg [B][S_deg] (the synthesis) are fp32 waveforms AT 10 kHz, the lengths int32 in device memory, clamped to
+ * [0, S_ref] / [0, S_deg] (a captured call follows each batch).  One launch, one workgroup per item over its own
+ * n = min(len_ref, len_deg) samples; all arithmetic fp32, every sum in a fixed order, no float atomics.  Constants: frame 256, hop 128,
+ * transform 512, 15 bands, N = 30, beta = -15 dB, range 40 dB, eps = 2.220446049250313e-16.
+ *   w = hanning(258)[1:-1];  frames start at 128 i for every i with 128 i < n - 256: F = ceil((n - 256) / 128) for n > 256, else 0
+ *   e_i = 20 log10(||w . ref frame i|| + eps);  frame i is kept iff max_i e_i - 40 - e_i < 0 (the same frames of deg); K kept frames
+ *   the kept windowed frames overlap-added at hop 128 and framed and windowed again give K - 1 frames; their band values are
+ *   sqrt(sum of |DFT_512|^2 over the band's bins), bands [7,9) [9,11) [11,14) [14,17) [17,22) [22,27) [27,34) [34,43) [43,55) [55,69)
+ *   [69,87) [87,109) [109,138) [138,174) [174,219)
+ *   segments m = 30 .. K - 1 over columns m - 30 .. m - 1, J = K - 30 for K >= 31, else 0; per segment and band with x, y the 30
+ *   values of ref and deg: c = ||x|| / (||y|| + eps), y' = min(c y, x (1 + 10^(15/20))), both minus their mean and over
+ *   (their norm + eps), rho = their inner product
+ * Outputs per item: stoi[b] = the mean of rho over all 15 J values (NaN when J == 0); counts[b] = (F, K, J); segment[b][s] = the mean
+ * of rho over the 15 bands of segment s, 0 for s >= J; frame_of[b][k] = the original index of kept frame k, -1 for k >= K.  The rows of
+ * segment and frame_of have j_cap and f_cap entries, evmi_stoi_plan's values at S = min(S_ref, S_deg).
+ * An item's outputs are the same bits alone and in any batch, at any padded S_ref / S_deg.  Nothing beyond an item's n samples is
+ * read.  No value in the inputs, NaN and Inf included, makes the kernel address memory outside the item or fail to terminate: the
+ * only data-dependent index is the compaction count, bounded by F (a frame with a NaN energy is dropped, an Inf drops every frame).
+ * An all-zero reference keeps every frame and scores 0.
+ * min(S_ref, S_deg) <= max_n of evmi_stoi_plan (the band values of every frame sit in one workgroup's LDS: at least 110000 samples, 11 s);
+ * more returns EVMI_ERR_UNSUPPORTED naming the limit.  EVMI_ERR_INVALID_ARG: a null pointer, a size below 1.  Both before any device
+ * work.  evmi_stoi_plan (host arithmetic, no GPU): the largest n, and the row strides f_cap = max(F(S), 1) and j_cap = max(F(S) - 30, 1)
+ * at min(S, max_n). */
+int evmi_stoi_plan(int S, int* max_n, int* f_cap, int* j_cap);
+int evmi_stoi_f32(const float* ref_dev, const float* deg_dev, const int* ref_lens_dev, const int* deg_lens_dev, float* stoi_dev,
+                  int* counts_dev, float* segment_dev, int* frame_of_dev, int B, int S_ref, int S_deg, void* stream);
+
 /* Global Style Token module of FastSpeech2 (csrc/gst.hip), fp32.
  * Reference encoder: 3 x 3 convolution with stride 2 and padding 1 on channel-major x [Cin][B][H][W] -> y [Cout][B][OH][OW],
  * O = (n - 1) / 2 + 1 on both axes, w [Cout][Cin][3][3], bias [Cout] or NULL; act 0 (none) or 3 (ReLU: the folded eval-mode
